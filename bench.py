@@ -7,12 +7,17 @@ ResNet-v2-50 regressor -> mesh -> multi-grid warp -> feedback push.  Frames of a
 Inputs (the synthetic 720p clip) are resident in HBM before the timed region.
 
   python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full   # + roofline pass and per-kernel table, f32-MFMA and bf16 legs,
+                                                            #   CPU baseline, train leg, empirical peaks (each has a --no-* switch)
+  python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR   # + the last timed step's results as DIR/<name>.npy
   python bench.py --gpus N --steps K --warmup W        # N > 1 without a torchrun environment: this process starts N
                                                        # fresh child ranks itself (before it touches the GPU), relays
                                                        # rank 0's JSON line and exits non-zero if fewer than N came up
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W        # the driver's form: one rank per GPU over RCCL
 `n_gpus` in the line is the number of ranks the process group really has, never the flag.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line; everything else it can
+measure runs only with --full.
 """
 import argparse
 import json
@@ -31,13 +36,42 @@ PEAK_HBM_GBPS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec
 PEAK_BF16_MFMA_TFLOPS = 2516.6   # v_mfma_f32_32x32x16_bf16: 32 cycles per 32x32x16 on each of 256 CUs x 4 SIMDs at 2.4 GHz (~2.5 PF dense)
 SPLIT_PRODUCTS = 6               # bf16 x bf16 partial products per f32 product in operand mode 4 (conv_kernel.h)
 PEAK_SPLIT_F32_TFLOPS = PEAK_BF16_MFMA_TFLOPS / SPLIT_PRODUCTS   # f32-equivalent matrix peak of the packed split kernels
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs: all files together, .npy headers included
+NPY_HEADER_BYTES = 256           # allowance per file (np.save pads a header of simple arrays to 128 bytes)
 
 
 def is_packed_kernel(name):
     return name.startswith("conv_ring_f32_kernel<") and name.split(",")[1].strip() in ("4", "5")
 
 
-def parse():
+def leg(args, skipped):
+    """A measurement beyond the headline runs only with --full, and not when its own --no-* switch is given."""
+    return args.full and not skipped
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """{name: tensor or array} -> out_dir/<name>.npy; float64 stays float64, everything else is written as float32.  The arrays
+    share `budget` bytes, smallest first: one larger than what is left to it per remaining array is replaced by the values at a
+    fixed set of flat indices (seeded, sorted), so the same arguments always dump the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left = budget - NPY_HEADER_BYTES * len(host)
+    names = sorted(host, key=lambda k: (host[k].nbytes, k))
+    for i, name in enumerate(names):
+        a = host[name]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return names
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200 frames; --mode train: 50 optimiser steps, SURVEY 8d)")
@@ -56,7 +90,7 @@ def parse():
     ap.add_argument("--train-batch", type=int, default=8, help="pairs per GPU (weak scaling)")
     ap.add_argument("--train-height", type=int, default=288)
     ap.add_argument("--train-width", type=int, default=512)
-    ap.add_argument("--train-steps", type=int, default=30, help="steps of the extra train leg of the default run (5 warm-up steps)")
+    ap.add_argument("--train-steps", type=int, default=30, help="steps of the train leg of a --full run (5 warm-up steps)")
     ap.add_argument("--no-train-leg", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch the frame eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-bf16-leg", action="store_true", help="skip the SECONDARY bf16-operand line (never the headline)")
@@ -67,12 +101,23 @@ def parse():
     ap.add_argument("--no-f32-mfma-leg", action="store_true", help="skip the second figure taken with --operand-mode 0")
     ap.add_argument("--dump-event-raw", default=None, metavar="JSON",
                     help="write {kernel: raw HIP-event average} of the instrumented pass (tools/profile_stamp.py calibrates the "
-                         "per-kernel event offsets against rocprofv3 with it)")
-    a = ap.parse_args()
+                         "per-kernel event offsets against rocprofv3 with it); needs --full")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the instrumented roofline pass and per-kernel table, the f32-MFMA and bf16-operand "
+                         "legs, the CPU baseline, the train leg and the empirical peaks (each still skipped by its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, loss "
+                         "terms float64; %d MB at most in all: a larger output is replaced by a fixed seeded sample)" % (
+                             DUMP_BUDGET_BYTES // 10**6))
+    a = ap.parse_args(argv)
     if a.steps is None:
         a.steps = 50 if a.mode == "train" else 200
     if a.warmup is None:
         a.warmup = 10 if a.mode == "train" else 20
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_event_raw and not a.full:
+        ap.error("--dump-event-raw needs --full (it dumps the instrumented pass)")
     return a
 
 
@@ -131,9 +176,26 @@ def empirical_peaks(dev):
                    "float4 per thread, read+write bytes)"}
 
 
-def train_leg(args, dev, dist, rank, world, steps, warmup, with_prof):
+def train_dump_arrays(tr):
+    """What a caller of the training step receives from its last call: both towers' theta and warp results, the loss terms
+    (float64, as Trainer.losses() reads them back), the step's gradient and the updated trainables."""
+    out = {}
+    for k, t in enumerate(tr.last["towers"]):
+        out["theta%d" % (k + 1)] = tr.theta[k]
+        for key in ("output", "black_pix", "x_map", "y_map", "Hs"):
+            out["%s%d" % (key, k + 1)] = t[key]
+    for key, v in tr.losses().items():
+        if not isinstance(v, dict):
+            out["loss_" + key] = np.float64(v)
+    out["grad"] = tr.grad_flat()
+    out["params"] = tr.params
+    return out
+
+
+def train_leg(args, dev, dist, rank, world, steps, warmup, with_prof, dump_dir=None):
     """BASELINE configs[2]/[3]: one optimiser step = `train_batch` siamese pairs per GPU at 288x512, full forward +
-    backward (incl. warp gradient) + Adam, gradient all-reduce over RCCL when world > 1.  Returns a dict."""
+    backward (incl. warp gradient) + Adam, gradient all-reduce over RCCL when world > 1.  Returns a dict.  dump_dir: write
+    what the last timed step computed there (--dump-outputs)."""
     from stabnet_amd import synthetic
     from stabnet_amd.config import Config
     from stabnet_amd.deploy import Profiler
@@ -181,6 +243,8 @@ def train_leg(args, dev, dist, rank, world, steps, warmup, with_prof):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
         dist.barrier()
+    if dump_dir is not None:
+        dump_outputs(dump_dir, train_dump_arrays(tr))
     out = {"value": steps * N * world / el, "unit": "pairs/s", "ms_per_step": 1e3 * el / steps, "steps": steps,
            "warmup": warmup, "pairs_per_gpu": N, "global_batch": N * world, "height": H, "width": W,
            "tower_fwd_gflop": tr.plan.flops / 1e9, "loss": tr.losses()["total_loss"] if rank == 0 else None,
@@ -488,7 +552,8 @@ def main():
     from stabnet_amd.deploy import Profiler, StabNetStream
 
     if args.mode == "train":
-        t = train_leg(args, dev, dist, rank, world, args.steps, args.warmup, not args.no_roofline)
+        t = train_leg(args, dev, dist, rank, world, args.steps, args.warmup, leg(args, args.no_roofline),
+                      dump_dir=args.dump_outputs if rank == 0 else None)
         if rank == 0:
             line = {"metric": "train samples/sec (siamese pairs, 288x512)", "value": t["value"], "unit": "pairs/s",
                     "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": t["ms_per_step"],
@@ -532,7 +597,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        stream.step(frames[t % args.clip_frames])
+        res = stream.step(frames[t % args.clip_frames])
         t += 1
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -541,6 +606,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     barrier()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)     # before anything below steps the stream again
     checksum = float(stream.out_img.double().sum().item())
     from stabnet_amd import _lib as _sl
     plan_flops, plan_launches = stream.reg.plan.flops, stream.reg.plan.num_launches
@@ -548,7 +615,7 @@ def main():
     graph_used = stream._graph is not None
 
     roof, table, prof_ms, roof_warp = None, None, None, None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and leg(args, args.no_roofline):
         # the same K steps again with an event pair around every launch (instrumentation kept out of `value`)
         prof = Profiler(max_records=args.steps * (stream.reg.plan.num_launches + 16))
         prof.calibrate()
@@ -582,7 +649,7 @@ def main():
         annotate_roofline(roof, ktab, knote, prof)
 
     f32leg = None
-    if rank == 0 and args.operand_mode != 0 and not args.no_f32_mfma_leg:
+    if rank == 0 and args.operand_mode != 0 and leg(args, args.no_f32_mfma_leg):
         # the same frames on the exact f32 MFMA kernels (operand mode 0: the headline of rounds 1-3), and what separates the two
         # modes on ONE frame from identical ring state
         s0 = StabNetStream(P, H, W, cfg, streams=S, device=dev, refine=args.refine, use_graph=not args.no_graph, operand_mode=0)
@@ -608,7 +675,7 @@ def main():
                   "theta_max_abs_dev_headline_vs_this": float((a - b).abs().max().item()), "theta_scale": float(b.abs().max().item())}
         del s0
     bf16 = None
-    if rank == 0 and not args.no_bf16_leg:
+    if rank == 0 and leg(args, args.no_bf16_leg):
         # SECONDARY, labelled: the same frames with the conv operands rounded to bf16 at fragment-read time (fp32 tensors,
         # fp32 accumulate).  Reported beside the fp32 headline with the deviation it costs; `value` stays the fp32 figure.
         th32 = stream.theta.clone()
@@ -636,14 +703,14 @@ def main():
                 "theta_max_abs_dev_vs_headline": float((a - b).abs().max().item()), "theta_scale": float(a.abs().max().item())}
         del s16, th32
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and leg(args, args.no_cpu_baseline):
         cpu = cpu_baseline(P, clip, H, W, args.cpu_baseline_seconds)
     train = None
-    if not args.no_train_leg:
+    if leg(args, args.no_train_leg):
         del stream
         torch.cuda.empty_cache()
-        train = train_leg(args, dev, dist, rank, world, args.train_steps, 5, not args.no_roofline)
-    peaks = empirical_peaks(dev) if (rank == 0 and not args.no_roofline) else None
+        train = train_leg(args, dev, dist, rank, world, args.train_steps, 5, leg(args, args.no_roofline))
+    peaks = empirical_peaks(dev) if (rank == 0 and leg(args, args.no_roofline)) else None
 
     if dist is not None:
         dist.barrier()

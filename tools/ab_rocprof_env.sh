@@ -7,7 +7,7 @@ cd /tmp
 for v in $A $B $A $B; do
   export $VAR=$v
   rm -rf $O/_ab_$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/_ab_$v -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-train-leg --no-bf16-leg --no-roofline > $O/${TAG}_$v.json 2> $O/${TAG}_$v.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/_ab_$v -- python3 $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-train-leg --no-bf16-leg --no-roofline > $O/${TAG}_$v.json 2> $O/${TAG}_$v.err || exit 1
   cp $(find $O/_ab_$v -name "*kernel_stats.csv" | head -1) $O/${TAG}_${v}_stats.csv
   rm -rf $O/_ab_$v
   python3 -c "import json; d=json.load(open('$O/${TAG}_$v.json')); print('$VAR=$v', round(d['value'],1), 'fps', round(d['ms_per_step'],4), 'ms')"
