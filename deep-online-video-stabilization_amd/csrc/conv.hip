@@ -440,7 +440,17 @@ static int launch_ring_pro(ConvArgs a, long delta, hipStream_t st) {
 
 // 1 if conv_launch() of this (planned) convolution is followed by a split-K reduce launch (plan-time view: the prologue is known
 // from in_scale_expected)
+static int conv_reduce_launches_in_mode(const ConvArgs& a, int operand_mode);
 int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
+    // conv_kgroups / ring_pro_geometry read the launch's operand mode (set by conv_launch, mode 4 -> 0 wherever the packed kernel does
+    // not take the launch): evaluate the model in the mode it is asked about, not in whatever mode the thread's last launch left
+    const int saved = g_bf16_operands;
+    g_bf16_operands = operand_mode == 4 ? 0 : operand_mode;
+    const int n = conv_reduce_launches_in_mode(a, operand_mode);
+    g_bf16_operands = saved;
+    return n;
+}
+static int conv_reduce_launches_in_mode(const ConvArgs& a, int operand_mode) {
     if (a.splitk < 2) return 0;
     int splitk_unused = 1;
     const int t = pick_tile(a, splitk_unused);
@@ -461,6 +471,30 @@ int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
 // ---- pre-split weight image (conv.h) -----------------------------------------------------------------------------------
 size_t conv_weight_image_floats(int Cout, int K) { return (size_t)cdiv(Cout, 64) * (size_t)(K / 32) * 3072; }
 
+// sn_split3 with a saturating head: a finite |w| >= 2^127 (2 - 2^-8) rounds to a bf16 infinity (h = inf, m = -inf, l = NaN for
+// FLT_MAX); its head is the largest finite bf16 (0x7F7F) instead, and h + m + l == w stays exact (FLT_MAX = (2^128 - 2^120) + 2^120
+// - 2^104).  Fold time only (the weight image); infinities and NaN keep h = w.
+__device__ __forceinline__ unsigned weight_split_head(float& x0, float& x1) {
+    const float top = __builtin_bit_cast(float, 0x7F7F0000u), fmax = __builtin_bit_cast(float, 0x7F7FFFFFu);
+    const float h0 = (fabsf(x0) > top && fabsf(x0) <= fmax) ? copysignf(top, x0) : x0;
+    const float h1 = (fabsf(x1) > top && fabsf(x1) <= fmax) ? copysignf(top, x1) : x1;
+    const unsigned p = sn_pack_bf16(h0, h1);
+    x0 = sn_sub_f32(x0, __builtin_bit_cast(float, p << 16));
+    x1 = sn_sub_f32(x1, __builtin_bit_cast(float, p & 0xffff0000u));
+    return p;
+}
+__device__ __forceinline__ SnSplit3 weight_split3(const f32x4 x) {
+    float a = x.x, b = x.y, c = x.z, d = x.w;
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 h, m, l;
+    h.x = weight_split_head(a, b); h.y = weight_split_head(c, d);
+    m.x = sn_split_level(a, b); m.y = sn_split_level(c, d);
+    l.x = sn_pack_bf16(a, b); l.y = sn_pack_bf16(c, d);
+    SnSplit3 s;
+    s.h = __builtin_bit_cast(sn_bf16x4, h); s.m = __builtin_bit_cast(sn_bf16x4, m); s.l = __builtin_bit_cast(sn_bf16x4, l);
+    return s;
+}
+
 // one thread per (N tile, K step, wave column, k group, lane): 8 weights -> three 16-byte plane entries
 __device__ __forceinline__ void weight_split_image_thread(const float* __restrict__ w, int Cout, int K, uint4* __restrict__ img, long i) {
     const int steps = K / 32;
@@ -474,7 +508,7 @@ __device__ __forceinline__ void weight_split_image_thread(const float* __restric
         lo = *reinterpret_cast<const f32x4*>(r);
         hi = *reinterpret_cast<const f32x4*>(r + 8);
     }
-    const SnSplit3 a = sn_split3(lo), b = sn_split3(hi);
+    const SnSplit3 a = weight_split3(lo), b = weight_split3(hi);
     uint4* out = img + ts * 768 + (size_t)(wn * 6 + j) * 64 + lane;       // 16-byte units: stage 768, chunk 64
     out[0] = __builtin_bit_cast(uint4, SN_CAT8(a.h, b.h));
     out[2 * 64] = __builtin_bit_cast(uint4, SN_CAT8(a.m, b.m));
@@ -574,19 +608,21 @@ int conv_launch(const ConvArgs& a_in, hipStream_t st, Prof* prof, int bf16_opera
     }
     const int mode = (a.up > 1 || a.rowrun) ? 2 : (a.pad == 0 ? 0 : 1);
     const bool b_has_pro = a.in_scale != nullptr;           // (the packed launchers pick the prologue form from the pointer)
-    int kind = PK_KERNEL_CONV_RING + mode + (bf16_operands ? 3 : 0);
+    // the read-time split modes (2 / 3) have kinds of their own (prof.h PK_KERNEL_CONV_SPLIT): their ring, K-group and PRO launches
+    const int split = (bf16_operands == 2 || bf16_operands == 3) ? PK_KERNEL_CONV_SPLIT + 8 * (bf16_operands - 2) : 0;
+    int kind = split ? split + mode : PK_KERNEL_CONV_RING + mode + (bf16_operands ? 3 : 0);
     if (packed) {
         kind = packed_kg2 ? (b_has_pro ? PK_KERNEL_CONV_PACKED + 6 : PK_KERNEL_CONV_PACKED + 4 + mode)
                           : (b_has_pro ? PK_KERNEL_CONV_PACKED + 3 : PK_KERNEL_CONV_PACKED + mode);
     } else if (pro) {
-        kind = PK_KERNEL_CONV_KG + 2;
+        kind = split ? split + 5 : PK_KERNEL_CONV_KG + 2;
     } else if (kg > 1) {
-        kind = kg == 2 ? PK_KERNEL_CONV_KG + 3 : PK_KERNEL_CONV_KG + mode;
-    } else if (!ring) {                                                  // + 18 for the one-stage (NBUF = 1), + 36 for the bf16-operand instantiation
+        kind = split ? split + (kg == 2 ? 6 : 3 + mode) : (kg == 2 ? PK_KERNEL_CONV_KG + 3 : PK_KERNEL_CONV_KG + mode);
+    } else if (!ring) {                                                  // + 18 for the one-stage (NBUF = 1), + 36 per BF16 (operand mode 1..3)
         int bm, bn, nbuf, bf16;
         tile_dims(t, bm, bn);
         igemm_variant(a, bm, bn, bk32 ? 32 : 16, mode, nbuf, bf16);
-        kind = PK_KERNEL_CONV_BASE + mode * 6 + t * 2 + (bk32 ? 1 : 0) + (nbuf == 1 ? 18 : 0) + (bf16 ? 36 : 0);
+        kind = PK_KERNEL_CONV_BASE + mode * 6 + t * 2 + (bk32 ? 1 : 0) + (nbuf == 1 ? 18 : 0) + 36 * bf16;
     }
     if (rec) prof->end(st, kind, 2.0 * a.M * (double)(a.KH * a.KW * (a.cin_real ? a.cin_real : a.Cin)) * a.Cout,
                        // algorithmic bytes: input + weights + output (or the split-K slabs) + the residual read
@@ -695,7 +731,7 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
     SN_REQUIRE(c2.div_hw_mul != 0 && c3.div_hw_mul != 0 && c2.M == c3.M, "conv b2b: conv_plan() not called on both convolutions");
     SN_REQUIRE(c2.x && c2.w && c3.w && c3.y && c2.out_scale && c2.out_shift, "conv b2b: null pointer");
     SN_REQUIRE(c2.bias == nullptr && c2.residual == nullptr, "conv b2b: the 3x3 convolution takes no bias / residual");
-    SN_REQUIRE(g_bf16_operands == 0, "conv b2b: fp32 only");
+    g_bf16_operands = 0;                                              // exact f32 only: the launch's mode, whatever the last launch left
     const int cus = device_cus();
     if (cus <= 0) {
         stabnet_set_error("conv: cannot read the CU count");

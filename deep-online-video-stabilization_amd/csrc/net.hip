@@ -541,6 +541,11 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
 // head (head.hip) they ride in the output layer's launch; `done` tells the caller whether run_forward did them.
 struct MeshTail { int gh, gw; float lim; float* Hs; int* head_adv; int depth; bool done; const float* prefetch_src = nullptr; /* the frame the sampler behind the mesh gathers from */ };
 
+// S_CONV_B2B steps: the fused kernel is exact f32 -- operand modes 0 and 4 run it (mode 4 has no weight images for these convolutions and
+// runs the exact-f32 kernels wherever no packed kernel takes a launch); modes 1 / 2 / 3 run conv2 and conv3 as two launches in their
+// own mode.  run_forward and stabnet_net_num_launches both follow this.
+static bool b2b_fused(const Net* net) { return net->bf16_operands == 0 || net->bf16_operands == 4; }
+
 static int run_forward(const Net* net, const float* params, const float* fold, const float* x, float* theta,
                        float* ws, hipStream_t st, Prof* prof = nullptr, bool skip_pad = false, MeshTail* mesh = nullptr) {
     float* splitk = ws + net->act_floats;
@@ -593,11 +598,11 @@ static int run_forward(const Net* net, const float* params, const float* fold, c
                 b.residual = s.res_off >= 0 ? ws + s.res_off : nullptr;
                 if (s.obn_off >= 0) { b.out_scale = scale + s.obn_off; b.out_shift = shift + s.obn_off; b.relu_out = 1; }
                 a.partial = b.partial = splitk;
-                if (net->bf16_operands) {                  // the fused kernel is fp32 only: the secondary mode runs the two launches
-                    rc = conv_launch(a, st, prof, 1);
-                    if (!rc) rc = conv_launch(b, st, prof, 1);
-                } else {
+                if (b2b_fused(net)) {
                     rc = conv_b2b_launch(a, b, st, prof);
+                } else {                                   // modes 1 / 2 / 3: the two convolutions in the plan's own mode
+                    rc = conv_launch(a, st, prof, net->bf16_operands);
+                    if (!rc) rc = conv_launch(b, st, prof, net->bf16_operands);
                 }
                 break;
             }
@@ -743,14 +748,21 @@ const char* stabnet_prof_kind_name(int kind) {
         snprintf(pbuf[i], sizeof(pbuf[i]), "conv_ring_f32_kernel<%d, %d, %d, %d>", shape[i][0], conv_packed_variant(), shape[i][1], shape[i][2]);
         return pbuf[i];
     }
+    if (kind >= PK_KERNEL_CONV_SPLIT && kind < PK_KERNEL_CONV_SPLIT + 16 && (kind - PK_KERNEL_CONV_SPLIT) % 8 < 7) {   // modes 2 / 3
+        static const int shape[7][3] = {{0, 1, 0}, {1, 1, 0}, {2, 1, 0}, {0, 3, 0}, {1, 3, 0}, {0, 1, 1}, {0, 2, 1}};   // MODE, KG, PRO
+        static thread_local char sbuf[16][48];
+        const int i = kind - PK_KERNEL_CONV_SPLIT, s = i % 8;
+        snprintf(sbuf[i], sizeof(sbuf[i]), "conv_ring_f32_kernel<%d, %d, %d, %d>", shape[s][0], 2 + i / 8, shape[s][1], shape[s][2]);
+        return sbuf[i];
+    }
     if (kind == PK_KERNEL_CONV_B2B) return "conv_b2b_f32_kernel<2>";
     if (kind == PK_KERNEL_CONV_B2B + 1) return "conv_b2b_f32_kernel<4>";
-    if (kind >= PK_KERNEL_CONV_BASE && kind < PK_KERNEL_CONV_BASE + 72) {
+    if (kind >= PK_KERNEL_CONV_BASE && kind < PK_KERNEL_CONV_BASE + 144) {
         // names as rocprofv3 prints the template instantiation: <BM, BN, BK, WM, WN, MODE, NBUF, BF16>
-        // (kind = base + MODE*6 + tile*2 + (BK==32) + 18 if NBUF == 1 + 36 if BF16, conv.hip)
+        // (kind = base + MODE*6 + tile*2 + (BK==32) + 18 if NBUF == 1 + 36 * BF16, conv.hip)
         static thread_local char buf[96];
         int k = kind - PK_KERNEL_CONV_BASE;
-        const int bf16 = k >= 36 ? 1 : 0;
+        const int bf16 = k / 36;
         k -= 36 * bf16;
         const int nbuf = k >= 18 ? 1 : 2;
         k -= (nbuf == 1) ? 18 : 0;
@@ -823,8 +835,9 @@ int stabnet_net_num_launches(const void* netp) {
     int n = 0;
     // (shortened head: GAP partials + fc_1 = 2 launches, fc_2, fc_3, output layer [+ mesh] = 3; else 2 + 4 x fc_launches)
     for (const Step& s : net->steps) {
-        if (s.kind == S_CONV_B2B && net->bf16_operands) n += 2 + conv_reduce_launches(s.conv) + conv_reduce_launches(s.conv_b);   // runs as two launches there
-        else n += (s.kind == S_CONV) ? 1 + conv_reduce_launches(s.conv, (net->bf16_operands == 4 && s.wimg_off >= 0) ? 4 : 0)
+        const int mode = net->bf16_operands;       // (mode 4 without a weight image: conv_launch runs the exact-f32 kernels)
+        if (s.kind == S_CONV_B2B) n += b2b_fused(net) ? 1 : 2 + conv_reduce_launches(s.conv, mode) + conv_reduce_launches(s.conv_b, mode);
+        else n += (s.kind == S_CONV) ? 1 + conv_reduce_launches(s.conv, (mode == 4 && s.wimg_off < 0) ? 0 : mode)
                                      : (s.kind == S_FC ? fc_launches(s.M) : (s.kind == S_GAP ? 2 : 1));
     }
     if (head_fused_supported(net->N, net->t_last.C, net->fc_dims)) n -= 1 /* gap_finalize */ + (fc_launches(net->N) - 1) * 2;

@@ -96,7 +96,10 @@ int stabnet_conv2d_fwd_ex(const float* x, const float* w_ohwi, const float* bias
  * multiple of 32) the kernel reads; w_ohwi must still be passed (geometries the packed kernel does not take -- Cin % 32 != 0,
  * other tiles -- run stabnet_conv2d_fwd_ex's exact-f32 kernels on it).  splitk > 0 forces the K split (2 with equal halves runs
  * inside the workgroup, others through `workspace` slabs + a reduce launch); 0 = the planned one.  workspace: at least
- * max(stabnet_conv2d_workspace_bytes(), splitk * N*Ho*Wo*Cout * 4). */
+ * max(stabnet_conv2d_workspace_bytes(), splitk * N*Ho*Wo*Cout * 4).  The image splits every finite weight exactly (|w| >= 2^-110;
+ * within 2^-133 below), FLT_MAX included; x must be finite with |x| in [2^-110, 2^127 (2 - 2^-8)) for f32-equal results (same split
+ * limits; the run-time split of x does not saturate: a larger finite x gives NaN).  Non-finite inputs give non-finite outputs over
+ * their receptive fields, NaN where stabnet_conv2d_fwd_ex gives +-inf (0 behind relu_out, where fwd_ex gives +inf). */
 size_t stabnet_conv_weight_image_floats(int Cout, int KH, int KW, int Cin);
 int stabnet_conv_weight_split_image(const float* w_ohwi, int Cout, int KH, int KW, int Cin, float* w_img, void* stream);
 int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
@@ -139,6 +142,11 @@ void stabnet_net_destroy(void* net);
  *      as the reference form of mode 4;
  *   4  packed split: the weights are split once into a fragment-major image inside `fold` (stabnet_net_fold_bn), only the A
  *      fragments are split at run time (conv_ring_f32_kernel<MODE, 4, KG, PRO>).  Same f32-level parity bar as mode 0.
+ *      Range: mode 4 equals f32 for finite weights of any magnitude (the image's head saturates at the largest finite bf16) and for
+ *      finite activations of magnitude in [2^-110, 2^127 (2 - 2^-8)); both splits are exact down to 2^-110 and within 2^-133 (absolute)
+ *      below it, and the run-time split of the activations does not saturate: a larger finite activation gives NaN (out of contract).
+ *      Non-finite operands give non-finite outputs, but NaN where f32 gives +-inf, and a ReLU epilogue turns that NaN into 0 (fmaxf).
+ *   S_CONV_B2B units of a plan (STABNET_CONV_B2B_PLAN=1) run the fused exact-f32 kernel in modes 0 and 4, two launches in modes 1 - 3.
  * Training plans (keep_activations = 1) accept 0 and 4 only; 4 = the step's weight-operand launches (the prologue-carrying 1x1
  * forward pairs, the stride-1 dgrad launches) read images of the forward weights and of the re-packed dgrad weights that the step
  * writes itself, inside its workspace -- call it BEFORE stabnet_net_train_workspace_bytes().  Off by default in the Python

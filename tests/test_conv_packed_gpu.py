@@ -111,6 +111,56 @@ def test_weight_image_is_an_exact_three_term_split(cuda):
     assert not raw[1, :, 1].any()
 
 
+def _image_planes(img, Cout, K):
+    """h, m, l (float32, [Cout][K]) of every weight from a fragment-major image: [N tile][K step][wn][plane][j][lane][e]."""
+    raw = img.cpu().numpy().view(np.uint16).reshape((Cout + 63) // 64, K // 32, 2, 3, 2, 64, 8)
+    f = (raw.astype(np.uint32) << 16).view(np.float32)
+    n, k = np.meshgrid(np.arange(Cout), np.arange(K), indexing="ij")
+    kk = k % 32
+    j, rem = kk // 16, kk % 16
+    lane = n % 32 + 32 * ((rem % 8) // 4)
+    e = 4 * (rem // 8) + rem % 4
+    return [f[n // 64, k // 32, (n % 64) // 32, p, j, lane, e] for p in range(3)]
+
+
+def test_weight_image_split_over_the_whole_float32_range(cuda):
+    """The weight image (fold time) over every float32 class: finite |w| >= 2^-110 is h + m + l bit for bit -- up to FLT_MAX: a
+    finite |w| >= 2^127 (2 - 2^-8) takes the largest finite bf16 as its head instead of rounding to infinity (FLT_MAX = (2^128 -
+    2^120) + 2^120 - 2^104); below 2^-110 the last term is a bf16 subnormal and the split is exact to 2^-133; +-inf and NaN stay
+    non-finite (include/stabnet_hip.h, operand mode 4)."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import ptr, stream_ptr
+    rng = np.random.default_rng(17)
+    Cout, K = 64, 64
+    bits = [0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x003FFFFF, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000,   # +-0, subnormals, 2^-126
+            0x7F7F8000, 0xFF7F8000, 0x7F7F8001, 0x7F7FC000, 0x7F7FFFFF, 0xFF7FFFFF, 0x7F7F7FFF, 0x7F7F0000,                # the top of the range
+            0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001]                                                                  # +-inf, NaN
+    n_small = 256                                          # exponents -149 .. -100: around and below 2^-110
+    small = (rng.integers(0, 2, n_small) << 31) | (rng.integers(0, 27, n_small) << 23) | rng.integers(0, 1 << 23, n_small)
+    n_rest = Cout * K - len(bits) - n_small                 # random exponents -126 .. 127, random mantissas and signs
+    rest = (rng.integers(0, 2, n_rest) << 31) | (rng.integers(1, 255, n_rest) << 23) | rng.integers(0, 1 << 23, n_rest)
+    allbits = np.concatenate([np.array(bits, np.int64), small, rest]).astype(np.uint32)
+    w = rng.permutation(allbits).view(np.float32).reshape(Cout, 1, 1, K)
+    wt = torch.from_numpy(w).to(cuda)
+    img = torch.full((int(_lib.lib().stabnet_conv_weight_image_floats(Cout, 1, 1, K)),), float("nan"), device=cuda)
+    _lib.call("stabnet_conv_weight_split_image", ptr(wt), Cout, 1, 1, K, ptr(img), stream_ptr(cuda), device=cuda)
+    h, m, l = _image_planes(img, Cout, K)
+    w2 = w.reshape(Cout, K)
+    fin = np.isfinite(w2)
+    big = fin & (np.abs(w2) >= 2.0 ** -110)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s32 = (l + m) + h                                   # float32, small terms first
+        s64 = l.astype(np.float64) + m.astype(np.float64) + h.astype(np.float64)
+    assert np.isfinite(h[fin]).all() and np.isfinite(m[fin]).all() and np.isfinite(l[fin]).all()
+    assert np.array_equal(s32[big].view(np.uint32), w2[big].view(np.uint32)), np.argwhere(s32 != w2)[:5]
+    tiny_err = np.abs(s64[fin & ~big] - w2[fin & ~big].astype(np.float64)).max()
+    print("split error below 2^-110: max %.3e = 2^%.1f" % (tiny_err, np.log2(tiny_err) if tiny_err > 0 else -np.inf))
+    assert tiny_err <= 2.0 ** -133
+    assert not np.isfinite(s64[~fin]).any()
+    top = np.abs(w2) == np.float32(np.finfo(np.float32).max)
+    assert top.any() and (np.abs(h[top]).view(np.uint32) == 0x7F7F0000).all()   # the saturated head
+
+
 @pytest.mark.parametrize("k,Cin,Cout", [(1, 512, 128), (3, 128, 64), (1, 2048, 64)])
 def test_packed_error_against_float64_is_the_f32_mfma_error(cuda, k, Cin, Cout):
     """Not a reduced-precision mode: against a FLOAT64 convolution of the same float32 inputs, the packed split kernel's error is
@@ -137,3 +187,166 @@ def test_packed_error_against_float64_is_the_f32_mfma_error(cuda, k, Cin, Cout):
         k, k * k * Cin, e_p, r_p, e_f, r_f))
     assert e_p <= 2.0 * e_f + 1e-7 and r_p <= 1.5 * r_f + 2e-8
     assert e_p < 3e-6
+
+
+# ---- activations: the run-time split of the A fragments (operand range, non-finite inputs, guard bands) -------------------------
+GUARD_FLOATS = 16 * 1024                                   # 64 KiB of NaN / canary on each side of a buffer
+CANARY = 0x5CA1AB1E
+
+
+def _conv64(a, w, stride=1, pad=0):
+    """float64 convolution of the float32 values (HWIO weights, NHWC input)."""
+    k, C = w.shape[0], a.shape[3]
+    N, H, W = a.shape[:3]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    ap = np.pad(a.astype(np.float64), ((0, 0), (pad, pad), (pad, pad), (0, 0)))
+    cols = np.concatenate([ap[:, i:i + stride * (Ho - 1) + 1:stride, j:j + stride * (Wo - 1) + 1:stride, :]
+                           for i in range(k) for j in range(k)], axis=-1)
+    return (cols.reshape(-1, k * k * C) @ w.astype(np.float64).reshape(k * k * C, -1)).reshape(N, Ho, Wo, -1)
+
+
+def _conv_guarded(cuda, packed, x, w, stride=1, pad=0, relu=False, splitk=0, sc=None, sh=None):
+    """One convolution through the C ABI -- stabnet_conv2d_fwd_packed (packed=True) or stabnet_conv2d_fwd_ex -- with guard bands:
+    x sits inside a NaN-filled buffer, y inside a canary-filled one, and the workspace is NaN with a canary tail beyond the size
+    asked for.  Asserts the canaries intact; returns y (numpy)."""
+    from stabnet_amd import _lib, ops
+    from stabnet_amd._tensor import stream_ptr
+    L = _lib.lib()
+    N, H, W, Cin = x.shape
+    k, Cout = w.shape[0], w.shape[3]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    g = GUARD_FLOATS
+    xb = torch.full((x.size + 2 * g,), float("nan"), dtype=torch.float32, device=cuda)
+    xb[g:g + x.size] = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32).reshape(-1)).to(cuda)
+    ny = N * Ho * Wo * Cout
+    yb = torch.full((ny + 2 * g,), CANARY, dtype=torch.int32, device=cuda)
+    ws_bytes = int(L.stabnet_conv2d_workspace_bytes(N, H, W, Cin, Cout, k, k, stride, pad))
+    if packed:
+        ws_bytes = max(ws_bytes, max(splitk, 0) * ny * 4)
+    n4 = (ws_bytes + 3) // 4
+    wsb = torch.full((n4 + g,), CANARY, dtype=torch.int32, device=cuda)
+    wsb[:n4].view(torch.float32).fill_(float("nan"))
+    wt = torch.from_numpy(np.ascontiguousarray(ops.pack_conv_weight(w), dtype=np.float32)).to(cuda)
+    ss = torch.from_numpy(np.concatenate([sc, sh]).astype(np.float32)).to(cuda) if sc is not None else None
+    p_sc, p_sh = (ss[:Cin].data_ptr(), ss[Cin:].data_ptr()) if ss is not None else (0, 0)
+    xp, yp, wsp = xb[g:].data_ptr(), yb[g:].data_ptr(), wsb.data_ptr()
+    st = stream_ptr(cuda)
+    if packed:
+        n_img = int(L.stabnet_conv_weight_image_floats(Cout, k, k, Cin))
+        img = torch.empty(max(n_img, 1), dtype=torch.float32, device=cuda)
+        if n_img:
+            _lib.call("stabnet_conv_weight_split_image", wt.data_ptr(), Cout, k, k, Cin, img.data_ptr(), st, device=cuda)
+        _lib.call("stabnet_conv2d_fwd_packed", xp, wt.data_ptr(), img.data_ptr(), 0, p_sc, p_sh, 0, 0, 0, 1, 0, 0, yp, N, H, W, Cin,
+                  Cout, k, k, stride, pad, int(relu), int(splitk), wsp, ws_bytes, st, device=cuda)
+    else:
+        _lib.call("stabnet_conv2d_fwd_ex", xp, wt.data_ptr(), 0, p_sc, p_sh, 0, 0, 0, 1, 0, 0, yp, N, H, W, Cin, Cout, k, k, stride,
+                  pad, int(relu), wsp, ws_bytes, st, device=cuda)
+    torch.cuda.synchronize()
+    yh, wsh = yb.cpu().numpy().view(np.uint32), wsb.cpu().numpy().view(np.uint32)
+    assert (yh[:g] == CANARY).all() and (yh[g + ny:] == CANARY).all(), "write outside y"
+    assert (wsh[n4:] == CANARY).all(), "write beyond the workspace size asked for"
+    return yh[g:g + ny].view(np.float32).reshape(N, Ho, Wo, Cout).copy()
+
+
+@pytest.mark.parametrize("s", [-100, -60, 60])
+@pytest.mark.parametrize("k,Cin,Cout,splitk", [(1, 512, 128, 0), (3, 128, 64, 0), (3, 64, 64, 2)])
+def test_packed_error_is_the_f32_error_across_the_activation_range(cuda, k, Cin, Cout, splitk, s):
+    """Inputs scaled by 2^s and weights by 2^-s: the run-time split of the activations stays exact (|x| >= 2^-110), so the packed
+    kernel's error against a float64 convolution is the f32 kernel's at every scale (the bar of the unscaled test above)."""
+    rng = np.random.default_rng(1000 * k + Cin + s)
+    N, H, W = 1, 24, 32
+    x = (rng.standard_normal((N, H, W, Cin)) * 2.0 ** s).astype(np.float32)
+    w = (rng.standard_normal((k, k, Cin, Cout)) * np.sqrt(2.0 / (k * k * Cin)) * 2.0 ** -s).astype(np.float32)
+    pad = k // 2
+    want = _conv64(x, w, 1, pad)
+    got_p = _conv_guarded(cuda, True, x, w, pad=pad, splitk=splitk).astype(np.float64)
+    got_f = _conv_guarded(cuda, False, x, w, pad=pad).astype(np.float64)
+    scale = np.abs(want).max()
+    e_p, e_f = np.abs(got_p - want).max() / scale, np.abs(got_f - want).max() / scale
+    print("s=%d k=%d K=%d splitk=%d: max error vs float64 / output scale: packed %.2e, f32 %.2e" % (s, k, k * k * Cin, splitk, e_p, e_f))
+    assert np.isfinite(got_p).all() and np.isfinite(got_f).all()
+    assert e_p <= 2.0 * e_f + 1e-7 and e_p < 3e-6
+
+
+# N,H,W,Cin,Cout,k,stride,pad, prologue, splitk (0 = planned)
+NONFINITE_CASES = [
+    (1, 17, 23, 96, 64, 1, 1, 0, False, 0),      # 1x1, ragged last M tile
+    (1, 17, 23, 64, 64, 3, 1, 1, False, 0),      # 3x3 SAME, zero-padded border
+    (1, 9, 16, 512, 512, 3, 1, 1, False, 0),     # planned split-K: slabs + reduce
+    (1, 30, 30, 64, 64, 3, 1, 1, False, 2),      # two K groups inside the workgroup
+    (1, 36, 64, 256, 64, 1, 1, 0, True, 0),      # BN + ReLU prologue on the A fragments (fmaxf: NaN -> 0, -inf -> 0)
+]
+
+
+@pytest.mark.parametrize("N,H,W,Cin,Cout,k,stride,pad,prologue,splitk", NONFINITE_CASES)
+def test_nonfinite_inputs_poison_exactly_their_receptive_fields(cuda, N, H, W, Cin, Cout, k, stride, pad, prologue, splitk):
+    """+-inf and NaN at chosen input positions -- the last pixel (ragged last tile, last K slice), a mid-K channel of an inner pixel,
+    a pixel of the top row (next to the zero padding).  Without a ReLU epilogue the non-finite outputs of the packed kernel, of the
+    f32 kernel and the receptive fields of the non-finite (post-prologue, np.fmax semantics) inputs are the same set; the packed
+    kernel gives NaN there (the split of an infinity is inf + NaN + NaN) where the f32 kernel may give +-inf.  Every other output
+    keeps the bars of test_conv2d_packed_matches_oracle_and_f32_kernels."""
+    rng = np.random.default_rng(Cin + 7 * Cout + k + splitk)
+    x = rng.standard_normal((N, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((k, k, Cin, Cout)) * np.sqrt(2.0 / (k * k * Cin))).astype(np.float32)
+    sc = rng.uniform(0.5, 1.5, Cin).astype(np.float32) if prologue else None
+    sh = (rng.standard_normal(Cin) * 0.3).astype(np.float32) if prologue else None
+    vals = [np.inf, -np.inf, np.nan]
+    for i, (pix, c) in enumerate([((N - 1, H - 1, W - 1), Cin - 1), ((0, H // 2, W // 2), Cin // 2 + 3), ((0, 0, W // 3), 1)]):
+        x[pix + (c,)] = vals[(i + k + splitk) % 3]
+    with np.errstate(invalid="ignore"):
+        a = x if not prologue else np.fmax(x * sc + sh, np.float32(0)).astype(np.float32)
+    bad = ~np.isfinite(a).all(axis=-1)
+    expect = _conv64(bad[..., None].astype(np.float64), np.ones((k, k, 1, 1)), stride, pad)[..., 0] > 0
+    expect = np.broadcast_to(expect[..., None], expect.shape + (Cout,))
+    got_p = _conv_guarded(cuda, True, x, w, stride, pad, splitk=splitk, sc=sc, sh=sh)
+    got_f = _conv_guarded(cuda, False, x, w, stride, pad, sc=sc, sh=sh)
+    assert expect.any()
+    assert np.array_equal(~np.isfinite(got_f), expect)
+    assert np.array_equal(~np.isfinite(got_p), expect)
+    assert np.isnan(got_p[expect]).all()
+    want = _conv64(np.where(np.isfinite(a), a, 0), w, stride, pad)
+    fin = ~expect
+    scale = np.abs(want[fin]).max()
+    assert np.abs(got_p[fin] - want[fin]).max() <= 2e-5 * scale
+    assert np.abs(got_p[fin] - got_f[fin]).max() <= 4e-6 * scale
+
+
+def test_relu_epilogue_turns_the_packed_nan_of_an_infinite_input_into_zero(cuda):
+    """Pinned, not wanted: an output that is +inf on the f32 kernel is NaN before the ReLU epilogue on the packed kernel, and
+    fmaxf(NaN, 0) = 0 -- a silent finite result.  -inf outputs are 0 on both (include/stabnet_hip.h, operand mode 4)."""
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((1, 17, 23, 128)).astype(np.float32)      # (Cin = 64 1x1 layers take the f32 register-staged kernel)
+    w = (rng.standard_normal((1, 1, 128, 64)) * 0.125).astype(np.float32)
+    x[0, 5, 7, 10] = np.inf
+    got_p = _conv_guarded(cuda, True, x, w, relu=True)
+    got_f = _conv_guarded(cuda, False, x, w, relu=True)
+    pos = w[0, 0, 10, :] > 0
+    assert pos.any() and (~pos).any()
+    assert (got_f[0, 5, 7, pos] == np.inf).all() and (got_f[0, 5, 7, ~pos] == 0).all()
+    assert (got_p[0, 5, 7, :] == 0).all()
+    other = np.ones(got_p.shape[:3], bool)
+    other[0, 5, 7] = False
+    assert np.isfinite(got_p[other]).all() and np.abs(got_p[other] - got_f[other]).max() <= 4e-6 * np.abs(got_f[other]).max()
+
+
+def test_finite_activations_beyond_the_bf16_range_are_out_of_contract(cuda):
+    """Pinned, out of contract: the run-time split of x does not saturate (no VALU added to the K loop), so a finite |x| >=
+    2^127 (2 - 2^-8) rounds its head to a bf16 infinity and the packed output is NaN where the f32 kernel's is finite.  The largest
+    float32 below that bound still splits."""
+    rng = np.random.default_rng(4)
+    x = rng.standard_normal((1, 17, 23, 128)).astype(np.float32)
+    w = (rng.standard_normal((1, 1, 128, 64)) * 2.0 ** -20).astype(np.float32)
+    big = [((0, 3, 4), 9, 0x7F7F8000), ((0, 10, 11), 20, 0x7F7FFFFF), ((0, 16, 22), 63, 0xFF7FFFFF)]
+    for pix, c, b in big:
+        x[pix + (c,)] = np.array([b], np.uint32).view(np.float32)[0]
+    x[0, 8, 8, 30] = np.array([0x7F7F7FFF], np.uint32).view(np.float32)[0]
+    got_p = _conv_guarded(cuda, True, x, w)
+    got_f = _conv_guarded(cuda, False, x, w)
+    assert np.isfinite(got_f).all()
+    mask = np.zeros(got_p.shape[:3], bool)
+    for pix, _, _ in big:
+        mask[pix] = True
+    assert np.isnan(got_p[mask]).all()
+    assert np.isfinite(got_p[~mask]).all()
+    d = np.abs(got_p[~mask].astype(np.float64) - got_f[~mask])
+    assert (d <= 4e-6 * np.abs(got_f[~mask]).max(axis=-1, keepdims=True)).all()
