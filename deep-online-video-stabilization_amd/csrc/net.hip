@@ -717,6 +717,10 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_PUSH: return "ring_push_kernel";
         case PK_KERNEL_SPLITK_REDUCE: return "conv_splitk_reduce_kernel";
         case PK_KERNEL_WGRAD: return "conv_wgrad_f32_kernel";
+        case PK_KERNEL_MJPEG_TRANSFORM: return "mjpeg_transform_kernel";
+        case PK_KERNEL_MJPEG_ENTROPY: return "mjpeg_entropy_kernel";
+        case PK_KERNEL_MJPEG_LAYOUT: return "mjpeg_layout_kernel";
+        case PK_KERNEL_MJPEG_GATHER: return "mjpeg_gather_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

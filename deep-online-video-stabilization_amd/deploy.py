@@ -1,6 +1,7 @@
 """Host side of the online loop (deploy_bundle.py:183-342, the network + feedback part): an on-device history ring
 per stream and ONE C call per frame (StabNetStream); ClipPipeline drives it from a clip in HOST memory with the PCIe copies
-of neighbouring frames overlapped and the colour remap (warpRevBundle2) on the device.  Video decode/encode stay with the caller."""
+of neighbouring frames overlapped, the colour remap (warpRevBundle2) and, when asked for, the JPEG encoding of the stabilised frame
+(mjpeg.MjpegEncoder) on the device.  Video decode and the container (avi.py) stay on the host."""
 from __future__ import annotations
 
 import ctypes
@@ -200,9 +201,16 @@ class ClipPipeline:
     run(grey, bgr=None, sink=None, maps=False): grey = sequence of host float32 [H,W] frames in the training normalisation, frame 0 seeds
     the ring (deploy_bundle.py:206-222); bgr = matching uint8 [H,W,3] frames or None.  Per processed frame t >= 1 the host gets
     {"t", "output" uint8 [H,W], "bgr" uint8 [H,W,3] (if bgr), "x_map"/"y_map"/"black" (if maps)}: passed to `sink` as views of pinned
-    staging memory that stay valid until the sink returns, or -- without a sink -- copied and returned as a list."""
+    staging memory that stay valid until the sink returns, or -- without a sink -- copied and returned as a list.
 
-    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4):
+    jpeg=dict(quality=.., subsampling=.., restart_mcus=..): every slot's frame graph also encodes the stabilised frame (the BGR frame
+    when colour, else the grey output) as a baseline JPEG (csrc/mjpeg.hip) and the result carries "jpeg" (uint8 view of pinned memory,
+    valid until the sink returns).  run(..., raw=False) then skips the raw downloads ("output" / "bgr" are absent): what crosses PCIe
+    per frame is the compressed frame.  Its length is only known on the device, so the download is a FIXED first chunk (jpeg_chunk
+    bytes: a quarter of the raw frame, several times a q75 frame) together with the length; the rare frame that is longer gets the
+    rest by a second, synchronous copy when it is handed over."""
+
+    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
@@ -223,6 +231,17 @@ class ClipPipeline:
             self.h_warp = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_warp = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
             self.remap_ws = on((2 * (H // rate) * (W // rate),), torch.float32)
+        self.enc = None
+        if jpeg is not None:
+            from .mjpeg import MjpegEncoder
+            C = 3 if colour else 1
+            self.enc = MjpegEncoder(H, W, C, device=dev, **jpeg)
+            mb = self.enc.max_bytes
+            self.jpeg_chunk = min(mb, (H * W * C // 4 + 4095) & ~4095)
+            self.d_jpeg = [on((1, mb), torch.uint8) for _ in range(slots)]
+            self.d_jlen = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(slots)]
+            self.h_jpeg = [pin((mb,), torch.uint8) for _ in range(slots)]
+            self.h_jlen = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(slots)]
         self.h_maps = None
         self.use_graph = True
         self._graphs = {}
@@ -240,6 +259,8 @@ class ClipPipeline:
         if self.colour:
             _lib.call("stabnet_warp_rev_bundle2", ptr(self.d_bgr[k]), ptr(st.x_map), ptr(st.y_map), 1, H, W, 3, self.rate,
                       ptr(self.d_warp[k]), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), device=self.dev)
+        if self.enc is not None:
+            self.enc.encode(self.d_warp[k] if self.colour else self.d_out[k], out=self.d_jpeg[k], nbytes=self.d_jlen[k])
         if maps:
             self.d_maps[0][k].copy_(st.x_map.view(H, W)); self.d_maps[1][k].copy_(st.y_map.view(H, W))
             self.d_maps[2][k].copy_(st.black.view(H, W))
@@ -257,16 +278,29 @@ class ClipPipeline:
             self.use_graph = False
             return None
 
-    def _result(self, slot: int, t: int, maps: bool):
-        r = {"t": t, "output": self.h_out[slot].numpy()}
-        if self.colour:
-            r["bgr"] = self.h_warp[slot].numpy()
+    def _result(self, slot: int, t: int, maps: bool, raw: bool = True):
+        r = {"t": t}
+        if raw:
+            r["output"] = self.h_out[slot].numpy()
+            if self.colour:
+                r["bgr"] = self.h_warp[slot].numpy()
+        if self.enc is not None:
+            n = int(self.h_jlen[slot][0])
+            if n > self.jpeg_chunk:                           # longer than the chunk that came with the length: fetch the rest now
+                with torch.cuda.stream(self.s_out):
+                    self.h_jpeg[slot][self.jpeg_chunk:n].copy_(self.d_jpeg[slot][0, self.jpeg_chunk:n], non_blocking=True)
+                self.s_out.synchronize()
+            self.jpeg_bytes_down += max(n, self.jpeg_chunk) + 4
+            r["jpeg"] = self.h_jpeg[slot].numpy()[:n]
         if maps:
             r["x_map"], r["y_map"], r["black"] = (m[slot].numpy() for m in self.h_maps)
         return r
 
-    def run(self, grey, bgr=None, sink=None, maps: bool = False):
+    def run(self, grey, bgr=None, sink=None, maps: bool = False, raw: bool = True):
         st, H, W, K = self.st, self.st.H, self.st.W, self.slots
+        if not raw and self.enc is None:
+            raise _lib.StabnetError("ClipPipeline.run: raw=False needs a pipeline built with jpeg=...: nothing would come back")
+        self.jpeg_bytes_down = 0
         if self.colour and bgr is None:
             raise _lib.StabnetError("ClipPipeline.run: this pipeline was built with colour=True, bgr frames are required")
         if maps and self.h_maps is None:
@@ -289,7 +323,7 @@ class ClipPipeline:
                 w0 = time.perf_counter()
                 self.ev_down[k].synchronize()
                 self.host_wait_s += time.perf_counter() - w0
-                emit(self._result(k, pending[k], maps))
+                emit(self._result(k, pending[k], maps, raw))
                 pending[k] = None
             self.h_grey[k].numpy()[...] = grey[t]
             if self.colour:
@@ -314,9 +348,13 @@ class ClipPipeline:
                 self.ev_run[k].record(self.s_run)
             with torch.cuda.stream(self.s_out):
                 self.s_out.wait_event(self.ev_run[k])
-                self.h_out[k].copy_(self.d_out[k], non_blocking=True)
-                if self.colour:
-                    self.h_warp[k].copy_(self.d_warp[k].view(H, W, 3), non_blocking=True)
+                if raw:
+                    self.h_out[k].copy_(self.d_out[k], non_blocking=True)
+                    if self.colour:
+                        self.h_warp[k].copy_(self.d_warp[k].view(H, W, 3), non_blocking=True)
+                if self.enc is not None:
+                    self.h_jlen[k].copy_(self.d_jlen[k], non_blocking=True)
+                    self.h_jpeg[k][:self.jpeg_chunk].copy_(self.d_jpeg[k][0, :self.jpeg_chunk], non_blocking=True)
                 if maps:
                     for h, d in zip(self.h_maps, self.d_maps):
                         h[k].copy_(d[k], non_blocking=True)
@@ -325,6 +363,6 @@ class ClipPipeline:
         order = sorted((p, k) for k, p in enumerate(pending) if p is not None)
         for p, k in order:
             self.ev_down[k].synchronize()
-            emit(self._result(k, p, maps))
+            emit(self._result(k, p, maps, raw))
         torch.cuda.synchronize(self.dev)
         return results if sink is None else None

@@ -7,9 +7,11 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
   * --model-dir/--model-name take either a TF checkpoint prefix (`model-80000.index` + `.data-*`, read by
     stabnet_amd/tf_checkpoint.py without TensorFlow; the `.meta` graph is not needed) or a `.npz` written by
     train_bundle_nobm.py (TF variable names); without one, seeded synthetic weights are used and said so.
-  * OpenCV is absent: clips are `.npy` arrays ([T,H,W] grey in [0,255] or [T,H,W,3] BGR) under
-    <prefix>/unstable/<name>; results are written as `.npy` (stabilised grey frames, x/y maps, black masks).  Video
-    decode / MJPG encode (cv2.VideoCapture / VideoWriter in the reference) are outside the path and not implemented.
+  * OpenCV is absent: clips are `.npy` arrays ([T,H,W] grey in [0,255] or [T,H,W,3] BGR) or Motion-JPEG `.avi` files
+    (read on the host with Pillow, stabnet_amd/avi.py) under <prefix>/unstable/<name>; results are written as `.npy`
+    (stabilised grey frames, x/y maps, black masks).  --mjpg also writes what the reference's cv2.VideoWriter('MJPG')
+    writes (deploy_bundle.py:197-198,215,305,366-371): <name>.avi (the first frame as read, then every stabilised frame)
+    and <name>_cut.avi (the crop), every frame a baseline JPEG encoded on the GPU (csrc/mjpeg.hip).
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -54,6 +56,11 @@ def build_parser():
                    help='conv operand mode of the regressor (include/stabnet_hip.h): 4 = packed split kernels -- float32 operands as exact '
                         'sums of three bf16 terms on the bf16 matrix pipe, float32 accumulation, float32-level results (default); '
                         '0 = exact f32 MFMA; 1 = bf16 operands (reduced precision)')
+    p.add_argument('--mjpg', action='store_true',
+                   help='also write <output-dir>/output/<name>.avi and <name>_cut.avi (Motion-JPEG, encoded on the GPU) as the reference does')
+    p.add_argument('--jpeg-quality', type=int, default=75)
+    p.add_argument('--jpeg-subsampling', default='420', choices=['420', '444'])
+    p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
 
 
@@ -99,7 +106,18 @@ def is_colour(frame, H, W):
     return f.ndim == 3 and f.shape[:2] == (H, W)
 
 
-def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks):
+def first_frame_u8(clip, H, W):
+    """The frame the reference writes before the loop (deploy_bundle.py:215): the first frame as read, at the network's size."""
+    if is_colour(clip[0], H, W):
+        return np.ascontiguousarray(clip[0], dtype=np.uint8)
+    return ((grey_train(clip[0], H, W) + 0.5) * 255).clip(0, 255).astype(np.uint8)
+
+
+def jpeg_options(args):
+    return dict(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
+
+
+def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289)."""
     import torch
@@ -120,6 +138,9 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
             colour_out.append(warp.warpRevBundle2(bgr, r['x_map'], r['y_map']).cpu().numpy())
         net_output = ((r['output'][0, :, :, 0].cpu().numpy() + 0.5) * 255).clip(0, 255).astype(np.uint8)
         frames_out.append(net_output)
+        if jpeg_sink is not None:                                             # the frame that is kept, compressed on the device
+            kept = colour_out[-1] if is_colour(clip[t], H, W) else net_output
+            jpeg_sink(enc.encode_bytes(torch.from_numpy(np.ascontiguousarray(kept)).to(dev))[0])
         xmaps.append(r['x_map'][0, :, :, 0].cpu().numpy()); ymaps.append(r['y_map'][0, :, :, 0].cpu().numpy())
         blacks.append(r['black_pix'][0].cpu().numpy().astype(np.uint8))
         length += 1
@@ -129,7 +150,7 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     return length, tot_time
 
 
-def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks):
+def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included."""
     from stabnet_amd.deploy import ClipPipeline
@@ -146,12 +167,14 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
         frames_out.append(r['output'].copy())
         if colour:
             colour_out.append(r['bgr'].copy())
+        if jpeg_sink is not None:
+            jpeg_sink(bytes(r['jpeg']))
         xmaps.append(r['x_map'].copy()); ymaps.append(r['y_map'].copy()); blacks.append(r['black'].copy())
         if len(frames_out) % 10 == 0:
             print('length: ' + str(len(frames_out)))
 
     start = time.time()
-    ClipPipeline(stream, colour=colour).run(Grey(), clip if colour else None, sink=sink, maps=True)
+    ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
     tot_time = time.time() - start
     if frames_out:
         print('fps={}'.format(len(frames_out) / tot_time))
@@ -189,7 +212,7 @@ def main():
                            use_graph=True, operand_mode=args.operand_mode)   # one frame = fixed-argument launches: captured once, replayed per frame
     stream.track_black()            # all_black += round(black) inside every refine pass (deploy_bundle.py:234,291), on the device
 
-    clips = []
+    clips, fps_of = [], {}
     if args.synthetic > 0:
         clips.append(('synthetic', (synthetic.make_clip(H, W, args.synthetic, seed=1234) + 0.5) * 255.0))
     else:
@@ -204,8 +227,16 @@ def main():
                     clips.append((name, np.load(path, mmap_mode='r')))
                 elif os.path.exists(path + '.npy'):
                     clips.append((name, np.load(path + '.npy', mmap_mode='r')))
+                elif os.path.exists(path) and path.lower().endswith('.avi'):
+                    from stabnet_amd.avi import AviMjpegReader
+                    rd = AviMjpegReader(path)
+                    clips.append((name, np.stack(list(rd.frames()))))
+                    if rd.fps > 0:
+                        fps_of[name] = rd.fps
+                    print('read %s: %d MJPG frames %dx%d at %.3f fps, decoded on the host with Pillow (outside the timed part)'
+                          % (path, len(rd), rd.width, rd.height, rd.fps))
                 else:
-                    print('skipping %s: only .npy clips can be read without OpenCV' % path)
+                    print('skipping %s: only .npy clips and MJPG .avi files can be read without OpenCV' % path)
     out_dir = os.path.join(args.output_dir, 'output')
     os.makedirs(out_dir, exist_ok=True)
 
@@ -213,17 +244,31 @@ def main():
         print(name)
         tot_time, length = 0.0, 0
         frames_out, xmaps, ymaps, blacks, colour_out = [], [], [], [], []
+        stem = os.path.join(out_dir, os.path.splitext(os.path.basename(name))[0])
+        writer, enc, fps = None, None, fps_of.get(name, args.fps)
         try:
+            if args.mjpg:
+                from stabnet_amd.avi import AviMjpegWriter
+                from stabnet_amd.mjpeg import MjpegEncoder
+                first = first_frame_u8(clip, H, W)
+                enc = MjpegEncoder(H, W, 3 if first.ndim == 3 else 1, device=dev, **jpeg_options(args))
+                writer = AviMjpegWriter(stem + '.avi', W, H, fps)
+                writer.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])          # deploy_bundle.py:215
+            sink = writer.write if writer is not None else None
             if args.pipeline:
-                length, tot_time = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks)
+                length, tot_time = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
+                                                 jpeg_options(args) if args.mjpg else None)
             else:
-                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks)
+                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
             print('total length={}'.format(length + 2))
+            if writer is not None:
+                writer.close()
+                print('wrote %s (%d frames, MJPG q%d %s, %.3f fps)' % (stem + '.avi', writer.frames_written, args.jpeg_quality,
+                                                                        args.jpeg_subsampling, fps))
             if frames_out:
-                stem = os.path.join(out_dir, os.path.splitext(os.path.basename(name))[0])
                 np.save(stem + '_stable.npy', np.stack(frames_out))
                 if colour_out:
                     np.save(stem + '_stable_bgr.npy', np.stack(colour_out))
@@ -233,8 +278,16 @@ def main():
                 ans, area = warp.max_inscribed_rect(stream.all_black[0])
                 if ans:
                     src = np.stack(colour_out) if colour_out else np.stack(frames_out)
-                    np.save(stem + '_cut.npy', src[:, ans[0]:ans[2] + 1, ans[1]:ans[3] + 1])
+                    cut = src[:, ans[0]:ans[2] + 1, ans[1]:ans[3] + 1]
+                    np.save(stem + '_cut.npy', cut)
                     print('crop', ans, 'area', area)
+                    if args.mjpg:                    # deploy_bundle.py:366-371: the cropped frames as a second video
+                        ch, cw = cut.shape[1], cut.shape[2]
+                        cenc = MjpegEncoder(ch, cw, 3 if cut.ndim == 4 else 1, device=dev, **jpeg_options(args))
+                        with AviMjpegWriter(stem + '_cut.avi', cw, ch, fps) as wcut:
+                            for f in cut:
+                                wcut.write(cenc.encode_bytes(torch.from_numpy(np.ascontiguousarray(f)).to(dev))[0])
+                        print('wrote %s (%d frames %dx%d)' % (stem + '_cut.avi', len(cut), cw, ch))
 
 
 if __name__ == '__main__':

@@ -410,6 +410,29 @@ int stabnet_augment_pairs(const float* stable, const float* unstable, const floa
                           float* x1, float* y1, float* x2, float* y2, float* flow_out, float* fm1, float* mk1, float* fm2,
                           float* mk2, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- after the path: Motion-JPEG encoding of the stabilised frame (deploy_bundle.py:197-198,305: VideoWriter 'MJPG') ----
+ * Baseline JFIF (SOF0, 8-bit, the four Annex K Huffman tables, restart intervals) encoded where the frame lies.
+ * img uint8 [N,H,W,C]: C = 3 BGR (what stabnet_warp_rev_bundle2 writes) or C = 1 grey (stabnet_cvt_train2img); any H, W in
+ * 1..65535, partial MCUs replicate the last row / column.  subsampling 420 (MCU 16x16, chroma = mean of 2x2) or 444 (MCU 8x8);
+ * ignored for C = 1.  Colour: JFIF full-range BT.601 in float32, not rounded to 8 bits before the orthonormal float32 DCT;
+ * q = rint(coef / Q), AC clamped to +-1023 and DC to +-1024.  restart_mcus (1..65535) = DRI: every interval starts byte-aligned
+ * with DC predictors 0, ends padded with 1-bits and is followed by RSTm (m mod 8) -- the intervals are coded in parallel.
+ * Every buffer is sized for the worst case of a block (416 bytes with every byte stuffed), so there is no overflow to report:
+ * out_bytes[n] <= stabnet_mjpeg_max_bytes always.  Nothing allocates, synchronises or copies from the host inside encode. */
+int stabnet_jpeg_quant_tables(int quality, unsigned short* luma64, unsigned short* chroma64);   /* host; IJG scaling of Annex K, quality 1..100, natural order */
+/* host; SOI .. SOS.  Returns the number of bytes (host_out NULL: only the count), -1 on bad arguments or a cap too small. */
+int stabnet_mjpeg_header(int H, int W, int C, int subsampling, int restart_mcus, const unsigned short* luma64,
+                         const unsigned short* chroma64, unsigned char* host_out, int cap);
+size_t stabnet_mjpeg_max_bytes(int H, int W, int C, int subsampling, int restart_mcus);        /* per frame, header included; 0 = bad arguments */
+size_t stabnet_mjpeg_workspace_bytes(int N, int H, int W, int C, int subsampling, int restart_mcus);
+/* luma64_dev, chroma64_dev (NULL allowed when C = 1): tables in natural order ON THE DEVICE; header_dev: the header of the same
+ * arguments ON THE DEVICE.  out + n * out_stride receives stream n (out_stride >= stabnet_mjpeg_max_bytes), out_bytes[n] its
+ * length (device int32).  workspace: 16-byte aligned. */
+int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, int subsampling, int restart_mcus,
+                         const unsigned short* luma64_dev, const unsigned short* chroma64_dev, const unsigned char* header_dev,
+                         int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
+                         size_t workspace_bytes, void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif

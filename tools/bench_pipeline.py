@@ -5,7 +5,10 @@ colour uint8 frames) in, stabilised colour frame + the network's grey output bac
             download, one after the other with the host waiting in between
   pipeline  stabnet_amd.deploy.ClipPipeline: the same work with upload / frame / download on three HIP streams (pinned staging)
   resident  the frame alone, inputs already in HBM (= what bench.py reports as `value`)
-One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280]"""
+  --jpeg    instead of the legs above: the pipeline with the raw download (today's leg), with the JPEG encoder in every frame graph
+            + the raw download, and with the encoder and NO raw download (what crosses PCIe per frame is the compressed frame); the
+            three alternate, each repeated --repeats times, fps, host_wait_s and bytes downloaded per frame beside each
+One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg]"""
 import argparse
 import json
 import os
@@ -25,6 +28,9 @@ ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--height", type=int, default=720)
 ap.add_argument("--width", type=int, default=1280)
 ap.add_argument("--slots", type=int, default=3)
+ap.add_argument("--jpeg", action="store_true")
+ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--jpeg-quality", type=int, default=75)
 a = ap.parse_args()
 H, W, T = a.height, a.width, a.frames
 dev = torch.device("cuda", 0)
@@ -85,6 +91,42 @@ def resident():
     torch.cuda.synchronize()
     return (T - 1) / (time.perf_counter() - t0)
 
+
+def jpeg_legs():
+    """raw / jpeg + raw / jpeg only, alternating in one process: the legs see the same clocks and the same neighbours."""
+    opts = dict(quality=a.jpeg_quality, subsampling="420")
+    pipes = {"raw": (ClipPipeline(StabNetStream(params, H, W, cfg, device=dev, use_graph=True), colour=True, slots=a.slots), True),
+             "jpeg_and_raw": (ClipPipeline(StabNetStream(params, H, W, cfg, device=dev, use_graph=True), colour=True, slots=a.slots, jpeg=opts), True),
+             "jpeg_only": (ClipPipeline(StabNetStream(params, H, W, cfg, device=dev, use_graph=True), colour=True, slots=a.slots, jpeg=opts), False)}
+    legs = {k: {"fps": [], "host_wait_s": [], "bytes_down_per_frame": []} for k in pipes}
+    got_c, got_o, got_j = np.zeros((H, W, 3), np.uint8), np.zeros((H, W), np.uint8), np.zeros(H * W * 3, np.uint8)
+    def sink(r):                                                                  # the consumer touches everything it was given
+        if "bgr" in r:
+            np.copyto(got_c, r["bgr"]); np.copyto(got_o, r["output"])
+        if "jpeg" in r:
+            got_j[:len(r["jpeg"])] = r["jpeg"]
+    for pipe, raw in pipes.values():
+        pipe.run(grey[:120], bgr[:120], sink=sink, **({} if raw else {"raw": False}))      # graph capture + warm-up
+    for _ in range(a.repeats):
+        for name, (pipe, raw) in pipes.items():
+            t0 = time.perf_counter()
+            pipe.run(grey, bgr, sink=sink, **({} if raw else {"raw": False}))
+            dt = time.perf_counter() - t0
+            legs[name]["fps"].append((T - 1) / dt)
+            legs[name]["host_wait_s"].append(pipe.host_wait_s)
+            legs[name]["bytes_down_per_frame"].append((H * W * 4 if raw else 0) + getattr(pipe, "jpeg_bytes_down", 0) / (T - 1))
+    med = lambda v: sorted(v)[len(v) // 2]
+    out["jpeg_legs"] = legs
+    out["jpeg_chunk_bytes"] = pipes["jpeg_only"][0].jpeg_chunk
+    out["jpeg_only_over_raw"] = med(legs["jpeg_only"]["fps"]) / med(legs["raw"]["fps"])
+    out["jpeg_and_raw_over_raw"] = med(legs["jpeg_and_raw"]["fps"]) / med(legs["raw"]["fps"])
+
+
+if a.jpeg:
+    jpeg_legs()
+    out["slots"] = a.slots
+    print(json.dumps(out))
+    sys.exit(0)
 
 fs, last_s = serial()
 fp, last_p = pipeline()
