@@ -5,23 +5,31 @@
 #include "train_layers.h"
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 
 // ---------------------------------------------------------------------------------------------------------
 // Column reductions over an [M][C] tensor, two stages (deterministic order).  (Measured and dropped: ONE launch per reduction
 // with a last-block-done ticket doing the finalize -- with agent-scope release/acquire fences each reduction took 22 us
 // instead of 6 + 6, 512 blocks each paying a buffer_wbl2; in the fence-free sc1 store/load form the serial tail of the
 // last block still cost more than the second launch: 22.9 ms vs 21.9 ms per step.)
-//   MODE 0: (sum x, sum x^2)                           BN batch statistics
+//   MODE 0: (sum x, sum x^2)                           BN batch statistics, accumulated and handed over in FLOAT64 (below)
 //   MODE 1: (sum dz, sum dz*xhat), dz = g*(a>0)        BN+ReLU backward;  a = x*scale+shift, xhat = (x-mean)*invstd
 //   MODE 2: (sum g, -)                                 bias gradient
 // block = 16 channel-quads x 16 row lanes; grid = (C/64, chunks, groups); partial [groups][chunks][2][C].
 // GROUPS: the two siamese towers run in lockstep (train_bundle_nobm.py:107-108 builds two towers over the same weights), so
 // the same reduction of both towers is ONE launch (blockIdx.z = tower) -- these kernels are launch-latency sized (about 6 us
 // for either one or two towers' rows), and there are ~240 of them per tower per step.
+// MODE 0 in float64: the variance comes out as E[x^2] - mean^2, which amplifies the rounding of the two sums by 1 + r^2,
+// r = |mean| / std of the channel.  With float32 per-lane sums, lane combine and partials (only the chunks were combined in
+// float64) the relative variance error, worst over 1 .. 294 912 rows x 4 .. 2 048 channels on an MI355X, was 2.0e-7 / 7.4e-7 /
+// 1.4e-5 / 8.5e-5 / 1.3e-4 / 5.6e-4 / 4.5e-3 at r = 0 / 1 / 3 / 8 / 16 / 32 / 100 -- outside (1 + r^2) 2^-23 from r = 0 on wherever
+// few roundings average out (12 .. 65 rows, 1 152 rows x 2 048 channels), and a single row gave a positive variance.  The
+// products of float32 values are exact in float64 and its sums round at 2^-53, so here the amplified error stays below 2^-24 of
+// the variance up to r ~ 10^4: measured 5.8e-8 .. 6.0e-8 at every r, the rounding of the float32 result alone.
+// The partials of MODE 0 are doubles: [groups][chunks][2][C] of them in the same workspace (sized for it, 8-byte aligned).
 template <int MODE>
 __global__ __launch_bounds__(256) void col_reduce_kernel(const ColGroups G, long M, int C, long rows_per_chunk,
                                                          float* __restrict__ partial_all) {
-    __shared__ float4 s0[16][16], s1[16][16];
     const int grp = blockIdx.z;
     const float* __restrict__ x = G.x[grp];
     const float* __restrict__ g = G.g[grp];
@@ -34,6 +42,50 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const ColGroups G, long
     const int c = blockIdx.x * 64 + q * 4;
     const long r0 = (long)blockIdx.y * rows_per_chunk;
     const long r1 = min(M, r0 + rows_per_chunk);
+    if constexpr (MODE == 0) {
+        __shared__ double d0[16][16][4], d1[16][16][4];
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+        if (c < C) {
+            // four rows per trip as below, and the next trip's loads are issued before this trip's sums: at two waves per SIMD the
+            // float64 work would otherwise sit between the loads (2 us more per launch than the float32 sums, 0.7 % of a step).
+            // A row past the end adds exact zeros; fma(v, v, b) rounds once, as the exact product followed by the add does.
+            auto load4 = [&](float4* xv, long rb) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const long r = rb + 16 * j;
+                    xv[j] = r < r1 ? *reinterpret_cast<const float4*>(x + r * C + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            };
+            float4 cur[4], nxt[4];
+            load4(cur, r0 + rl);
+            for (long rb = r0 + rl; rb < r1; rb += 64) {
+                load4(nxt, rb + 64);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double v[4] = {(double)cur[j].x, (double)cur[j].y, (double)cur[j].z, (double)cur[j].w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { a[i] += v[i]; b[i] = __builtin_fma(v[i], v[i], b[i]); }
+                    cur[j] = nxt[j];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { d0[rl][q][i] = a[i]; d1[rl][q][i] = b[i]; }
+        __syncthreads();
+        // lane combine in row-lane order: wave 0 takes the 64 sums of x, wave 1 those of x^2, one channel per thread (sixteen
+        // independent LDS reads each; the 16 threads of row lane 0 doing all 128 of their quad were a 5 us serial tail)
+        const int t = threadIdx.x & 63, which = threadIdx.x >> 6;
+        if (which < 2 && blockIdx.x * 64 + t < C) {
+            const double* d = which ? &d1[0][0][0] : &d0[0][0][0];      // [row lane][64 channels]
+            double sum = d[t];
+#pragma unroll
+            for (int l = 1; l < 16; ++l) sum += d[l * 64 + t];
+            double* p = reinterpret_cast<double*>(partial_all) + ((size_t)grp * gridDim.y + blockIdx.y) * 2 * C;
+            p[which * C + blockIdx.x * 64 + t] = sum;
+        }
+        return;
+    }
+    __shared__ float4 s0[16][16], s1[16][16];
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
     if (c < C) {
         float4 sc = a0, sh = a0, mu = a0, is = a0;
@@ -55,11 +107,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const ColGroups G, long
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (rb + 16 * j >= r1) break;
-                if (MODE == 0) {
-                    const float4 v = xv[j];
-                    a0.x += v.x; a0.y += v.y; a0.z += v.z; a0.w += v.w;
-                    a1.x += v.x * v.x; a1.y += v.y * v.y; a1.z += v.z * v.z; a1.w += v.w * v.w;
-                } else if (MODE == 1) {
+                if (MODE == 1) {
                     const float4 v = xv[j];
                     float4 d = gv[j];
                     d.x = (__builtin_fmaf(v.x, sc.x, sh.x) > 0.f) ? d.x : 0.f; d.y = (__builtin_fmaf(v.y, sc.y, sh.y) > 0.f) ? d.y : 0.f;   // the forward's own decision (fma + max in the conv prologue)
@@ -97,7 +145,8 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const ColGroups G, long
 // Measured and not kept (rocprofv3, 6.3-6.7 us per launch as it stands): eight chunk loads issued together (12-13 us: 120
 // VGPRs at 1024 threads), the final 63-term sum by lane 0 only instead of by every thread (7.1-7.2 us).
 constexpr int FIN_LANES = 64, FIN_CH = 16;
-__device__ __forceinline__ void combine_partials(const float* __restrict__ partial, int chunks, int C, int c, int lane,
+template <typename T>                                       // float partials; double ones for the BN statistics
+__device__ __forceinline__ void combine_partials(const T* __restrict__ partial, int chunks, int C, int c, int lane,
                                                  double& s0, double& s1) {
     __shared__ double sh0[FIN_LANES][FIN_CH], sh1[FIN_LANES][FIN_CH];
     double a0 = 0.0, a1 = 0.0;
@@ -125,7 +174,7 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(const float* __
     const int c = blockIdx.x * FIN_CH + (threadIdx.x % FIN_CH), lane = threadIdx.x / FIN_CH;
     for (int gi = 0; gi < groups; ++gi) {
         double s, ss;
-        combine_partials(partial + (size_t)gi * chunks * 2 * C, chunks, C, c, lane, s, ss);
+        combine_partials(reinterpret_cast<const double*>(partial) + (size_t)gi * chunks * 2 * C, chunks, C, c, lane, s, ss);
         if (lane == 0 && c < C) {
             const double mean = s / (double)M;
             const double var = fmax(ss / (double)M - mean * mean, 0.0);
@@ -541,7 +590,7 @@ static int reduce_chunks(long M, int C, long& rows_per_chunk) {
 size_t col_reduce_workspace_floats(long M, int C) {
     long rpc;
     const int chunks = reduce_chunks(M, C, rpc);
-    return (size_t)chunks * 2 * C;
+    return (size_t)chunks * 2 * C * 2;                      // the BN statistics keep their partials as doubles
 }
 
 size_t col_reduce_workspace_floats(long M, int C, int groups) { return (size_t)groups * col_reduce_workspace_floats(M, C); }
@@ -551,6 +600,7 @@ int launch_bn_stats_g(int groups, const float* const* x, long M, int C, const fl
                       float decay, float* const* scale, float* const* shift, float* const* save_mean, float* const* save_invstd,
                       float* mov_mean, float* mov_var, float* partial, hipStream_t st) {
     SN_REQUIRE(C % 4 == 0 && (groups == 1 || groups == 2), "bn_stats: C %% 4 != 0 or bad group count");
+    SN_REQUIRE((reinterpret_cast<uintptr_t>(partial) & 7) == 0, "bn_stats: the workspace must be 8-byte aligned (float64 partials)");
     long rpc;
     const int chunks = reduce_chunks(M, C, rpc);
     ColGroups G{};
@@ -650,12 +700,13 @@ int launch_gap_bwd(const float* dg, int N, int HW, int C, float* da, hipStream_t
 int launch_fc_bwd(const float* x, const float* w, const float* y, const float* dy, int M, int K, int Nout, int relu,
                   float* dW, float* db, float* dx, float* scratch, size_t scratch_floats, hipStream_t st) {
     SN_REQUIRE(K % 4 == 0, "fc_bwd: K %% 4 != 0");
+    const int npb = fc_bwd_x_rows(K, Nout), splits = cdiv(Nout, npb);
+    // (checked before the first launch: a refused call leaves dW / db as they were)
+    SN_REQUIRE(dx == nullptr || (scratch != nullptr && scratch_floats >= (size_t)splits * M * K), "fc_bwd: scratch of %zu floats needed",
+               (size_t)splits * M * K);
     fc_bwd_w_kernel<<<dim3(cdiv(K, 1024), Nout), 256, 0, st>>>(x, y, dy, M, K, Nout, relu, dW, db);
     SN_LAUNCH_CHECK("fc_bwd_w_kernel");
     if (dx != nullptr) {
-        const int npb = fc_bwd_x_rows(K, Nout), splits = cdiv(Nout, npb);
-        SN_REQUIRE(scratch != nullptr && scratch_floats >= (size_t)splits * M * K, "fc_bwd: scratch of %zu floats needed",
-                   (size_t)splits * M * K);
         fc_bwd_x_kernel<<<dim3(cdiv(K, 64), splits), 256, 0, st>>>(w, y, dy, M, K, Nout, relu, npb, scratch);
         SN_LAUNCH_CHECK("fc_bwd_x_kernel");
         fc_bwd_x_reduce_kernel<<<cdiv((long)M * K, 256), 256, 0, st>>>(scratch, splits, (long)M * K, dx);
@@ -682,3 +733,121 @@ int launch_adam(float* w, const float* g, const float* g2, float* m, float* v, l
     SN_LAUNCH_CHECK("adam_kernel");
     return STABNET_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// C entry points of the launchers above, one per operator (include/stabnet_hip.h): the training step reaches these kernels
+// through stabnet_tower(s)_fwd_train / _bwd*; the operator tests reach the same launchers through these.
+static int check_device_all(std::initializer_list<const void*> ptrs, const char* what, hipStream_t st) {
+    for (const void* p : ptrs)
+        if (p != nullptr)
+            if (int rc = sn_check_device(p, what, st)) return rc;
+    return STABNET_OK;
+}
+
+extern "C" {
+
+size_t stabnet_col_reduce_workspace_floats(long M, int C, int groups) {
+    if (M <= 0 || C <= 0 || (groups != 1 && groups != 2)) return 0;
+    return col_reduce_workspace_floats(M, C, groups);
+}
+
+int stabnet_bn_stats_train(int groups, const float* x0, const float* x1, long M, int C, const float* gamma, const float* beta,
+                           float eps, float decay, float* stats0, float* stats1, float* mov_mean, float* mov_var, float* partial,
+                           void* stream) {
+    SN_REQUIRE(groups == 1 || groups == 2, "bn_stats_train: groups = %d (1 or 2)", groups);
+    SN_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "bn_stats_train: M = %ld, C = %d (C %% 4 != 0 or an empty tensor)", M, C);
+    SN_REQUIRE(x0 && stats0 && gamma && beta && partial && (groups == 1 || (x1 && stats1)), "bn_stats_train: null pointer");
+    SN_REQUIRE((mov_mean == nullptr) == (mov_var == nullptr), "bn_stats_train: moving mean and variance come together (both or neither)");
+    if (int rc = check_device_all({x0, groups == 2 ? x1 : nullptr, gamma, beta, stats0, groups == 2 ? stats1 : nullptr, mov_mean, mov_var, partial},
+                                  "bn_stats_train: an argument", (hipStream_t)stream)) return rc;
+    const float* x[2] = {x0, x1};
+    float* sc[2] = {stats0, stats1};
+    float *sh[2] = {nullptr, nullptr}, *mu[2] = {nullptr, nullptr}, *is[2] = {nullptr, nullptr};
+    for (int i = 0; i < groups; ++i) { sh[i] = sc[i] + C; mu[i] = sc[i] + 2 * (size_t)C; is[i] = sc[i] + 3 * (size_t)C; }
+    return launch_bn_stats_g(groups, x, M, C, gamma, beta, eps, decay, sc, sh, mu, is, mov_mean, mov_var, partial, (hipStream_t)stream);
+}
+
+int stabnet_bn_relu_bwd(int groups, const float* x0, const float* x1, const float* g0, const float* g1, const float* stats0,
+                        const float* stats1, const float* gamma, long M, int C, const float* addend0, const float* addend1,
+                        int add_stride, int H, int W, float* d_gamma, float* d_beta, float* d_x0, float* d_x1, float* partial,
+                        float* coef0, float* coef1, void* stream) {
+    SN_REQUIRE(groups == 1 || groups == 2, "bn_relu_bwd: groups = %d (1 or 2)", groups);
+    SN_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "bn_relu_bwd: M = %ld, C = %d (C %% 4 != 0 or an empty tensor)", M, C);
+    SN_REQUIRE(x0 && g0 && stats0 && gamma && d_gamma && d_beta && d_x0 && partial && coef0, "bn_relu_bwd: null pointer");
+    SN_REQUIRE(groups == 1 || (x1 && g1 && stats1 && d_x1 && coef1), "bn_relu_bwd: null pointer (second group)");
+    SN_REQUIRE(groups == 1 || ((addend0 == nullptr) == (addend1 == nullptr)), "bn_relu_bwd: an addend for one group only");
+    if (addend0 != nullptr) {
+        SN_REQUIRE(add_stride >= 1, "bn_relu_bwd: add_stride = %d", add_stride);
+        SN_REQUIRE(add_stride == 1 || (H > 0 && W > 0 && M % ((long)H * W) == 0),
+                   "bn_relu_bwd: a strided addend needs H, W with M = N*H*W (M = %ld, H = %d, W = %d)", M, H, W);
+    }
+    if (int rc = check_device_all({x0, g0, stats0, addend0, d_x0, coef0, groups == 2 ? x1 : nullptr, groups == 2 ? g1 : nullptr,
+                                   groups == 2 ? stats1 : nullptr, groups == 2 ? addend1 : nullptr, groups == 2 ? d_x1 : nullptr,
+                                   groups == 2 ? coef1 : nullptr, gamma, d_gamma, d_beta, partial},
+                                  "bn_relu_bwd: an argument", (hipStream_t)stream)) return rc;
+    const float* x[2] = {x0, x1};
+    const float* g[2] = {g0, g1};
+    const float* sc[2] = {stats0, stats1};
+    const float *sh[2] = {nullptr, nullptr}, *mu[2] = {nullptr, nullptr}, *is[2] = {nullptr, nullptr};
+    for (int i = 0; i < groups; ++i) { sh[i] = sc[i] + C; mu[i] = sc[i] + 2 * (size_t)C; is[i] = sc[i] + 3 * (size_t)C; }
+    const float* ad[2] = {addend0, addend1};
+    float* dx[2] = {d_x0, d_x1};
+    float* cf[2] = {coef0, coef1};
+    return launch_bn_relu_bwd_g(groups, x, g, sc, sh, mu, is, gamma, M, C, addend0 ? ad : nullptr, addend0 ? add_stride : 1, H, W,
+                                d_gamma, d_beta, dx, partial, cf, (hipStream_t)stream);
+}
+
+int stabnet_bias_grad(int groups, const float* g0, const float* g1, long M, int C, float* d_bias, float* d_bias2, float* partial,
+                      void* stream) {
+    SN_REQUIRE(groups == 1 || groups == 2, "bias_grad: groups = %d (1 or 2)", groups);
+    SN_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "bias_grad: M = %ld, C = %d (C %% 4 != 0 or an empty tensor)", M, C);
+    SN_REQUIRE(g0 && d_bias && partial && (groups == 1 || g1), "bias_grad: null pointer");
+    if (int rc = check_device_all({g0, groups == 2 ? g1 : nullptr, d_bias, d_bias2, partial}, "bias_grad: an argument", (hipStream_t)stream))
+        return rc;
+    const float* g[2] = {g0, g1};
+    return launch_bias_grad_g(groups, g, M, C, d_bias, partial, (hipStream_t)stream, d_bias2);
+}
+
+static int pool_args_ok(int N, int H, int W, int C, int Ho, int Wo, int k, int stride, int pt, int pl) {
+    return N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0 && k > 0 && stride > 0 && pt >= 0 && pl >= 0 && pt < k && pl < k &&
+           k * k <= 255 && (long)(Ho - 1) * stride - pt < H && (long)(Wo - 1) * stride - pl < W;
+}
+
+int stabnet_max_pool_train_fwd(const float* x, float* y, unsigned char* argmax, int N, int H, int W, int C, int Ho, int Wo, int k,
+                               int stride, int pt, int pl, void* stream) {
+    SN_REQUIRE(x && y && argmax, "max_pool_train_fwd: null pointer");
+    SN_REQUIRE(pool_args_ok(N, H, W, C, Ho, Wo, k, stride, pt, pl), "max_pool_train_fwd: bad geometry (a window outside the image, k*k > 255)");
+    if (int rc = check_device_all({x, y, argmax}, "max_pool_train_fwd: an argument", (hipStream_t)stream)) return rc;
+    return launch_max_pool_argmax(x, y, argmax, N, H, W, C, Ho, Wo, k, stride, pt, pl, (hipStream_t)stream);
+}
+
+int stabnet_max_pool_bwd(const unsigned char* argmax, const float* dy, float* dx, int N, int H, int W, int C, int Ho, int Wo, int k,
+                         int stride, int pt, int pl, void* stream) {
+    SN_REQUIRE(argmax && dy && dx, "max_pool_bwd: null pointer");
+    SN_REQUIRE(pool_args_ok(N, H, W, C, Ho, Wo, k, stride, pt, pl), "max_pool_bwd: bad geometry (a window outside the image, k*k > 255)");
+    if (int rc = check_device_all({argmax, dy, dx}, "max_pool_bwd: an argument", (hipStream_t)stream)) return rc;
+    return launch_max_pool_bwd(argmax, dy, dx, N, H, W, C, Ho, Wo, k, stride, pt, pl, (hipStream_t)stream);
+}
+
+int stabnet_gap_bwd(const float* dg, int N, int HW, int C, float* da, void* stream) {
+    SN_REQUIRE(dg && da, "gap_bwd: null pointer");
+    SN_REQUIRE(N > 0 && HW > 0 && C > 0, "gap_bwd: N = %d, HW = %d, C = %d", N, HW, C);
+    if (int rc = check_device_all({dg, da}, "gap_bwd: an argument", (hipStream_t)stream)) return rc;
+    return launch_gap_bwd(dg, N, HW, C, da, (hipStream_t)stream);
+}
+
+size_t stabnet_fc_bwd_scratch_floats(int M, int K, int Nout) {
+    if (M <= 0 || K <= 0 || Nout <= 0) return 0;
+    return (size_t)cdiv(Nout, fc_bwd_x_rows(K, Nout)) * M * K;
+}
+
+int stabnet_fc_bwd(const float* x, const float* w, const float* y, const float* dy, int M, int K, int Nout, int relu, float* dW,
+                   float* db, float* dx, float* scratch, size_t scratch_floats, void* stream) {
+    SN_REQUIRE(M > 0 && K > 0 && K % 4 == 0 && Nout > 0 && Nout <= 65535, "fc_bwd: M = %d, K = %d (K %% 4 != 0?), Nout = %d", M, K, Nout);
+    SN_REQUIRE(x && w && dy && dW && db, "fc_bwd: null pointer");
+    SN_REQUIRE((relu != 0) == (y != nullptr), "fc_bwd: y is the layer's output when relu = 1 and NULL when relu = 0");
+    if (int rc = check_device_all({x, w, y, dy, dW, db, dx, dx ? scratch : nullptr}, "fc_bwd: an argument", (hipStream_t)stream)) return rc;
+    return launch_fc_bwd(x, w, y, dy, M, K, Nout, relu ? 1 : 0, dW, db, dx, scratch, scratch_floats, (hipStream_t)stream);
+}
+
+}  // extern "C"

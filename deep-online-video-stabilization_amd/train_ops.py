@@ -90,3 +90,87 @@ def mesh_losses(theta, d_pts2_warp, cfg: Config, w_id, w_dist, w_cons, use_black
               cfg.id_mul, float(w_id), float(w_dist), float(w_cons), float(use_black), float(w_black), ptr(losses),
               ptr(d_theta), stream_ptr(theta.device), device=theta.device)
     return losses, d_theta
+
+
+# ---- the non-convolution training layers, one operator per call (the launchers of the training step) ----------------------
+
+def col_reduce_workspace_floats(M, C, groups=1):
+    return int(_lib.lib().stabnet_col_reduce_workspace_floats(M, C, groups))
+
+
+def _pair(ts):
+    """(ptr0, ptr1) of a 1- or 2-element list of tensors (or None)."""
+    if ts is None:
+        return 0, 0
+    return ptr(ts[0]), (ptr(ts[1]) if len(ts) > 1 else 0)
+
+
+def bn_stats_train(xs, gamma, beta, eps, decay, stats, mov_mean=None, mov_var=None, partial=None):
+    """xs: one or two [M, C] tensors (the towers); stats: as many [4, C] outputs (scale, shift, mean, invstd)."""
+    M, C = xs[0].shape
+    if partial is None:
+        partial = empty((col_reduce_workspace_floats(M, C, len(xs)),), xs[0])
+    _lib.call("stabnet_bn_stats_train", len(xs), *_pair(xs), M, C, ptr(gamma), ptr(beta), float(eps), float(decay), *_pair(stats),
+              ptr(mov_mean), ptr(mov_var), ptr(partial), stream_ptr(xs[0].device), device=xs[0].device)
+    return stats
+
+
+def bn_relu_bwd(xs, gs, stats, gamma, d_gamma, d_beta, d_xs, coefs, addends=None, add_stride=1, H=0, W=0, partial=None):
+    M, C = xs[0].shape
+    if partial is None:
+        partial = empty((col_reduce_workspace_floats(M, C, len(xs)),), xs[0])
+    x0, x1 = _pair(xs)
+    g0, g1 = _pair(gs)
+    s0, s1 = _pair(stats)
+    a0, a1 = _pair(addends)
+    d0, d1 = _pair(d_xs)
+    c0, c1 = _pair(coefs)
+    _lib.call("stabnet_bn_relu_bwd", len(xs), x0, x1, g0, g1, s0, s1, ptr(gamma), M, C, a0, a1, int(add_stride), int(H), int(W),
+              ptr(d_gamma), ptr(d_beta), d0, d1, ptr(partial), c0, c1, stream_ptr(xs[0].device), device=xs[0].device)
+    return d_xs
+
+
+def bias_grad(gs, d_bias, d_bias2=None, partial=None):
+    M, C = gs[0].shape
+    if partial is None:
+        partial = empty((col_reduce_workspace_floats(M, C, len(gs)),), gs[0])
+    _lib.call("stabnet_bias_grad", len(gs), *_pair(gs), M, C, ptr(d_bias), ptr(d_bias2), ptr(partial), stream_ptr(gs[0].device),
+              device=gs[0].device)
+    return d_bias
+
+
+def max_pool_train_fwd(x, y, argmax, k, stride, pt, pl):
+    """x [N,H,W,C] -> y [N,Ho,Wo,C] and the argmax bytes (uint8, same shape); Ho, Wo are taken from y."""
+    N, H, W, C = x.shape
+    _lib.call("stabnet_max_pool_train_fwd", ptr(x), ptr(y), ptr(argmax), N, H, W, C, y.shape[1], y.shape[2], k, stride, pt, pl,
+              stream_ptr(x.device), device=x.device)
+    return y, argmax
+
+
+def max_pool_bwd(argmax, dy, dx, k, stride, pt, pl):
+    N, H, W, C = dx.shape
+    _lib.call("stabnet_max_pool_bwd", ptr(argmax), ptr(dy), ptr(dx), N, H, W, C, dy.shape[1], dy.shape[2], k, stride, pt, pl,
+              stream_ptr(dx.device), device=dx.device)
+    return dx
+
+
+def gap_bwd(dg, da):
+    """dg [N,C] -> da [N,HW,C]."""
+    N, HW, C = da.shape
+    _lib.call("stabnet_gap_bwd", ptr(dg), N, HW, C, ptr(da), stream_ptr(da.device), device=da.device)
+    return da
+
+
+def fc_bwd_scratch_floats(M, K, Nout):
+    return int(_lib.lib().stabnet_fc_bwd_scratch_floats(M, K, Nout))
+
+
+def fc_bwd(x, w, y, dy, dW, db, dx=None, scratch=None):
+    """y = None: no ReLU.  dW, db are accumulated into; dx (optional) is written."""
+    M, K = x.shape
+    Nout = w.shape[0]
+    if dx is not None and scratch is None:
+        scratch = empty((fc_bwd_scratch_floats(M, K, Nout),), x)
+    _lib.call("stabnet_fc_bwd", ptr(x), ptr(w), ptr(y), ptr(dy), M, K, Nout, int(y is not None), ptr(dW), ptr(db), ptr(dx),
+              ptr(scratch), 0 if scratch is None else scratch.numel(), stream_ptr(x.device), device=x.device)
+    return dW, db, dx

@@ -365,6 +365,66 @@ int stabnet_net_train_bn_offsets(const void* net, long* scale_off, long* shift_o
  * argmax bytes, byte count), "pool". */
 int stabnet_net_train_debug_offset(const void* net, const char* what, long* off, long* count);
 
+/* ---- training: the non-convolution layers of the tower, one entry per operator ------------------------------
+ * The launchers that stabnet_tower(s)_fwd_train / _bwd* run (slim resnet_v2_50 + FC head under is_training=True and their
+ * autodiff: s_net_bundle_nobm.py:252-258, minimised at train_bundle_nobm.py:160), reachable one at a time.  Tensors are
+ * [M][C] row-major (M = N*H*W pixels, C % 4 == 0).  groups = 1 | 2: the same operator on both siamese towers in one launch each
+ * (train_bundle_nobm.py:107-108); the arguments ending in 1 are read only when groups = 2.  Every sum is taken in a fixed order
+ * (no atomics): the same call gives the same bits, and groups = 2 gives the bits of two groups = 1 calls in order.
+ * `partial`: stabnet_col_reduce_workspace_floats(M, C, groups) floats (0 = bad arguments). */
+size_t stabnet_col_reduce_workspace_floats(long M, int C, int groups);
+
+/* slim batch_norm(is_training=True) statistics (resnet_v2.resnet_arg_scope, s_net_bundle_nobm.py:252): tf.nn.moments over the M
+ * rows -> stats [4][C] per group = {scale = gamma * invstd, shift = beta - mean * scale, mean, invstd = 1 / sqrt(var + eps)} with
+ * the BIASED variance, and the moving averages mov -= (mov - value) * (1 - decay) (UPDATE_OPS, s_net_bundle_nobm.py:355-356;
+ * group 0's update, then group 1's; both NULL = left alone).
+ * Conditioning: the variance is formed as E[x^2] - mean^2 in one pass, not in the two passes of tf.nn.moments, which amplifies
+ * the rounding of the two sums by 1 + r^2, r = |mean| / std of the channel.  The sums are therefore taken in float64 (float32
+ * products are exact there): the variance error stays inside (1 + r^2) * 2^-23 -- asserted per channel for r = 0 .. 100 at every
+ * layer size of the 8 x 288 x 512 step -- and is in fact the rounding of the float32 result, 2^-24, up to r ~ 10^4.
+ * partial must be 8-byte aligned. */
+int stabnet_bn_stats_train(int groups, const float* x0, const float* x1, long M, int C, const float* gamma, const float* beta,
+                           float eps, float decay, float* stats0, float* stats1, float* mov_mean, float* mov_var, float* partial,
+                           void* stream);
+
+/* Autodiff of relu(batch_norm(x)) with batch statistics (the preact / conv BN + ReLU sites of resnet_v2 `bottleneck`):
+ * dz = g * (fma(x, scale, shift) > 0), xhat = (x - mean) * invstd,
+ * d_x = gamma * invstd * (dz - mean_M(dz) - xhat * mean_M(dz * xhat)) (+ addend), d_gamma += sum dz * xhat, d_beta += sum dz
+ * (both ACCUMULATED into, group 0 then group 1).  stats: what stabnet_bn_stats_train wrote.  d_x may alias g.
+ * addend (optional, NULL): the gradient arriving over the identity shortcut; add_stride = 1: [M][C]; add_stride = s > 1 (slim
+ * `subsample`): [N][ceil(H/s)][ceil(W/s)][C], added at the pixels with y % s == 0 and x % s == 0 (H, W are read only then,
+ * M = N*H*W).  coef: [3][C] floats of scratch per group. */
+int stabnet_bn_relu_bwd(int groups, const float* x0, const float* x1, const float* g0, const float* g1, const float* stats0,
+                        const float* stats1, const float* gamma, long M, int C, const float* addend0, const float* addend1,
+                        int add_stride, int H, int W, float* d_gamma, float* d_beta, float* d_x0, float* d_x1, float* partial,
+                        float* coef0, float* coef1, void* stream);
+
+/* d_bias [C] += column sums of g (group 0 then group 1) -- autodiff of slim conv2d's bias add; d_bias2 (optional, NULL) receives
+ * the same increment: the conv3 and projection-shortcut biases of a unit add into the same tensor. */
+int stabnet_bias_grad(int groups, const float* g0, const float* g1, long M, int C, float* d_bias, float* d_bias2, float* partial,
+                      void* stream);
+
+/* slim max_pool2d [3,3] stride 2 of resnet_v2 ('pool1'), training form: y [N,Ho,Wo,C] and argmax bytes [N,Ho,Wo,C] = dy*k + dx of
+ * the FIRST maximum in scan order (rows, then columns) over the in-image taps of the window at (oy*stride - pt, ox*stride - pl).
+ * Backward (gather, no atomics): dx [N,H,W,C] = sum of the dy of every window whose argmax points at the pixel (written, not
+ * accumulated).  k*k <= 255. */
+int stabnet_max_pool_train_fwd(const float* x, float* y, unsigned char* argmax, int N, int H, int W, int C, int Ho, int Wo, int k,
+                               int stride, int pt, int pl, void* stream);
+int stabnet_max_pool_bwd(const unsigned char* argmax, const float* dy, float* dx, int N, int H, int W, int C, int Ho, int Wo, int k,
+                         int stride, int pt, int pl, void* stream);
+
+/* Autodiff of tf.reduce_mean(resnet, [1, 2]) (s_net_bundle_nobm.py:254): da [N,HW,C] = dg [N,C] / HW (one float32 division). */
+int stabnet_gap_bwd(const float* dg, int N, int HW, int C, float* da, void* stream);
+
+/* Autodiff of slim.fully_connected (s_net_bundle_nobm.py:256-258 with ReLU, the output layer without): x [M,K], w [Nout][K],
+ * y [M,Nout] = the layer's output (relu = 1; NULL when relu = 0), dy [M,Nout].  dyr = dy * (y > 0) when relu;
+ * dW [Nout][K] += dyr^T x, db [Nout] += column sums of dyr (both ACCUMULATED into), dx [M,K] = dyr w (written; NULL = not
+ * wanted).  K % 4 == 0.  scratch: stabnet_fc_bwd_scratch_floats(M, K, Nout) floats, read and written only when dx is given;
+ * a smaller one is refused (STABNET_ERR_BAD_ARG) before anything is launched. */
+size_t stabnet_fc_bwd_scratch_floats(int M, int K, int Nout);
+int stabnet_fc_bwd(const float* x, const float* w, const float* y, const float* dy, int M, int K, int Nout, int relu, float* dW,
+                   float* db, float* dx, float* scratch, size_t scratch_floats, void* stream);
+
 /* slim L2 regularisers (REGULARIZATION_LOSSES, s_net_bundle_nobm.py:324-325; resnet.py:35-37): *loss_out +=
  * sum_seg coef*0.5*sum w^2 (NULL to skip), grads[seg] += gscale*coef*w (NULL to skip).  seg_* are DEVICE arrays.
  * workspace: 64*nseg floats (block partials of the value; may be NULL when loss_out is). */
