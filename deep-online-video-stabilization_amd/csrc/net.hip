@@ -721,6 +721,9 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_MJPEG_ENTROPY: return "mjpeg_entropy_kernel";
         case PK_KERNEL_MJPEG_LAYOUT: return "mjpeg_layout_kernel";
         case PK_KERNEL_MJPEG_GATHER: return "mjpeg_gather_kernel";
+        case PK_KERNEL_INGEST_GREY_ROWS: return "ingest_grey_rows_kernel";
+        case PK_KERNEL_INGEST_GREY_COLS: return "ingest_grey_cols_kernel";
+        case PK_KERNEL_INGEST_COLOUR: return "ingest_colour_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

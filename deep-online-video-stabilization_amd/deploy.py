@@ -127,6 +127,9 @@ class StabNetStream:
         self.all_black = None                             # optional int32 [S,H,W]: += round(black) per refine pass (:291)
         self.use_graph = use_graph
         self._graph = None
+        self._graph_u8 = None                             # step_u8's frame graph: ingest launches + the frame
+        self.cur_u8 = None                                # fixed-address uint8 staging buffer of the raw frame (step_u8)
+        self._ingest = None
         self.started = False
 
     @property
@@ -146,7 +149,7 @@ class StabNetStream:
     def track_black(self, enable: bool = True):
         """Accumulate all_black (deploy_bundle.py:234,291) on the device for the crop search; reset by start()."""
         self.all_black = (torch.zeros((self.S, self.H, self.W), dtype=torch.int32, device=self.reg.device) if enable else None)
-        self._graph = None
+        self._graph = self._graph_u8 = None
         return self.all_black
 
     def _enqueue(self, prof=None, cur=None):
@@ -186,6 +189,61 @@ class StabNetStream:
         return {"output": self.out_img, "black_pix": self.black, "Hs": self.Hs, "x_map": self.x_map,
                 "y_map": self.y_map, "theta": self.theta, "frame": self.frame_fb}
 
+    def _bind_ingest(self, ingest):
+        if (ingest.H, ingest.W) != (self.H, self.W) or ingest.device != self.reg.device:
+            raise _lib.StabnetError("StabNetStream: ingest produces %dx%d on %s, the stream runs %dx%d on %s"
+                                    % (ingest.H, ingest.W, ingest.device, self.H, self.W, self.reg.device))
+        if ingest is not self._ingest:
+            self._ingest, self._graph_u8 = ingest, None
+            self.cur_u8 = torch.empty((self.S, ingest.sh, ingest.sw, ingest.C), dtype=torch.uint8, device=self.reg.device)
+            ingest._reserve(self.S)
+
+    def _stage_u8(self, frame_u8, ingest, what):
+        self._bind_ingest(ingest)
+        if not isinstance(frame_u8, torch.Tensor) or not frame_u8.is_cuda or frame_u8.dtype != torch.uint8:
+            raise _lib.StabnetError("%s: expected a uint8 tensor on the GPU (there is no CPU fallback)" % what)
+        if frame_u8.numel() != self.cur_u8.numel():
+            raise _lib.StabnetError("%s: expected %s, got %s" % (what, list(self.cur_u8.shape), list(frame_u8.shape)))
+        self.cur_u8.copy_(frame_u8.reshape(self.cur_u8.shape))                         # D2D into the fixed buffer
+
+    def start_u8(self, frame_u8: torch.Tensor, ingest):
+        """start() from the raw first frames: uint8 [S,src_h,src_w,C] as read from the video; `ingest` (ingest.FrameIngest) converts
+        them on the device (cvt_img2train, config.py:6-21) straight into the staging buffer the ring is seeded from."""
+        self._stage_u8(frame_u8, ingest, "start_u8")
+        ingest.grey(self.cur_u8, out=self.cur)
+        self.start(self.cur)
+
+    def _enqueue_u8(self, prof=None):
+        self._ingest.grey(self.cur_u8, out=self.cur, prof=prof)
+        self._enqueue(prof)
+
+    def step_u8(self, frame_u8: torch.Tensor, ingest, prof: Profiler = None):
+        """step() from the raw frames: the ingest launches write the grey frame into self.cur in front of the frame's own launches;
+        with use_graph they are captured with it and read the fixed uint8 staging buffer self.cur_u8."""
+        if not self.started:
+            raise _lib.StabnetError("StabNetStream.step_u8 before start_u8(first_frame, ingest)")
+        self._stage_u8(frame_u8, ingest, "step_u8")
+        if self.use_graph and prof is None:
+            if self._graph_u8 is None:
+                self._enqueue_u8()                   # this frame runs eagerly (also loads modules / sets kernel attributes)
+                torch.cuda.synchronize()
+                try:
+                    with torch.cuda.device(self.reg.device):
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):    # capture records only; nothing executes here
+                            self._enqueue_u8()
+                    self._graph_u8 = g
+                except Exception as e:               # capture unsupported on this runtime: stay eager, say so once
+                    import sys
+                    print("StabNetStream: hipGraph capture failed (%s); continuing without a graph" % e, file=sys.stderr)
+                    self.use_graph = False
+            else:
+                self._graph_u8.replay()
+        else:
+            self._enqueue_u8(prof)
+        return {"output": self.out_img, "black_pix": self.black, "Hs": self.Hs, "x_map": self.x_map,
+                "y_map": self.y_map, "theta": self.theta, "frame": self.frame_fb}
+
 
 class ClipPipeline:
     """A clip that lives in HOST memory through one StabNetStream, with upload, frame and download on three HIP streams.
@@ -208,9 +266,14 @@ class ClipPipeline:
     valid until the sink returns).  run(..., raw=False) then skips the raw downloads ("output" / "bgr" are absent): what crosses PCIe
     per frame is the compressed frame.  Its length is only known on the device, so the download is a FIXED first chunk (jpeg_chunk
     bytes: a quarter of the raw frame, several times a q75 frame) together with the length; the rare frame that is longer gets the
-    rest by a second, synchronous copy when it is handed over."""
+    rest by a second, synchronous copy when it is handed over.
 
-    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None):
+    ingest=FrameIngest: the clip is the RAW one -- run(frames_u8, ...), uint8 [src_h,src_w,C] frames of any size as read from the
+    video.  A slot then uploads ONE uint8 frame at source size, and the slot's frame graph starts with the ingest launches
+    (csrc/ingest.hip: grey conversion + Pillow resize into the stream's staging buffer; cv2.resize of the colour frame, which the
+    remap then reads).  The host converts nothing."""
+
+    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
@@ -221,12 +284,22 @@ class ClipPipeline:
         self.dev = dev
         pin = lambda shape, dt: torch.empty(shape, dtype=dt, pin_memory=True)
         on = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        self.h_grey = [pin((H, W), torch.float32) for _ in range(slots)]
-        self.d_grey = [on((1, H, W), torch.float32) for _ in range(slots)]
+        self.ingest = ingest
+        if ingest is not None:
+            if colour and ingest.C != 3:
+                raise _lib.StabnetError("ClipPipeline: colour=True needs a BGR source, the ingest reads %d channel(s)" % ingest.C)
+            stream._bind_ingest(ingest)
+            src = (ingest.sh, ingest.sw, ingest.C)
+            self.h_u8 = [pin(src, torch.uint8) for _ in range(slots)]
+            self.d_u8 = [on((1,) + src, torch.uint8) for _ in range(slots)]
+        else:
+            self.h_grey = [pin((H, W), torch.float32) for _ in range(slots)]
+            self.d_grey = [on((1, H, W), torch.float32) for _ in range(slots)]
         self.h_out = [pin((H, W), torch.uint8) for _ in range(slots)]
         self.d_out = [on((H, W), torch.uint8) for _ in range(slots)]
         if colour:
-            self.h_bgr = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
+            if ingest is None:
+                self.h_bgr = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_bgr = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
             self.h_warp = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_warp = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
@@ -253,7 +326,14 @@ class ClipPipeline:
     def _frame(self, k: int, maps: bool):
         """Everything frame-shaped of slot k on the current stream: the frame, its results into the slot's buffers."""
         st, H, W = self.st, self.st.H, self.st.W
-        st._enqueue(cur=self.d_grey[k])                      # the frame reads the upload slot itself: no staging copy
+        if self.ingest is not None:
+            # cvt_img2train (config.py:6-21) and cv2.resize (deploy_bundle.py:303) of the raw frame in the upload slot
+            self.ingest.grey(self.d_u8[k], out=st.cur)
+            if self.colour:
+                self.ingest.colour(self.d_u8[k], out=self.d_bgr[k])
+            st._enqueue()
+        else:
+            st._enqueue(cur=self.d_grey[k])                  # the frame reads the upload slot itself: no staging copy
         # cvt_train2img (deploy_bundle.py:75)
         _lib.call("stabnet_cvt_train2img", ptr(st.out_img), ptr(self.d_out[k]), H * W, stream_ptr(self.dev), device=self.dev)
         if self.colour:
@@ -301,7 +381,7 @@ class ClipPipeline:
         if not raw and self.enc is None:
             raise _lib.StabnetError("ClipPipeline.run: raw=False needs a pipeline built with jpeg=...: nothing would come back")
         self.jpeg_bytes_down = 0
-        if self.colour and bgr is None:
+        if self.colour and bgr is None and self.ingest is None:
             raise _lib.StabnetError("ClipPipeline.run: this pipeline was built with colour=True, bgr frames are required")
         if maps and self.h_maps is None:
             self.h_maps = tuple([torch.empty((H, W), dtype=dt, pin_memory=True) for _ in range(K)]
@@ -314,8 +394,12 @@ class ClipPipeline:
         self.host_wait_s = 0.0                                # time the host spent blocked on a slot: ~0 means the HOST is the bound
         torch.cuda.synchronize(self.dev)
         with torch.cuda.stream(self.s_run):
-            first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.float32)).to(self.dev)
-            st.start(first[None])
+            if self.ingest is not None:
+                first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.uint8)).to(self.dev)
+                st.start_u8(first, self.ingest)
+            else:
+                first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.float32)).to(self.dev)
+                st.start(first[None])
         pending = [None] * K                                  # frame number whose results sit in (or are on their way to) slot k
         for t in range(1, n):
             k = t % K
@@ -325,12 +409,18 @@ class ClipPipeline:
                 self.host_wait_s += time.perf_counter() - w0
                 emit(self._result(k, pending[k], maps, raw))
                 pending[k] = None
-            self.h_grey[k].numpy()[...] = grey[t]
-            if self.colour:
-                self.h_bgr[k].numpy()[...] = bgr[t]
-            with torch.cuda.stream(self.s_in):
-                self.d_grey[k].copy_(self.h_grey[k].view(1, H, W), non_blocking=True)
+            if self.ingest is not None:
+                self.h_u8[k].numpy()[...] = np.asarray(grey[t]).reshape(self.h_u8[k].shape)
+            else:
+                self.h_grey[k].numpy()[...] = grey[t]
                 if self.colour:
+                    self.h_bgr[k].numpy()[...] = bgr[t]
+            with torch.cuda.stream(self.s_in):
+                if self.ingest is not None:
+                    self.d_u8[k].copy_(self.h_u8[k].view(self.d_u8[k].shape), non_blocking=True)
+                else:
+                    self.d_grey[k].copy_(self.h_grey[k].view(1, H, W), non_blocking=True)
+                if self.colour and self.ingest is None:
                     self.d_bgr[k].copy_(self.h_bgr[k].view(1, H, W, 3), non_blocking=True)
                 self.ev_up[k].record(self.s_in)
             with torch.cuda.stream(self.s_run):

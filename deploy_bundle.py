@@ -12,6 +12,10 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     (stabilised grey frames, x/y maps, black masks).  --mjpg also writes what the reference's cv2.VideoWriter('MJPG')
     writes (deploy_bundle.py:197-198,215,305,366-371): <name>.avi (the first frame as read, then every stabilised frame)
     and <name>_cut.avi (the crop), every frame a baseline JPEG encoded on the GPU (csrc/mjpeg.hip).
+  * --ingest device: the frame as read (uint8, any size, BGR or grey) is uploaded once and converted on the GPU with the reference's
+    own arithmetic (csrc/ingest.hip: cv2.cvtColor + PIL BILINEAR resize + normalisation for the network, cv2.resize for the colour
+    frame that is warped and written), so a 720p colour clip run at 288x512 keeps its colour outputs.  The default, --ingest host,
+    converts on the host with a two-tap resize and keeps colour only for clips that already have the network's size.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -60,6 +64,11 @@ def build_parser():
                    help='also write <output-dir>/output/<name>.avi and <name>_cut.avi (Motion-JPEG, encoded on the GPU) as the reference does')
     p.add_argument('--jpeg-quality', type=int, default=75)
     p.add_argument('--jpeg-subsampling', default='420', choices=['420', '444'])
+    p.add_argument('--ingest', default='host', choices=['host', 'device'],
+                   help='where a frame becomes the network input: host = NumPy (two-tap resize, colour only at the network size); device = '
+                        'stabnet_amd.ingest.FrameIngest, the reference\'s cv2/PIL chain on the GPU for uint8 clips of any size')
+    p.add_argument('--gray-weights', default='cv3', choices=['cv3', 'cv4'],
+                   help='--ingest device: fixed-point BGR2GRAY weights of OpenCV 3 (the reference\'s era) or OpenCV 4')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
 
@@ -117,29 +126,37 @@ def jpeg_options(args):
     return dict(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
 
 
-def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None):
+def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
-    fps = frames / time inside the step, as the reference prints it (:285-289)."""
+    fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
+    uploaded and converted on the GPU inside the step."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
-    first = grey_train(clip[0], H, W)
-    stream.start(torch.from_numpy(first[None]).to(dev))                       # ring = 32 x first frame, zero masks
+    raw = lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
+    if ing is not None:
+        stream.start_u8(raw(0), ing)
+    else:
+        first = grey_train(clip[0], H, W)
+        stream.start(torch.from_numpy(first[None]).to(dev))                   # ring = 32 x first frame, zero masks
     for t in range(1, len(clip)):
-        cur = torch.from_numpy(grey_train(clip[t], H, W)[None]).to(dev)
+        cur = raw(t) if ing is not None else torch.from_numpy(grey_train(clip[t], H, W)[None]).to(dev)
         torch.cuda.synchronize()
         start = time.time()
-        r = stream.step(cur)                                                  # one sess.run-equivalent
+        r = stream.step_u8(cur, ing) if ing is not None else stream.step(cur)     # one sess.run-equivalent
         torch.cuda.synchronize()
         tot_time += time.time() - start
-        if is_colour(clip[t], H, W):
+        if ing is not None and ing.C == 3:
+            # cv2.resize of the colour frame (deploy_bundle.py:303), then warpRevBundle2, both on the device
+            colour_out.append(warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map']).cpu().numpy())
+        elif ing is None and is_colour(clip[t], H, W):
             # warpRevBundle2 (deploy_bundle.py:136-146,303) on the device: colour frame remapped by the smoothed maps
             bgr = torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
             colour_out.append(warp.warpRevBundle2(bgr, r['x_map'], r['y_map']).cpu().numpy())
         net_output = ((r['output'][0, :, :, 0].cpu().numpy() + 0.5) * 255).clip(0, 255).astype(np.uint8)
         frames_out.append(net_output)
         if jpeg_sink is not None:                                             # the frame that is kept, compressed on the device
-            kept = colour_out[-1] if is_colour(clip[t], H, W) else net_output
+            kept = colour_out[-1] if (ing.C == 3 if ing is not None else is_colour(clip[t], H, W)) else net_output
             jpeg_sink(enc.encode_bytes(torch.from_numpy(np.ascontiguousarray(kept)).to(dev))[0])
         xmaps.append(r['x_map'][0, :, :, 0].cpu().numpy()); ymaps.append(r['y_map'][0, :, :, 0].cpu().numpy())
         blacks.append(r['black_pix'][0].cpu().numpy().astype(np.uint8))
@@ -150,11 +167,11 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     return length, tot_time
 
 
-def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None):
+def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included."""
     from stabnet_amd.deploy import ClipPipeline
-    colour = is_colour(clip[0], H, W)
+    colour = ing.C == 3 if ing is not None else is_colour(clip[0], H, W)
 
     class Grey:                                                               # frames converted as the pipeline asks for them
         def __len__(self):
@@ -174,7 +191,10 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
             print('length: ' + str(len(frames_out)))
 
     start = time.time()
-    ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
+    if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
+        ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing).run(clip, sink=sink, maps=True)
+    else:
+        ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
     tot_time = time.time() - start
     if frames_out:
         print('fps={}'.format(len(frames_out) / tot_time))
@@ -246,20 +266,36 @@ def main():
         frames_out, xmaps, ymaps, blacks, colour_out = [], [], [], [], []
         stem = os.path.join(out_dir, os.path.splitext(os.path.basename(name))[0])
         writer, enc, fps = None, None, fps_of.get(name, args.fps)
+        ing = None
         try:
+            if args.ingest == 'device':
+                shp = np.shape(clip[0])
+                if np.asarray(clip[0]).dtype == np.uint8 and (len(shp) == 2 or (len(shp) == 3 and shp[2] in (1, 3))):
+                    from stabnet_amd.ingest import FrameIngest
+                    ing = FrameIngest(shp[0], shp[1], 1 if len(shp) == 2 else shp[2], H, W, gray=args.gray_weights, device=dev)
+                    print('note: --ingest device: %dx%dx%d uint8 frames -> %dx%d on the GPU as the reference\'s cv2/PIL chain '
+                          '(cv2.cvtColor %s weights, PIL BILINEAR resize, * (1./255) - 0.5; cv2.resize for the colour frame)'
+                          % (ing.sh, ing.sw, ing.C, H, W, args.gray_weights))
+                else:
+                    print('note: --ingest device reads uint8 frames; this clip is %s %s: converted on the host as with --ingest host'
+                          % (np.asarray(clip[0]).dtype, list(shp)))
             if args.mjpg:
                 from stabnet_amd.avi import AviMjpegWriter
                 from stabnet_amd.mjpeg import MjpegEncoder
-                first = first_frame_u8(clip, H, W)
+                if ing is not None:                  # deploy_bundle.py:215: the cv2-resized first frame
+                    f0 = torch.from_numpy(np.ascontiguousarray(clip[0], dtype=np.uint8)).to(dev)
+                    first = (ing.colour(f0)[0] if ing.C == 3 else ((ing.grey(f0)[0] + 0.5) * 255).round().clamp(0, 255).to(torch.uint8)).cpu().numpy()
+                else:
+                    first = first_frame_u8(clip, H, W)
                 enc = MjpegEncoder(H, W, 3 if first.ndim == 3 else 1, device=dev, **jpeg_options(args))
                 writer = AviMjpegWriter(stem + '.avi', W, H, fps)
                 writer.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])          # deploy_bundle.py:215
             sink = writer.write if writer is not None else None
             if args.pipeline:
                 length, tot_time = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
-                                                 jpeg_options(args) if args.mjpg else None)
+                                                 jpeg_options(args) if args.mjpg else None, ing)
             else:
-                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc)
+                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:

@@ -493,6 +493,42 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
                          int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
                          size_t workspace_bytes, void* stream, void* prof);
 
+/* ---- in front of the path: frame ingest (config.py:6-21 cvt_img2train; deploy_bundle.py:215,303 cv2.resize) ----
+ * A uint8 frame as read from the video, of any size, to the network's grey input and the network-size colour frame.
+ * img uint8 [N,sh,sw,C], C = 3 BGR or C = 1 grey, rows row_stride_bytes apart (>= sw*C), frames sh*row_stride_bytes apart.  Every
+ * base pointer and row stride is accepted: aligned dwords are read where the address allows, bytes otherwise, and nothing
+ * outside the rows themselves.
+ * Grey: g = (b*wb + g*wg + r*wr + (1 << (shift-1))) >> shift, cv2.cvtColor(BGR2GRAY) on uint8 [external: restated, not linked;
+ * OpenCV 3: 1868, 9617, 4899, 14; OpenCV 4: 3735, 19235, 9798, 15]; skipped for C = 1.  Then PIL.Image.resize((rw, rh), BILINEAR):
+ * horizontal pass (skipped when rw == sw), rounded and clipped to 8 bits, vertical pass (skipped when rh == sh); per axis scale =
+ * in/out, support = max(scale, 1), ksize = (int)ceil(support)*2 + 1, output i reads source samples xmin .. xmin + n with
+ * xmin = max((int)(center - support + 0.5), 0), xmin + n = min((int)(center + support + 0.5), in), center = (i + 0.5)*scale, with the
+ * normalised triangle weights in 22-bit fixed point: pixel = clip((2^21 + sum src*kk) >> 22, 0, 255).  Only the window of H x W
+ * outputs at (dy, dx) of the (rh, rw) resize is evaluated (cvt_img2train's crop_rate branch resizes, then crops).  The result goes
+ * through lut256_dev, 256 floats made by the host as float32(float64(u) * (1./255) - 0.5) -- what TensorFlow is fed -- to out
+ * float32 [N,H,W].  Two launches: rows (grey + horizontal, the source row in LDS) into the workspace uint8 [N][rows needed][W], then
+ * columns + table.  The horizontal tap count is bounded by the LDS tile: ksize <= 8193 (a 4096x downscale), refused before the
+ * first launch otherwise; the vertical one is not bounded.
+ * Colour: cv2.resize(img, (W, H)), INTER_LINEAR, uint8 [external]: per axis f = (float)((d + 0.5)*src/dst - 0.5), s = floor(f), the
+ * taps s and min(s+1, src-1) with short(rint((1-f)*2048)), short(rint(f*2048)) (f = 0 at a clamped edge); horizontal sums S in int32,
+ * out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  One launch, out uint8 [N,H,W,3].
+ * Nothing allocates, synchronises or copies from the host inside stabnet_ingest_grey / _colour. */
+/* host; Pillow's taps of one axis: *ksize, bounds2 [out][2] = (xmin, n), kk [out][ksize] (cap = ints kk can take).  Returns
+ * out * ksize (with bounds2 and kk NULL: only that, and *ksize if given), -1 on bad arguments or a cap too small. */
+int stabnet_ingest_pil_taps(int in, int out, int* ksize, int* bounds2, int* kk, int cap);
+/* host; cv2's taps of one axis: ofs2 [dst][2] source indices, coef2 [dst][2] weights of 2048. */
+int stabnet_ingest_cv_taps(int src, int dst, int* ofs2, short* coef2);
+size_t stabnet_ingest_workspace_bytes(int N, int sh, int sw, int C, int rh, int rw, int H, int W);    /* for any window origin; 0 = bad arguments */
+/* x*_dev / y*_dev: what stabnet_ingest_pil_taps gives for (sw, rw) / (sh, rh), ON THE DEVICE (NULL allowed for a skipped pass). */
+int stabnet_ingest_grey(const unsigned char* img, int N, int sh, int sw, int C, size_t row_stride_bytes, int wb, int wg, int wr,
+                        int shift, int rh, int rw, int dy, int dx, int H, int W, const int* xbounds_dev, const int* xkk_dev, int xksize,
+                        const int* ybounds_dev, const int* ykk_dev, int yksize, const float* lut256_dev, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream, void* prof);
+/* x*_dev / y*_dev: what stabnet_ingest_cv_taps gives for (sw, W) / (sh, H), ON THE DEVICE.  C must be 3. */
+int stabnet_ingest_colour(const unsigned char* img, int N, int sh, int sw, int C, size_t row_stride_bytes, int H, int W,
+                          const int* xofs_dev, const short* xcoef_dev, const int* yofs_dev, const short* ycoef_dev, unsigned char* out,
+                          void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif

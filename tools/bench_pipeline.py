@@ -8,7 +8,11 @@ colour uint8 frames) in, stabilised colour frame + the network's grey output bac
   --jpeg    instead of the legs above: the pipeline with the raw download (today's leg), with the JPEG encoder in every frame graph
             + the raw download, and with the encoder and NO raw download (what crosses PCIe per frame is the compressed frame); the
             three alternate, each repeated --repeats times, fps, host_wait_s and bytes downloaded per frame beside each
-One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg]"""
+  --ingest  instead of the legs above: the pipeline as above (float32 grey + uint8 BGR uploaded at the network's size, converted by the
+            host beforehand) against ClipPipeline(ingest=FrameIngest): ONE uint8 BGR frame uploaded at the source size
+            (--src-height / --src-width, default the network's) and converted in the frame graph (csrc/ingest.hip); the two
+            alternate, each repeated --repeats times, fps, host_wait_s and bytes uploaded per frame beside each
+One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg | --ingest]"""
 import argparse
 import json
 import os
@@ -30,6 +34,9 @@ ap.add_argument("--width", type=int, default=1280)
 ap.add_argument("--slots", type=int, default=3)
 ap.add_argument("--jpeg", action="store_true")
 ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--ingest", action="store_true")
+ap.add_argument("--src-height", type=int, default=None)
+ap.add_argument("--src-width", type=int, default=None)
 ap.add_argument("--jpeg-quality", type=int, default=75)
 a = ap.parse_args()
 H, W, T = a.height, a.width, a.frames
@@ -121,6 +128,46 @@ def jpeg_legs():
     out["jpeg_only_over_raw"] = med(legs["jpeg_only"]["fps"]) / med(legs["raw"]["fps"])
     out["jpeg_and_raw_over_raw"] = med(legs["jpeg_and_raw"]["fps"]) / med(legs["raw"]["fps"])
 
+
+def ingest_legs():
+    """upload at the network's size (host-converted) / one raw uint8 frame + ingest launches, alternating in one process."""
+    from stabnet_amd.ingest import FrameIngest
+    sh, sw = a.src_height or H, a.src_width or W
+    src = synthetic.make_clip(sh, sw, 40, seed=1234).astype(np.float32) if (sh, sw) != (H, W) else base
+    g8 = ((src + 0.5) * 255).clip(0, 255)
+    raw = np.ascontiguousarray(np.stack([g8 * 0.8 + 20, g8, g8 * 0.65 + 60], -1).clip(0, 255).astype(np.uint8)[np.arange(T) % len(src)])
+    ing = FrameIngest(sh, sw, 3, H, W, device=dev)
+    pipes = {"uploaded_at_network_size": ClipPipeline(StabNetStream(params, H, W, cfg, device=dev, use_graph=True), colour=True, slots=a.slots),
+             "ingest": ClipPipeline(StabNetStream(params, H, W, cfg, device=dev, use_graph=True), colour=True, slots=a.slots, ingest=ing)}
+    args = {"uploaded_at_network_size": (grey, bgr), "ingest": (raw,)}
+    legs = {k: {"fps": [], "host_wait_s": []} for k in pipes}
+    legs["uploaded_at_network_size"]["bytes_up_per_frame"] = H * W * 4 + H * W * 3
+    legs["ingest"]["bytes_up_per_frame"] = sh * sw * 3
+    got_c, got_o = np.zeros((H, W, 3), np.uint8), np.zeros((H, W), np.uint8)
+    def sink(r):                                                                  # the consumer touches everything it was given
+        np.copyto(got_c, r["bgr"]); np.copyto(got_o, r["output"])
+    for name, pipe in pipes.items():
+        pipe.run(*(v[:120] for v in args[name]), sink=sink)                       # graph capture + warm-up
+    for _ in range(a.repeats):
+        for name, pipe in pipes.items():
+            t0 = time.perf_counter()
+            pipe.run(*args[name], sink=sink)
+            dt = time.perf_counter() - t0
+            legs[name]["fps"].append((T - 1) / dt)
+            legs[name]["host_wait_s"].append(pipe.host_wait_s)
+    med = lambda v: sorted(v)[len(v) // 2]
+    out["ingest_legs"] = legs
+    out["source"] = [sh, sw]
+    out["ingest_over_uploaded"] = med(legs["ingest"]["fps"]) / med(legs["uploaded_at_network_size"]["fps"])
+    f = legs["uploaded_at_network_size"]["fps"]
+    out["uploaded_leg_spread"] = (max(f) - min(f)) / med(f)
+
+
+if a.ingest:
+    ingest_legs()
+    out["slots"] = a.slots
+    print(json.dumps(out))
+    sys.exit(0)
 
 if a.jpeg:
     jpeg_legs()
