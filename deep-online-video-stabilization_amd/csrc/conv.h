@@ -48,10 +48,37 @@ struct Prof;
 // (conv_weight_image_floats / launch_weight_split_image), only the A fragments are split at run time; launches the packed ring
 // kernel cannot take (register-staged path, in-workgroup split-K) run the exact f32 MFMA kernels on a.w as before.
 int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof = nullptr, int bf16_operands = 0, const float* w_img = nullptr);
+
+// Which kernel a convolution runs: decided ONCE, by conv_route(), for the launcher (conv_launch), for the plan-time launch count
+// (conv_reduce_launches) and for the Profiler's kernel name alike.
+enum ConvFamily {
+    CONV_IGEMM,        // register-staged conv_igemm_f32_kernel<tile, bk, ..., mode, nbuf, operand>
+    CONV_RING,         // LDS-DMA ring, conv_ring_f32_kernel<mode, operand, 1, 0>
+    CONV_RING_KG,      // ... K groups inside the workgroup: <mode, operand, 3, 0>, or <0, operand, 2, 1> with the fragment prologue
+    CONV_RING_PRO,     // ... fragment prologue, <0, operand, 1, 1>
+    CONV_PACKED,       // packed split kernel on the pre-split weight image, <mode, 4, 1, pro>
+    CONV_PACKED_KG2    // ... two K groups inside the workgroup, <mode, 4, 2, pro>
+};
+struct ConvRoute {
+    int family;        // ConvFamily
+    int tile, bk, nbuf;   // CONV_IGEMM: TileId (conv.hip), K-step, LDS stages
+    int mode;          // the kernels' MODE argument: 0 unpadded, 1 zero padding, 2 row-run (ring) / dilated input (register-staged)
+    int operand;       // the kernels' BF16 argument actually run (operand mode 4 runs 0 wherever the packed kernel does not take the launch)
+    int kg, pro;       // ring kernels: K groups inside the workgroup, fragment prologue
+    int reduce;        // 1: a split-K reduce launch follows
+    int prof_kind;     // PK_KERNEL_CONV_* (prof.h)
+};
+// operand_mode: conv_launch's bf16_operands; has_image: the launch comes with a pre-split weight image (mode 4 without one is mode 0).
+// bound = true, the launcher's view: the pointers of `a` are the launch's.  bound = false, the plan-time view: the prologue is
+// a.in_scale_expected and every condition on a pointer that is bound later (in_scale / in_shift, out_scale, partial; out_floor is
+// read as the plan holds it) counts as met -- `reduce` is then the launcher's for every launch a plan makes.  Reads nothing but its
+// arguments, the once-per-process STABNET_CONV_* switches and the tuning hooks (stabnet_conv_tuning_*).
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound);
+// Kernel name of a PK_KERNEL_CONV_* Profiler kind as rocprofv3 prints the instantiation; null for any other kind.
+const char* conv_prof_kind_name(int kind);
 // Pre-split weight image of a convolution whose weights are [Cout][K] rows (K % 32 == 0): per (64-channel N tile, 32-deep K step)
 // 3072 floats = [wave column 2][plane h, m, l][k group 2][lane 64][8 bf16]; lane (n = lane & 31, g = lane >> 5), element e holds
 // k = 32 step + 16 group + 8 (e >> 2) + 4 g + (e & 3) -- the k order of the ring kernel's A fragments.
-int conv_packed_variant();              // 4 or 5: the BF16 template value the packed launches run (conv.hip)
 size_t conv_weight_image_floats(int Cout, int K);
 int launch_weight_split_image(const float* w, int Cout, int K, float* img, hipStream_t st);
 // The images of several weight matrices by ONE launch (the training step re-splits its dgrad weights once per step): matrix i is
@@ -59,8 +86,9 @@ int launch_weight_split_image(const float* w, int Cout, int K, float* img, hipSt
 struct WeightImageTable { long w_off[64], img_off[64], tprefix[65]; int Cout[64], K[64]; int n; };
 void weight_image_table_add(WeightImageTable& t, long w_off, long img_off, int Cout, int K);
 int launch_weight_split_images(const float* w_base, float* img_base, const WeightImageTable& t, hipStream_t st);
-// 1 if that launch is followed by a split-K reduce launch (0: no split, or the split runs inside the workgroups)
-int conv_reduce_launches(const ConvArgs& a, int operand_mode = 0);      // (operand_mode 4: as conv_launch() with a weight image decides)
+// 1 if conv_launch() of this planned convolution is followed by a split-K reduce launch (0: no split, or the split runs inside the
+// workgroups): conv_route()'s plan-time view; operand_mode 4 = as conv_launch() with a weight image decides
+int conv_reduce_launches(const ConvArgs& a, int operand_mode = 0);
 
 // The two siamese towers of a training step as ONE launch (forward convolutions, conv_kernel.h).  `a` describes the pair as one
 // batch of 2N samples whose first N live where a.x / a.y / a.residual / a.in_scale / a.in_shift point; tiles of rows >= m_tower

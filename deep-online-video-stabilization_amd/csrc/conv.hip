@@ -16,8 +16,10 @@
 #include "conv.h"
 #include "prof.h"
 #include <climits>
+#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "conv_kernel.h"
@@ -90,14 +92,38 @@ static int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
-static int g_force_tile = -2, g_force_split = -1, g_force_bk16 = 0;
+// Every environment switch of this file, read once per process (on first use).
+struct ConvSwitches {
+    int tile = env_int("STABNET_CONV_TILE", -1), splitk = env_int("STABNET_CONV_SPLITK", -1);   // forced tile / split-K (< 0: the built-in choice)
+    int bk16 = env_int("STABNET_CONV_BK16", 0);
+    int nbuf = env_int("STABNET_CONV_NBUF", 0);                      // register-staged kernel's LDS stages: 0 the rule, 1 / 2 forced
+    int tuning_table = env_int("STABNET_CONV_TUNING_TABLE", 1);
+    int split_below = env_int("STABNET_CONV_SPLIT_BELOW", 400), split_target = env_int("STABNET_CONV_SPLIT_TARGET", 448);
+    int xcd = env_int("STABNET_CONV_XCD", 1);                        // halves the memory-side traffic at ~0.5 % of the frame rate
+    int ring = env_int("STABNET_CONV_RING", 1), ring_wgs_per_cu = env_int("STABNET_CONV_RING_WGS_PER_CU", 3);   // 48 KiB of LDS each
+    int lowk_igemm = env_int("STABNET_CONV_LOWK_IGEMM", 1);
+    int ring_pro = env_int("STABNET_CONV_RING_PRO", 1);
+    int kgroups = env_int("STABNET_CONV_KGROUPS", 1), kgroups_pro = env_int("STABNET_CONV_KGROUPS_PRO", 1);
+    int packed_kg2 = env_int("STABNET_CONV_PACKED_KG2", 1), packed_kg3 = env_int("STABNET_CONV_PACKED_KG3", 1);
+    int packed_pro = env_int("STABNET_CONV_PACKED_PRO", 1);
+    int packed_wgs_per_cu = env_int("STABNET_CONV_PACKED_WGS_PER_CU", 2);                        // 60 KiB of LDS each
+    int b2b = env_int("STABNET_CONV_B2B", 1), b2b_wgs_per_cu = env_int("STABNET_CONV_B2B_WGS_PER_CU", 2);   // 80 KB of LDS each
+};
+static const ConvSwitches& sw() {
+    static const ConvSwitches s;
+    return s;
+}
 
-static int conv_bk(const ConvArgs& a) { return (a.rowrun || (a.Cin % 32 == 0 && !g_force_bk16)) ? 32 : 16; }
+// tuning hook (stabnet_conv_tuning_override, tools/autotune.py); tile -2: never called, the environment's choice holds
+static int g_force_tile = -2, g_force_split = -1;
+static int force_tile() { return g_force_tile == -2 ? sw().tile : g_force_tile; }
+static int force_split() { return g_force_tile == -2 ? sw().splitk : g_force_split; }
+
+static int conv_bk(const ConvArgs& a) { return (a.rowrun || (a.Cin % 32 == 0 && !sw().bk16)) ? 32 : 16; }
 static int conv_total_steps(const ConvArgs& a) {
     if (a.rowrun) return a.KH * cdiv(a.KW * a.Cin, 32);
     return a.KH * a.KW * (a.Cin / conv_bk(a));
 }
-   // tuning hook (tools/autotune.py); -2 = read the environment once
 
 // ---- measured split-K table ------------------------------------------------------------------------------------
 struct TuneEntry { int M, Cout, K, KH, ring, splitk; };
@@ -105,32 +131,24 @@ struct TuneEntry { int M, Cout, K, KH, ring, splitk; };
 #include "conv_tuning_table_packed.h"   // static const TuneEntry g_tuning_packed[]: the same measurement with the packed split kernels (operand mode 4)
 static int g_tuning_profile = 0;        // 1: plans are made for the packed split kernels (stabnet_conv_tuning_profile)
 static std::vector<TuneEntry> g_tuning_runtime;      // set through stabnet_conv_tuning_table_set (the tuner itself)
-static int g_tuning_use_builtin = -1;
 
 static int tuning_lookup(int M, int Cout, int K, int KH, int ring) {
     for (const TuneEntry& e : g_tuning_runtime)
         if (e.M == M && e.Cout == Cout && e.K == K && e.KH == KH && e.ring == ring) return e.splitk;
-    if (g_tuning_use_builtin < 0) g_tuning_use_builtin = env_int("STABNET_CONV_TUNING_TABLE", 1);
-    if (g_tuning_use_builtin && g_tuning_profile == 1)
+    if (sw().tuning_table && g_tuning_profile == 1)
         for (const TuneEntry& e : g_tuning_packed)
             if (e.M == M && e.Cout == Cout && e.K == K && e.KH == KH && e.ring == ring) return e.splitk;
-    if (g_tuning_use_builtin)
+    if (sw().tuning_table)
         for (const TuneEntry& e : g_tuning_builtin)
             if (e.M == M && e.Cout == Cout && e.K == K && e.KH == KH && e.ring == ring) return e.splitk;
     return 0;
 }
 
 static int pick_tile(const ConvArgs& a, int& splitk) {
-    if (g_force_tile == -2) {
-        g_force_tile = env_int("STABNET_CONV_TILE", -1);
-        g_force_split = env_int("STABNET_CONV_SPLITK", -1);
-        g_force_bk16 = env_int("STABNET_CONV_BK16", 0);
-    }
-    const int force_tile = g_force_tile, force_split = g_force_split;
-    if (force_tile >= 0) {
+    if (force_tile() >= 0) {
         const int steps0 = conv_total_steps(a);
-        splitk = force_split > 0 ? std::min(force_split, steps0) : 1;
-        return force_tile;
+        splitk = force_split() > 0 ? std::min(force_split(), steps0) : 1;
+        return force_tile();
     }
     // Tile: at every shape of the regressor -- batch-1 720p, batch-8 288x512 forward and dgrad -- the 64x64 tile is the
     // fastest (tools/autotune.py, profiles/r01_autotune_*.txt).  Split-K: (1) the measured table (conv_tuning_table.h,
@@ -142,7 +160,7 @@ static int pick_tile(const ConvArgs& a, int& splitk) {
     const long blocks = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64);
     const bool ring_path = a.rowrun || (a.in_scale_expected == 0 && a.up == 1 && a.Cin % 32 == 0);
     int s = tuning_lookup(a.M, a.Cout, a.K, a.KH, ring_path ? 1 : 0);
-    static const int thr = env_int("STABNET_CONV_SPLIT_BELOW", 400), target = env_int("STABNET_CONV_SPLIT_TARGET", 448);
+    const int thr = sw().split_below, target = sw().split_target;
     if (s > 0) {
         s = std::min(s, std::max(1, total_steps / 2));
     } else if (blocks < thr && a.Cout % 4 == 0) {
@@ -157,8 +175,7 @@ static int pick_tile(const ConvArgs& a, int& splitk) {
 }
 
 size_t conv_plan(ConvArgs& a) {
-    static const int swz = env_int("STABNET_CONV_XCD", 1);   // halves the memory-side traffic at ~0.5 % of the frame rate
-    a.xcd_swizzle = swz;
+    a.xcd_swizzle = sw().xcd;
     a.M = a.N * a.Ho * a.Wo;
     a.K = a.rowrun ? a.KH * 32 * cdiv(a.KW * a.Cin, 32) : a.KH * a.KW * a.Cin;
     if (a.x_ld == 0) a.x_ld = a.Cin;
@@ -173,6 +190,181 @@ size_t conv_plan(ConvArgs& a) {
     return a.splitk > 1 ? (size_t)a.splitk * a.M * a.Cout * sizeof(float) : 0;
 }
 
+// ---- the route of a launch (conv.h) ------------------------------------------------------------------------------------
+// The register-staged kernel's (NBUF, BF16) in operand mode `operand`.
+// 1x1 launches over the large maps (block 1 at 720p: M = 57 600) are bandwidth / epilogue shaped: ONE LDS stage (18 KB, twice
+// the resident workgroups) beats the double-buffered loop there (30.4 -> 28.8 us, 33.7 -> 32.2 us); below that it loses 0.3 us.
+// The bf16-operand and split variants exist for the inference tile (64 x 64 x 32) only.
+static void igemm_variant(const ConvArgs& a, int bm, int bn, int bk, int mode, int operand, int& nbuf_out, int& bf16_out) {
+    const int nbuf = sw().nbuf;
+    bf16_out = (bm == 64 && bn == 64 && bk == 32) ? operand : 0;
+    const bool one_stage = nbuf == 1 || (nbuf == 0 && mode == 0 && bm == 64 && bn == 64 && a.M >= 32768);
+    nbuf_out = (bf16_out != 1 && one_stage) ? 1 : 2;
+}
+
+// LDS-DMA ring kernel (conv_ring_kernel.h): no A-operand prologue, stride-free addressing, Cin % 32 == 0, 64x64 tile.
+static bool ring_eligible(const ConvArgs& a, int tile, bool has_prologue) {
+    if (a.rowrun) return true;                              // the row-run A operand exists only in the ring kernel
+    // two-step tiles (1x1, K = 64) with a plain epilogue are 2 us faster per launch on the register-staged kernel (more resident
+    // workgroups to overlap the 16 KB epilogues: 33.4 vs 35.3 us at M = 57 600, N = 256); the merged shortcut|conv1 launch stays here
+    if (sw().lowk_igemm && a.KH == 1 && a.KW == 1 && a.Cin == 64 && a.x_ld == a.Cin && a.out_floor == nullptr) return false;
+    return sw().ring && tile == T64x64 && !has_prologue && a.up == 1 && a.Cin % 32 == 0 && !sw().bk16;
+}
+
+// The ring kernel's fragment prologue (conv_ring_kernel.h PRO): 1x1 / stride 1 convolutions whose input carries a BN + ReLU
+// prologue; not on bf16 operands (mode 1).
+// The PRO form fetches a step's scales AND shifts with one DMA instruction: the shifts are addressed as an unsigned 32-bit byte
+// offset from the (running) scale pointer.  Callers of the public operators pass two independent pointers: a shift vector below
+// the scales, or 4 GiB or more above them, must take the register-staged kernel (which dereferences both pointers).  Plan time
+// (pointers not bound yet): true -- the launch decides again with the real pointers.
+static bool ring_pro_vectors_ok(const ConvArgs& a) {
+    if (a.in_scale == nullptr || a.in_shift == nullptr) return true;
+    const long d = (long)(a.in_shift - a.in_scale);                   // floats
+    return d >= 0 && d < (1L << 30);
+}
+static bool ring_pro_geometry(const ConvArgs& a, int operand, bool has_prologue) {
+    return sw().ring_pro && sw().ring && operand != 1 && !sw().bk16 && has_prologue && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 &&
+           a.up == 1 && a.Cin % 32 == 0 && !a.rowrun && a.x_ld == a.Cin;
+}
+// One K group (<0, B, 1, 1>) with the launch's pointers: its epilogue has no consumer BN (the training forward), and the kernel takes
+// `out_floor` as the pair distance.  Measured: the 36 paired 1x1 launches of the 8 x 288 x 512 step 61.2 -> 55.9 us (76 -> 82.8 TF),
+// 494.7 -> 502.2 pairs/s.  The inference conv1 layers (prologue AND consumer BN) were tried on it too: 25.7 us against 23.5 / 28.7 us
+// on the register-staged kernel, the same 310 us per frame in sum -- they stay where they were.
+static bool ring_pro_eligible(const ConvArgs& a, int operand) {
+    return ring_pro_geometry(a, operand, a.in_scale != nullptr) && a.out_scale == nullptr && a.out_floor == nullptr && ring_pro_vectors_ok(a);
+}
+
+// Split-K inside the workgroup (conv_ring_kernel.h, "KG"): a launch strategy for a given split count.  Ring path: 3 groups x 48 KiB
+// of ring = one 12-wave workgroup per CU; the slices must be equal (steps % 3 == 0).  Measured at 720p (rocprofv3 inside the graph
+// replay, block-3 conv2, M = 3600, N = 256, K = 2304): 45.3 us against 45.8 us + a 4.9 us reduce launch.  The register-staged
+// kernel's two-group form lost (30.8 vs 24.3 + 4.9 us) and was removed.
+// Two groups with the fragment prologue (conv_ring_f32_kernel<0, 0, 2, 1>): the 1x1 layers that carry a BN + ReLU prologue AND
+// split K in two (the block-3 conv1 layers of a 720p frame, K = 1024: register-staged kernel x 2 slices + slabs + a reduce launch
+// before) as one 8-wave workgroup per tile.  No K groups on bf16 operands (mode 1).
+static int conv_kgroups(const ConvArgs& a, int operand, bool ring, bool has_prologue) {
+    if (!sw().kgroups || a.splitk < 2 || operand == 1) return 1;
+    if (a.steps_per_split * a.splitk != conv_total_steps(a)) return 1;
+    if (ring && a.splitk == 3 && !a.rowrun) return 3;
+    if (sw().kgroups_pro && !ring && a.splitk == 2 && ring_pro_geometry(a, operand, has_prologue) && ring_pro_vectors_ok(a)) return 2;
+    return 1;
+}
+
+// The Profiler kind of a route -- the ONE place that numbers the kernels (prof.h); conv_prof_kind_name() is its inverse by construction.
+static int route_prof_kind(const ConvRoute& r) {
+    switch (r.family) {
+        case CONV_IGEMM:      // + 18 for the one-stage (NBUF = 1), + 36 per BF16 (operand mode 1..3)
+            return PK_KERNEL_CONV_BASE + r.mode * 6 + r.tile * 2 + (r.bk == 32 ? 1 : 0) + (r.nbuf == 1 ? 18 : 0) + 36 * r.operand;
+        case CONV_PACKED: return PK_KERNEL_CONV_PACKED + (r.pro ? 3 : r.mode);
+        case CONV_PACKED_KG2: return PK_KERNEL_CONV_PACKED + (r.pro ? 6 : 4 + r.mode);
+        default: break;
+    }
+    // the read-time split modes (2 / 3) have kinds of their own (PK_KERNEL_CONV_SPLIT): their ring, K-group and PRO launches
+    const int split = r.operand >= 2 ? PK_KERNEL_CONV_SPLIT + 8 * (r.operand - 2) : 0;
+    if (r.family == CONV_RING) return split ? split + r.mode : PK_KERNEL_CONV_RING + r.mode + (r.operand ? 3 : 0);
+    if (r.family == CONV_RING_PRO) return split ? split + 5 : PK_KERNEL_CONV_KG + 2;
+    if (r.kg == 2) return split ? split + 6 : PK_KERNEL_CONV_KG + 3;
+    return split ? split + 3 + r.mode : PK_KERNEL_CONV_KG + r.mode;
+}
+
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound) {
+    const ConvSwitches& s = sw();
+    const bool image = operand_mode == 4 && has_image;
+    const int op = operand_mode == 4 ? 0 : operand_mode;     // every kernel but the packed one runs mode 4 as exact f32
+    int splitk_unused = 1;
+    const int t = pick_tile(a, splitk_unused);
+    const bool t64 = t == T64x64, bk32 = conv_bk(a) == 32;
+    const bool has_pro = bound ? a.in_scale != nullptr : a.in_scale_expected != 0;
+    const bool ring = ring_eligible(a, t, has_pro);
+    const bool slabs = !bound || a.splitk == 1 || a.partial != nullptr;
+    int kg = t64 ? conv_kgroups(a, op, ring, has_pro) : 1;
+    // the packed split kernel has no three-way in-workgroup split-K (60 KiB of ring per group): a ring launch that would split K three
+    // ways inside the workgroup goes through the slabs + reduce launch instead
+    if (image && s.packed_kg3 && ring && kg == 3 && a.K % 32 == 0 && slabs) kg = 1;
+    const bool pro = kg == 1 && !ring && t64 && bk32 && (bound ? ring_pro_eligible(a, op) : ring_pro_geometry(a, op, has_pro));
+    // packed split kernel with the fragment prologue: 1x1 / stride 1 layers that carry an input BN + ReLU (register-staged kernel or
+    // the two-group PRO ring form otherwise); a K split goes through the slabs + reduce launch, or runs as two K groups (below)
+    const bool packed_pro = image && s.packed_pro && !ring && t64 && bk32 && ring_pro_geometry(a, op, has_pro) &&
+                            (!bound || a.out_floor == nullptr) /* the kernel's pair distance */ && ring_pro_vectors_ok(a) && slabs;
+    if (packed_pro) kg = 1;
+    const bool packed = (image && ring && kg == 1 && a.K % 32 == 0) || packed_pro;
+    // a two-way K split with equal halves runs inside the packed workgroup (no slabs, no reduce launch)
+    const bool packed_kg2 = packed && s.packed_kg2 && a.splitk == 2 && !a.rowrun && a.steps_per_split * 2 == conv_total_steps(a);
+    if (packed_kg2) kg = 2;
+
+    ConvRoute r{};
+    r.tile = t;
+    r.bk = bk32 ? 32 : 16;
+    r.mode = (a.up > 1 || a.rowrun) ? 2 : (a.pad == 0 ? 0 : 1);
+    r.operand = op;
+    r.kg = kg;
+    r.reduce = (a.splitk > 1 && kg == 1) ? 1 : 0;
+    if (packed) {
+        r.family = packed_kg2 ? CONV_PACKED_KG2 : CONV_PACKED;
+        r.operand = 4;
+        r.pro = packed_pro ? 1 : 0;
+    } else if (pro) {
+        r.family = CONV_RING_PRO;
+        r.pro = 1;
+    } else if (kg > 1) {
+        r.family = CONV_RING_KG;
+        r.pro = kg == 2 ? 1 : 0;                             // (two groups exist with the prologue only, three without it only)
+    } else if (ring) {
+        r.family = CONV_RING;
+    } else {
+        int bm, bn;
+        tile_dims(t, bm, bn);
+        r.family = CONV_IGEMM;
+        igemm_variant(a, bm, bn, r.bk, r.mode, op, r.nbuf, r.operand);
+    }
+    r.prof_kind = route_prof_kind(r);
+    return r;
+}
+
+int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
+    return a.splitk < 2 ? 0 : conv_route(a, operand_mode, operand_mode == 4, false).reduce;
+}
+
+const char* conv_prof_kind_name(int kind) {
+    // every route the launchers take, named as rocprofv3 prints the template instantiation, at the kind route_prof_kind() gives it
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v(PK_KERNEL_CONV_BASE + 144);
+        char buf[96];
+        auto ring = [&](int family, int mode, int operand, int kg, int pro) {
+            ConvRoute r{};
+            r.family = family; r.mode = mode; r.operand = operand; r.kg = kg; r.pro = pro;
+            snprintf(buf, sizeof(buf), "conv_ring_f32_kernel<%d, %d, %d, %d>", mode, operand, kg, pro);
+            v[route_prof_kind(r)] = buf;
+        };
+        for (int operand = 0; operand < 4; ++operand) {
+            for (int mode = 0; mode < 3; ++mode) ring(CONV_RING, mode, operand, 1, 0);
+            if (operand == 1) continue;
+            ring(CONV_RING_KG, 0, operand, 3, 0); ring(CONV_RING_KG, 1, operand, 3, 0);
+            ring(CONV_RING_PRO, 0, operand, 1, 1); ring(CONV_RING_KG, 0, operand, 2, 1);
+        }
+        for (int mode = 0; mode < 3; ++mode) ring(CONV_PACKED, mode, 4, 1, 0);
+        ring(CONV_PACKED, 0, 4, 1, 1);
+        ring(CONV_PACKED_KG2, 0, 4, 2, 0); ring(CONV_PACKED_KG2, 1, 4, 2, 0); ring(CONV_PACKED_KG2, 0, 4, 2, 1);
+        for (int i = 0; i < 144; ++i) {                      // <BM, BN, BK, WM, WN, MODE, NBUF, BF16>
+            ConvRoute r{};
+            r.family = CONV_IGEMM;
+            r.operand = i / 36; r.nbuf = 2 - i / 18 % 2; r.mode = i / 6 % 3; r.tile = i / 2 % 3; r.bk = (i & 1) ? 32 : 16;
+            int bm, bn;
+            tile_dims(r.tile, bm, bn);
+            snprintf(buf, sizeof(buf), "conv_igemm_f32_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", bm, bn, r.bk, bm / 2, bn / 2, r.mode, r.nbuf, r.operand);
+            v[route_prof_kind(r)] = buf;
+        }
+        for (int i = 0; i < 4; ++i) {                        // conv_launch_pair: + 2 * MODE + (BK == 32)
+            snprintf(buf, sizeof(buf), "conv_igemm_f32_pair_kernel<64, 64, %d, 32, 32, %d>", (i & 1) ? 32 : 16, i / 2);
+            v[PK_KERNEL_CONV_PAIR + i] = buf;
+        }
+        v[PK_KERNEL_CONV_B2B] = "conv_b2b_f32_kernel<2>";
+        v[PK_KERNEL_CONV_B2B + 1] = "conv_b2b_f32_kernel<4>";
+        return v;
+    }();
+    return (kind >= 0 && kind < (int)names.size() && !names[kind].empty()) ? names[kind].c_str() : nullptr;
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------
 template <int BM, int BN, int BK, int WM, int WN, int MODE, int NBUF, int BF16 = 0>
 static int launch_one_nb(const ConvArgs& a, hipStream_t st) {
     constexpr size_t lds_op = NBUF * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
@@ -197,275 +389,95 @@ static int launch_one_nb(const ConvArgs& a, hipStream_t st) {
     return STABNET_OK;
 }
 
-static thread_local int g_bf16_operands = 0;      // set by conv_launch for the duration of one launch (see conv.h)
-
-// Which instantiation a register-staged launch runs: (NBUF, BF16) -- one rule for the launcher and for the profiler's kernel name.
-// 1x1 launches over the large maps (block 1 at 720p: M = 57 600) are bandwidth / epilogue shaped: ONE LDS stage (18 KB, twice
-// the resident workgroups) beats the double-buffered loop there (30.4 -> 28.8 us, 33.7 -> 32.2 us); below that it loses 0.3 us.
-// The bf16-operand variant exists for the inference tile (64 x 64 x 32) only.
-static void igemm_variant(const ConvArgs& a, int bm, int bn, int bk, int mode, int& nbuf_out, int& bf16_out) {
-    static const int nbuf = env_int("STABNET_CONV_NBUF", 0);          // 0: the rule; 1 / 2: forced
-    bf16_out = (g_bf16_operands && bm == 64 && bn == 64 && bk == 32) ? g_bf16_operands : 0;
-    const bool one_stage = nbuf == 1 || (nbuf == 0 && mode == 0 && bm == 64 && bn == 64 && a.M >= 32768);
-    nbuf_out = (bf16_out != 1 && one_stage) ? 1 : 2;
-}
-
 template <int BM, int BN, int BK, int WM, int WN, int MODE>
-static int launch_one_t(const ConvArgs& a, hipStream_t st) {
-    int nbuf, bf16;
-    igemm_variant(a, BM, BN, BK, MODE, nbuf, bf16);
+static int launch_one_t(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
     if constexpr (BM == 64 && BN == 64 && BK == 32) {
-        if (bf16 == 1) return launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 1>(a, st);
-        else if (bf16 == 2) return nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1, 2>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 2>(a, st);
-        else if (bf16 == 3) return nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1, 3>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 3>(a, st);
+        if (r.operand == 1) return launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 1>(a, st);
+        else if (r.operand == 2) return r.nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1, 2>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 2>(a, st);
+        else if (r.operand == 3) return r.nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1, 3>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2, 3>(a, st);
     }
-    return nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2>(a, st);
+    return r.nbuf == 1 ? launch_one_nb<BM, BN, BK, WM, WN, MODE, 1>(a, st) : launch_one_nb<BM, BN, BK, WM, WN, MODE, 2>(a, st);
 }
 
 template <int BM, int BN, int BK, int WM, int WN>
-static int launch_one(const ConvArgs& a, hipStream_t st) {
-    if (a.up > 1) return launch_one_t<BM, BN, BK, WM, WN, 2>(a, st);
-    if (a.pad == 0) return launch_one_t<BM, BN, BK, WM, WN, 0>(a, st);
-    return launch_one_t<BM, BN, BK, WM, WN, 1>(a, st);
+static int launch_one(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
+    if (r.mode == 2) return launch_one_t<BM, BN, BK, WM, WN, 2>(r, a, st);
+    if (r.mode == 0) return launch_one_t<BM, BN, BK, WM, WN, 0>(r, a, st);
+    return launch_one_t<BM, BN, BK, WM, WN, 1>(r, a, st);
 }
 
-// LDS-DMA ring kernel (conv_ring_kernel.h): no A-operand prologue, stride-free addressing, Cin % 32 == 0, 64x64 tile.
-static int g_ring = -1;
-
-static bool ring_eligible(const ConvArgs& a, int tile, bool has_prologue) {
-    if (g_ring < 0) {
-        g_ring = env_int("STABNET_CONV_RING", 1);
+static int launch_igemm(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
+    if (r.bk == 32) {
+        if (r.tile == T128x128) return launch_one<128, 128, 32, 64, 64>(r, a, st);
+        if (r.tile == T128x64) return launch_one<128, 64, 32, 64, 32>(r, a, st);
+        return launch_one<64, 64, 32, 32, 32>(r, a, st);
     }
-    if (a.rowrun) return true;                              // the row-run A operand exists only in the ring kernel
-    // two-step tiles (1x1, K = 64) with a plain epilogue are 2 us faster per launch on the register-staged kernel (more resident
-    // workgroups to overlap the 16 KB epilogues: 33.4 vs 35.3 us at M = 57 600, N = 256); the merged shortcut|conv1 launch stays here
-    static const int lowk = env_int("STABNET_CONV_LOWK_IGEMM", 1);
-    if (lowk && a.KH == 1 && a.KW == 1 && a.Cin == 64 && a.x_ld == a.Cin && a.out_floor == nullptr) return false;
-    return g_ring && tile == T64x64 && !has_prologue && a.up == 1 && a.Cin % 32 == 0 && !g_force_bk16;
+    if (r.tile == T128x128) return launch_one<128, 128, 16, 64, 64>(r, a, st);
+    if (r.tile == T128x64) return launch_one<128, 64, 16, 64, 32>(r, a, st);
+    return launch_one<64, 64, 16, 32, 32>(r, a, st);
 }
-static bool ring_eligible(const ConvArgs& a, int tile) { return ring_eligible(a, tile, a.in_scale != nullptr); }
 
-static int g_ring_wgs = 0;        // resident workgroups of the ring kernel on this device (3 per CU: 48 KiB LDS each)
-static int g_ring_cus = 0;        // (the CU count g_ring_wgs was computed from)
+// CUs of the current device (read once per process)
+static int device_cus(int& cus) {
+    static int cached = 0;
+    if (cached == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+            stabnet_set_error("conv: cannot read the CU count");
+            return STABNET_ERR_LAUNCH;
+        }
+        cached = n;
+    }
+    cus = cached;
+    return STABNET_OK;
+}
 static int g_reserved_cus = 0;    // CUs the persistent grids leave to a communication stream (stabnet_conv_reserve_cus)
 // persistent grids are sized for the CUs that are NOT reserved (never fewer than an eighth of the chip)
 static int usable_cus(int cus) { return std::max(cus / 8, cus - std::max(0, g_reserved_cus)); }
-static int ring_grid_cap() { return g_ring_cus > 0 ? g_ring_wgs / g_ring_cus * usable_cus(g_ring_cus) : g_ring_wgs; }
 
-template <int MODE>
-static int launch_ring_mode(const ConvArgs& a, hipStream_t st) {
-    if (g_ring_wgs == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus <= 0) {
-            stabnet_set_error("conv: cannot read the CU count");
-            return STABNET_ERR_LAUNCH;
-        }
-        g_ring_wgs = env_int("STABNET_CONV_RING_WGS_PER_CU", 3) * cus;
-        g_ring_cus = cus;
+// The ONE mapping from a route's (MODE, operand, KG, PRO) to the instantiation of conv_ring_f32_kernel (256 threads per K group);
+// false: the library has no such kernel.
+template <int B>
+static bool launch_ring_operand(const ConvRoute& r, const ConvArgs& a, int grid, hipStream_t st) {
+    const int key = 100 * r.mode + 10 * r.kg + r.pro;
+    if (key == 10) { conv_ring_f32_kernel<0, B><<<grid, 256, 0, st>>>(a); return true; }
+    if (key == 110) { conv_ring_f32_kernel<1, B><<<grid, 256, 0, st>>>(a); return true; }
+    if (key == 210) { conv_ring_f32_kernel<2, B><<<grid, 256, 0, st>>>(a); return true; }
+    if constexpr (B != 1) {                                  // the fragment prologue: one / two K groups
+        if (key == 11) { conv_ring_f32_kernel<0, B, 1, 1><<<grid, 256, 0, st>>>(a); return true; }
+        if (key == 21) { conv_ring_f32_kernel<0, B, 2, 1><<<grid, 512, 0, st>>>(a); return true; }
     }
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * a.splitk;
-    const int grid = (int)std::min<long>(ntiles, ring_grid_cap());
-    if (g_bf16_operands == 1) conv_ring_f32_kernel<MODE, 1><<<grid, 256, 0, st>>>(a);
-    else if (g_bf16_operands == 2) conv_ring_f32_kernel<MODE, 2><<<grid, 256, 0, st>>>(a);
-    else if (g_bf16_operands == 3) conv_ring_f32_kernel<MODE, 3><<<grid, 256, 0, st>>>(a);
-    else conv_ring_f32_kernel<MODE, 0><<<grid, 256, 0, st>>>(a);
+    if constexpr (B == 0 || B == 2 || B == 3) {              // three K groups
+        if (key == 30) { conv_ring_f32_kernel<0, B, 3><<<grid, 768, 0, st>>>(a); return true; }
+        if (key == 130) { conv_ring_f32_kernel<1, B, 3><<<grid, 768, 0, st>>>(a); return true; }
+    }
+    if constexpr (B == 4) {                                  // the packed split kernel's two K groups
+        if (key == 20) { conv_ring_f32_kernel<0, B, 2, 0><<<grid, 512, 0, st>>>(a); return true; }
+        if (key == 120) { conv_ring_f32_kernel<1, B, 2, 0><<<grid, 512, 0, st>>>(a); return true; }
+    }
+    return false;
+}
+
+// Every ring launch.  The grid is persistent: at most the resident workgroups -- 3 per CU (48 KiB of LDS each), 2 of the packed
+// split kernel (60 KiB), one when K splits inside the workgroup (KG x that; the K slices are then no tiles of their own).
+static int launch_ring_route(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
+    int cus = 0;
+    if (const int rc = device_cus(cus)) return rc;
+    const int per_cu = r.kg > 1 ? 1 : (r.operand == 4 ? sw().packed_wgs_per_cu : sw().ring_wgs_per_cu);
+    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * (r.kg > 1 ? 1 : a.splitk);
+    const int grid = (int)std::min<long>(ntiles, (long)per_cu * usable_cus(cus));
+    bool ok = false;
+    switch (r.operand) {
+        case 0: ok = launch_ring_operand<0>(r, a, grid, st); break;
+        case 1: ok = launch_ring_operand<1>(r, a, grid, st); break;
+        case 2: ok = launch_ring_operand<2>(r, a, grid, st); break;
+        case 3: ok = launch_ring_operand<3>(r, a, grid, st); break;
+        case 4: ok = launch_ring_operand<4>(r, a, grid, st); break;
+        default: break;
+    }
+    SN_REQUIRE(ok, "conv: no conv_ring_f32_kernel<%d, %d, %d, %d>", r.mode, r.operand, r.kg, r.pro);
     SN_LAUNCH_CHECK("conv_ring_f32_kernel");
     return STABNET_OK;
-}
-
-static int g_cus = 0;
-static int device_cus() {
-    if (g_cus == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return 0;
-        g_cus = cus;
-    }
-    return g_cus;
-}
-
-// 4 (default): every wave splits both k groups of its A rows itself.  5 (STABNET_CONV_PACKED_SHARE=1): the two waves over the same A
-// rows split one k group each and exchange the planes through LDS -- half the split VALU, a second barrier per step and an LDS
-// round trip: measured SLOWER (stand-alone 35.0 / 38.4 / 131.7 us against 31.0 / 32.5 / 119.7 us, 627 vs 636 frames/s at 720p; even
-// with the barriers compiled out 33.5 / 35.8 / 122.9 us): the split VALU is not what bounds the packed kernel.  Kept as a switch.
-int conv_packed_variant() {
-    static const int share = env_int("STABNET_CONV_PACKED_SHARE", 0);
-    return share ? 5 : 4;
-}
-
-// The packed split kernel (conv_ring_kernel.h, BF16 = 4 / 5): 60 / 72 KiB of LDS per workgroup -> two per CU.
-template <int MODE>
-static int launch_ring_packed_mode(const ConvArgs& a, hipStream_t st) {
-    const int cus = device_cus();
-    if (cus <= 0) {
-        stabnet_set_error("conv: cannot read the CU count");
-        return STABNET_ERR_LAUNCH;
-    }
-    static const int per_cu = env_int("STABNET_CONV_PACKED_WGS_PER_CU", 2);
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * a.splitk;
-    const int grid = (int)std::min<long>(ntiles, (long)per_cu * usable_cus(cus));
-    if constexpr (MODE == 0) {
-        if (a.in_scale != nullptr) {                          // BN + ReLU prologue on the A fragments (the inference conv1 layers)
-            if (conv_packed_variant() == 5) conv_ring_f32_kernel<0, 5, 1, 1><<<grid, 256, 0, st>>>(a);
-            else conv_ring_f32_kernel<0, 4, 1, 1><<<grid, 256, 0, st>>>(a);
-            SN_LAUNCH_CHECK("conv_ring_f32_kernel<packed, PRO>");
-            return STABNET_OK;
-        }
-    }
-    if (conv_packed_variant() == 5) conv_ring_f32_kernel<MODE, 5><<<grid, 256, 0, st>>>(a);
-    else conv_ring_f32_kernel<MODE, 4><<<grid, 256, 0, st>>>(a);
-    SN_LAUNCH_CHECK("conv_ring_f32_kernel<packed>");
-    return STABNET_OK;
-}
-// Two K groups inside the workgroup (p.splitk == 2, equal slices): 8 waves, 2 x 60 KiB of ring, one workgroup per CU, no reduce launch.
-static int launch_ring_packed_kg2(const ConvArgs& a, hipStream_t st) {
-    const int cus = device_cus();
-    if (cus <= 0) {
-        stabnet_set_error("conv: cannot read the CU count");
-        return STABNET_ERR_LAUNCH;
-    }
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64);
-    const int grid = (int)std::min<long>(ntiles, usable_cus(cus));
-    if (conv_packed_variant() == 5) {
-        if (a.in_scale != nullptr) conv_ring_f32_kernel<0, 5, 2, 1><<<grid, 512, 0, st>>>(a);
-        else if (a.pad == 0) conv_ring_f32_kernel<0, 5, 2, 0><<<grid, 512, 0, st>>>(a);
-        else conv_ring_f32_kernel<1, 5, 2, 0><<<grid, 512, 0, st>>>(a);
-    } else {
-        if (a.in_scale != nullptr) conv_ring_f32_kernel<0, 4, 2, 1><<<grid, 512, 0, st>>>(a);
-        else if (a.pad == 0) conv_ring_f32_kernel<0, 4, 2, 0><<<grid, 512, 0, st>>>(a);
-        else conv_ring_f32_kernel<1, 4, 2, 0><<<grid, 512, 0, st>>>(a);
-    }
-    SN_LAUNCH_CHECK("conv_ring_f32_kernel<packed, KG 2>");
-    return STABNET_OK;
-}
-static int launch_ring_packed(const ConvArgs& a, hipStream_t st) {
-    if (a.rowrun) return launch_ring_packed_mode<2>(a, st);
-    return a.pad == 0 ? launch_ring_packed_mode<0>(a, st) : launch_ring_packed_mode<1>(a, st);
-}
-
-static int launch_ring(const ConvArgs& a, hipStream_t st) {
-    if (a.rowrun) return launch_ring_mode<2>(a, st);
-    return a.pad == 0 ? launch_ring_mode<0>(a, st) : launch_ring_mode<1>(a, st);
-}
-
-// Split-K inside the workgroup (conv_ring_kernel.h, "KG"): a launch strategy for a given split count, chosen here for the
-// planner (no reduce launch counted) and for the launcher alike.  Ring path only: 3 groups x 48 KiB of ring = one 12-wave workgroup
-// per CU; the slices must be equal (steps % 3 == 0).  Measured at 720p (rocprofv3 inside the graph replay, block-3 conv2, M = 3600,
-// N = 256, K = 2304): 45.3 us against 45.8 us + a 4.9 us reduce launch.  The register-staged kernel's two-group form lost
-// (30.8 vs 24.3 + 4.9 us) and was removed.
-// Two groups with the fragment prologue (conv_ring_f32_kernel<0, 0, 2, 1>): the 1x1 layers that carry a BN + ReLU prologue AND
-// split K in two (the block-3 conv1 layers of a 720p frame, K = 1024: register-staged kernel x 2 slices + slabs + a reduce launch
-// before) as one 8-wave workgroup per tile.
-// The PRO form fetches a step's scales AND shifts with one DMA instruction: the shifts are addressed as an unsigned 32-bit byte
-// offset from the (running) scale pointer.  Callers of the public operators pass two independent pointers: a shift vector below
-// the scales, or 4 GiB or more above them, must take the register-staged kernel (which dereferences both pointers).  Plan time
-// (pointers not bound yet): true -- the launch decides again with the real pointers.
-static bool ring_pro_vectors_ok(const ConvArgs& a) {
-    if (a.in_scale == nullptr || a.in_shift == nullptr) return true;
-    const long d = (long)(a.in_shift - a.in_scale);                   // floats
-    return d >= 0 && d < (1L << 30);
-}
-static bool ring_pro_geometry(const ConvArgs& a, bool has_prologue) {
-    static const int on = env_int("STABNET_CONV_RING_PRO", 1);
-    if (g_ring < 0) g_ring = env_int("STABNET_CONV_RING", 1);
-    return on && g_ring && g_bf16_operands != 1 && !g_force_bk16 && has_prologue && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 &&
-           a.up == 1 && a.Cin % 32 == 0 && !a.rowrun && a.x_ld == a.Cin;
-}
-static int conv_kgroups(const ConvArgs& a, bool ring, bool has_prologue) {
-    static const int on = env_int("STABNET_CONV_KGROUPS", 1);
-    static const int on2 = env_int("STABNET_CONV_KGROUPS_PRO", 1);
-    if (!on || a.splitk < 2 || g_bf16_operands == 1) return 1;
-    const int steps = conv_total_steps(a);
-    if (a.steps_per_split * a.splitk != steps) return 1;
-    if (ring && a.splitk == 3 && !a.rowrun) return 3;
-    if (on2 && !ring && a.splitk == 2 && ring_pro_geometry(a, has_prologue) && ring_pro_vectors_ok(a)) return 2;
-    return 1;
-}
-
-
-static int launch_ring_kg(const ConvArgs& a, int kg, hipStream_t st) {
-    const int cus = device_cus();
-    if (cus <= 0) {
-        stabnet_set_error("conv: cannot read the CU count");
-        return STABNET_ERR_LAUNCH;
-    }
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64);
-    const int grid = (int)std::min<long>(ntiles, usable_cus(cus));     // 144 (102) KiB of LDS: one workgroup per CU
-#define SN_KG_LAUNCH(B)                                                                  \
-    do {                                                                                  \
-        if (kg == 2) conv_ring_f32_kernel<0, B, 2, 1><<<grid, 512, 0, st>>>(a);           \
-        else if (a.pad == 0) conv_ring_f32_kernel<0, B, 3><<<grid, 768, 0, st>>>(a);      \
-        else conv_ring_f32_kernel<1, B, 3><<<grid, 768, 0, st>>>(a);                      \
-    } while (0)
-    if (g_bf16_operands == 2) SN_KG_LAUNCH(2);
-    else if (g_bf16_operands == 3) SN_KG_LAUNCH(3);
-    else SN_KG_LAUNCH(0);
-#undef SN_KG_LAUNCH
-    SN_LAUNCH_CHECK("conv_ring_f32_kernel<KG>");
-    return STABNET_OK;
-}
-
-// The ring kernel's PRO form (conv_ring_kernel.h): 1x1 / stride 1 convolutions whose input carries a BN + ReLU prologue and whose
-// epilogue has no consumer BN (the training forward).  `delta` != 0: the pair of towers as one launch (ConvPair::dscale).
-// Measured: the 36 paired 1x1 launches of the 8 x 288 x 512 step 61.2 -> 55.9 us (76 -> 82.8 TF), 494.7 -> 502.2 pairs/s.  The
-// inference conv1 layers (prologue AND consumer BN) were tried on it too: 25.7 us against 23.5 / 28.7 us on the register-staged
-// kernel, the same 310 us per frame in sum -- they stay where they were.
-static bool ring_pro_eligible(const ConvArgs& a) {
-    static const int on = env_int("STABNET_CONV_RING_PRO", 1);
-    if (g_ring < 0) g_ring = env_int("STABNET_CONV_RING", 1);
-    return on && g_ring && g_bf16_operands != 1 && !g_force_bk16 && a.in_scale != nullptr && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 &&
-           a.up == 1 && a.Cin % 32 == 0 && a.out_scale == nullptr && a.out_floor == nullptr && !a.rowrun && a.x_ld == a.Cin &&
-           ring_pro_vectors_ok(a);
-}
-static int launch_ring_pro(ConvArgs a, long delta, hipStream_t st) {
-    if (g_ring_wgs == 0) {
-        const int cus = device_cus();
-        if (cus <= 0) {
-            stabnet_set_error("conv: cannot read the CU count");
-            return STABNET_ERR_LAUNCH;
-        }
-        g_ring_wgs = env_int("STABNET_CONV_RING_WGS_PER_CU", 3) * cus;
-        g_ring_cus = cus;
-    }
-    a.out_floor = reinterpret_cast<const float*>((size_t)delta);      // the kernel's pair distance (not a pointer: see conv_ring_kernel.h PRO)
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * a.splitk;
-    const int grid = (int)std::min<long>(ntiles, ring_grid_cap());
-    if (g_bf16_operands == 2) conv_ring_f32_kernel<0, 2, 1, 1><<<grid, 256, 0, st>>>(a);
-    else if (g_bf16_operands == 3) conv_ring_f32_kernel<0, 3, 1, 1><<<grid, 256, 0, st>>>(a);
-    else conv_ring_f32_kernel<0, 0, 1, 1><<<grid, 256, 0, st>>>(a);
-    SN_LAUNCH_CHECK("conv_ring_f32_kernel<PRO>");
-    return STABNET_OK;
-}
-
-// 1 if conv_launch() of this (planned) convolution is followed by a split-K reduce launch (plan-time view: the prologue is known
-// from in_scale_expected)
-static int conv_reduce_launches_in_mode(const ConvArgs& a, int operand_mode);
-int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
-    // conv_kgroups / ring_pro_geometry read the launch's operand mode (set by conv_launch, mode 4 -> 0 wherever the packed kernel does
-    // not take the launch): evaluate the model in the mode it is asked about, not in whatever mode the thread's last launch left
-    const int saved = g_bf16_operands;
-    g_bf16_operands = operand_mode == 4 ? 0 : operand_mode;
-    const int n = conv_reduce_launches_in_mode(a, operand_mode);
-    g_bf16_operands = saved;
-    return n;
-}
-static int conv_reduce_launches_in_mode(const ConvArgs& a, int operand_mode) {
-    if (a.splitk < 2) return 0;
-    int splitk_unused = 1;
-    const int t = pick_tile(a, splitk_unused);
-    const bool pro = a.in_scale_expected != 0;
-    const bool ring = ring_eligible(a, t, pro);
-    if (operand_mode == 4 && t == T64x64 && a.K % 32 == 0 && conv_bk(a) == 32) {
-        // conv_launch() with a weight image: the packed split kernel takes ring launches and the prologue-carrying 1x1 layers; only a
-        // two-way split with equal halves runs inside the workgroup
-        static const int kg2_on = env_int("STABNET_CONV_PACKED_KG2", 1), pro_on = env_int("STABNET_CONV_PACKED_PRO", 1),
-                         kg3_on = env_int("STABNET_CONV_PACKED_KG3", 1);
-        const int kgf = conv_kgroups(a, ring, pro);
-        const bool takes = (ring && (kgf == 1 || (kgf == 3 && kg3_on))) || (!ring && pro && pro_on && ring_pro_geometry(a, true));
-        if (takes) return (kg2_on && a.splitk == 2 && !a.rowrun && a.steps_per_split * 2 == conv_total_steps(a)) ? 0 : 1;
-    }
-    return (t == T64x64 && conv_kgroups(a, ring, pro) > 1) ? 0 : 1;
 }
 
 // ---- pre-split weight image (conv.h) -----------------------------------------------------------------------------------
@@ -552,85 +564,35 @@ int launch_weight_split_image(const float* w, int Cout, int K, float* img, hipSt
     return STABNET_OK;
 }
 
-int conv_launch(const ConvArgs& a_in, hipStream_t st, Prof* prof, int bf16_operands, const float* w_img) {
-    const bool want_packed = bf16_operands == 4 && w_img != nullptr;
-    if (bf16_operands == 4) bf16_operands = 0;               // every path but the packed ring kernel is the exact f32 one
-    g_bf16_operands = bf16_operands;
-    const ConvArgs& a = a_in;
+int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands, const float* w_img) {
     SN_REQUIRE(a.rowrun || a.Cin % 16 == 0, "conv: Cin=%d must be a multiple of 16 (pad the channels)", a.Cin);
     SN_REQUIRE(!a.rowrun || (a.in_scale == nullptr && a.up == 1 && a.KH <= 8 && cdiv(a.KW * a.Cin, 32) <= 4),
                "conv: row-run operand needs no prologue, KH <= 8 and KW*Cin <= 128");
     SN_REQUIRE(a.Cout % 4 == 0, "conv: Cout=%d must be a multiple of 4", a.Cout);
     SN_REQUIRE(a.splitk >= 1 && a.steps_per_split >= 1 && a.div_hw_mul != 0, "conv: conv_plan() not called");
     SN_REQUIRE(a.splitk == 1 || a.partial != nullptr, "conv: split-K needs a workspace");
-    int splitk_unused = 1;
-    const int t = pick_tile(a, splitk_unused);
-    const bool bk32 = conv_bk(a) == 32;
-    int rc;
+    const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, true);
+    SN_REQUIRE(r.family != CONV_IGEMM || a.x_ld == a.Cin, "conv: a strided input (x_ld %d != Cin %d) needs the ring kernel", a.x_ld, a.Cin);
     const bool rec = prof != nullptr && prof->begin(st);
-    const bool ring = ring_eligible(a, t);
-    SN_REQUIRE(ring || a.x_ld == a.Cin, "conv: a strided input (x_ld %d != Cin %d) needs the ring kernel", a.x_ld, a.Cin);
-    int kg = (t == T64x64) ? conv_kgroups(a, ring, a.in_scale != nullptr) : 1;
-    // the packed split kernel has no in-workgroup split-K (60 KiB of ring per group): a ring launch that would split K three ways
-    // inside the workgroup goes through the slabs + reduce launch instead
-    static const int packed_kg3 = env_int("STABNET_CONV_PACKED_KG3", 1);
-    if (want_packed && packed_kg3 && ring && kg == 3 && a.K % 32 == 0 && a.partial != nullptr) kg = 1;
-    const bool pro = kg == 1 && !ring && t == T64x64 && bk32 && ring_pro_eligible(a);
-    // packed split kernel with the fragment prologue: 1x1 / stride 1 layers that carry an input BN + ReLU (register-staged kernel or
-    // the two-group PRO ring form otherwise); a K split goes through the slabs + reduce launch
-    static const int packed_pro_on = env_int("STABNET_CONV_PACKED_PRO", 1);
-    const bool packed_pro = want_packed && packed_pro_on && !ring && t == T64x64 && bk32 && a.in_scale != nullptr && a.out_floor == nullptr &&
-                            ring_pro_geometry(a, true) && ring_pro_vectors_ok(a) && (a.splitk == 1 || a.partial != nullptr);   // (out_floor: the kernel's pair distance)
-    if (packed_pro) kg = 1;
-    const bool packed = (want_packed && ring && kg == 1 && !pro && a.K % 32 == 0) || packed_pro;
-    // a two-way K split runs inside the workgroup (no slabs, no reduce launch)
-    static const int packed_kg2_on = env_int("STABNET_CONV_PACKED_KG2", 1);
-    const bool packed_kg2 = packed && packed_kg2_on && a.splitk == 2 && !a.rowrun && a.steps_per_split * 2 == conv_total_steps(a);
-    if (packed_kg2) kg = 2;
-    if (packed) {
-        ConvArgs b = a;
-        b.w = w_img;
-        rc = packed_kg2 ? launch_ring_packed_kg2(b, st) : launch_ring_packed(b, st);
-    } else if (pro) {
-        rc = launch_ring_pro(a, 0, st);
-    } else if (kg > 1) {
-        rc = launch_ring_kg(a, kg, st);
-    } else if (ring) {
-        rc = launch_ring(a, st);
-    } else if (bk32) {
-        if (t == T128x128) rc = launch_one<128, 128, 32, 64, 64>(a, st);
-        else if (t == T128x64) rc = launch_one<128, 64, 32, 64, 32>(a, st);
-        else rc = launch_one<64, 64, 32, 32, 32>(a, st);
-    } else {
-        if (t == T128x128) rc = launch_one<128, 128, 16, 64, 64>(a, st);
-        else if (t == T128x64) rc = launch_one<128, 64, 16, 64, 32>(a, st);
-        else rc = launch_one<64, 64, 16, 32, 32>(a, st);
+    int rc;
+    switch (r.family) {
+        case CONV_IGEMM: rc = launch_igemm(r, a, st); break;
+        case CONV_PACKED:
+        case CONV_PACKED_KG2: {
+            ConvArgs b = a;
+            b.w = w_img;
+            rc = launch_ring_route(r, b, st);
+            break;
+        }
+        default: rc = launch_ring_route(r, a, st); break;
     }
-    const int mode = (a.up > 1 || a.rowrun) ? 2 : (a.pad == 0 ? 0 : 1);
-    const bool b_has_pro = a.in_scale != nullptr;           // (the packed launchers pick the prologue form from the pointer)
-    // the read-time split modes (2 / 3) have kinds of their own (prof.h PK_KERNEL_CONV_SPLIT): their ring, K-group and PRO launches
-    const int split = (bf16_operands == 2 || bf16_operands == 3) ? PK_KERNEL_CONV_SPLIT + 8 * (bf16_operands - 2) : 0;
-    int kind = split ? split + mode : PK_KERNEL_CONV_RING + mode + (bf16_operands ? 3 : 0);
-    if (packed) {
-        kind = packed_kg2 ? (b_has_pro ? PK_KERNEL_CONV_PACKED + 6 : PK_KERNEL_CONV_PACKED + 4 + mode)
-                          : (b_has_pro ? PK_KERNEL_CONV_PACKED + 3 : PK_KERNEL_CONV_PACKED + mode);
-    } else if (pro) {
-        kind = split ? split + 5 : PK_KERNEL_CONV_KG + 2;
-    } else if (kg > 1) {
-        kind = split ? split + (kg == 2 ? 6 : 3 + mode) : (kg == 2 ? PK_KERNEL_CONV_KG + 3 : PK_KERNEL_CONV_KG + mode);
-    } else if (!ring) {                                                  // + 18 for the one-stage (NBUF = 1), + 36 per BF16 (operand mode 1..3)
-        int bm, bn, nbuf, bf16;
-        tile_dims(t, bm, bn);
-        igemm_variant(a, bm, bn, bk32 ? 32 : 16, mode, nbuf, bf16);
-        kind = PK_KERNEL_CONV_BASE + mode * 6 + t * 2 + (bk32 ? 1 : 0) + (nbuf == 1 ? 18 : 0) + 36 * bf16;
-    }
-    if (rec) prof->end(st, kind, 2.0 * a.M * (double)(a.KH * a.KW * (a.cin_real ? a.cin_real : a.Cin)) * a.Cout,
+    if (rec) prof->end(st, r.prof_kind, 2.0 * a.M * (double)(a.KH * a.KW * (a.cin_real ? a.cin_real : a.Cin)) * a.Cout,
                        // algorithmic bytes: input + weights + output (or the split-K slabs) + the residual read
-                       4.0 * ((double)a.N * a.H * a.W * a.Cin + (double)a.K * a.Cout + (double)a.M * a.Cout * (kg > 1 ? 1 : a.splitk) +
-                              ((a.residual != nullptr && (a.splitk == 1 || kg > 1)) ? (double)a.M * a.Cout : 0.0)),
+                       4.0 * ((double)a.N * a.H * a.W * a.Cin + (double)a.K * a.Cout + (double)a.M * a.Cout * (r.reduce ? a.splitk : 1) +
+                              ((a.residual != nullptr && !r.reduce) ? (double)a.M * a.Cout : 0.0)),
                        a.M, a.Cout, a.K, a.splitk);
     if (rc) return rc;
-    if (a.splitk > 1 && kg == 1) {
+    if (r.reduce) {
         const size_t q = (size_t)a.M * (a.Cout / 4);
         const bool rec2 = prof != nullptr && prof->begin(st);
         conv_splitk_reduce_kernel<<<cdiv((long)q, 256), 256, 0, st>>>(a);
@@ -658,26 +620,7 @@ static int launch_pair_one(const ConvArgs& a, const ConvPair& pr, hipStream_t st
     return STABNET_OK;
 }
 
-// The packed split kernel's prologue form over the PAIR of towers (training forward, opt-in): launch_ring_pro with a weight image.
-static int launch_ring_packed_pro_pair(ConvArgs a, long delta, const float* w_img, hipStream_t st) {
-    const int cus = device_cus();
-    if (cus <= 0) {
-        stabnet_set_error("conv: cannot read the CU count");
-        return STABNET_ERR_LAUNCH;
-    }
-    a.w = w_img;
-    a.out_floor = reinterpret_cast<const float*>((size_t)delta);      // the kernel's pair distance (conv_ring_kernel.h PRO)
-    static const int per_cu = env_int("STABNET_CONV_PACKED_WGS_PER_CU", 2);
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * a.splitk;
-    const int grid = (int)std::min<long>(ntiles, (long)per_cu * usable_cus(cus));
-    if (conv_packed_variant() == 5) conv_ring_f32_kernel<0, 5, 1, 1><<<grid, 256, 0, st>>>(a);
-    else conv_ring_f32_kernel<0, 4, 1, 1><<<grid, 256, 0, st>>>(a);
-    SN_LAUNCH_CHECK("conv_ring_f32_kernel<packed, PRO, pair>");
-    return STABNET_OK;
-}
-
 int conv_launch_pair(const ConvArgs& a, const ConvPair& pr, hipStream_t st, Prof* prof, const float* w_img) {
-    g_bf16_operands = 0;
     SN_REQUIRE(a.Cin % 16 == 0 && a.Cout % 4 == 0, "conv pair: Cin %% 16 and Cout %% 4 must be 0");
     SN_REQUIRE(a.splitk >= 1 && a.steps_per_split >= 1 && a.div_hw_mul != 0, "conv pair: conv_plan() not called");
     SN_REQUIRE(a.splitk == 1 || a.partial != nullptr, "conv pair: split-K needs a workspace");
@@ -686,18 +629,29 @@ int conv_launch_pair(const ConvArgs& a, const ConvPair& pr, hipStream_t st, Prof
                pr.m_tower, a.M);
     const bool bk32 = conv_bk(a) == 32;
     const int mode = a.pad == 0 ? 0 : 1;
-    const bool rec = prof != nullptr && prof->begin(st);
-    int rc;
-    // 1x1 layers: the LDS-DMA ring kernel with the BN + ReLU prologue on the A fragments (both towers in one launch: the offsets of
-    // the second tower all derive from the distance of the two workspaces, which must be what ConvPair describes)
-    const bool pro = bk32 && ring_pro_eligible(a) && pr.dx == pr.dscale - (long)pr.m_tower * a.Cin && pr.dy == pr.dscale - (long)pr.m_tower * a.Cout &&
+    // 1x1 layers: the LDS-DMA ring kernel with the BN + ReLU prologue on the A fragments, exact f32 (both towers in one launch: the
+    // offsets of the second tower all derive from the distance of the two workspaces, which must be what ConvPair describes); with a
+    // weight image the packed split kernel's prologue form
+    const bool pro = bk32 && ring_pro_eligible(a, 0) && pr.dx == pr.dscale - (long)pr.m_tower * a.Cin && pr.dy == pr.dscale - (long)pr.m_tower * a.Cout &&
                      (a.residual == nullptr || pr.dres == pr.dscale - (long)(a.N / 2) * a.res_H * a.res_W * a.res_ld);
     const bool packed = pro && w_img != nullptr && a.K % 32 == 0 && a.splitk == 1;
-    if (packed) rc = launch_ring_packed_pro_pair(a, pr.dscale, w_img, st);
-    else if (pro) rc = launch_ring_pro(a, pr.dscale, st);
-    else if (bk32) rc = mode == 0 ? launch_pair_one<32, 0>(a, pr, st) : launch_pair_one<32, 1>(a, pr, st);
-    else rc = mode == 0 ? launch_pair_one<16, 0>(a, pr, st) : launch_pair_one<16, 1>(a, pr, st);
-    if (rec) prof->end(st, packed ? PK_KERNEL_CONV_PACKED + 3 : pro ? PK_KERNEL_CONV_KG + 2 : PK_KERNEL_CONV_PAIR + mode * 2 + (bk32 ? 1 : 0), 2.0 * a.M * (double)(a.KH * a.KW * (a.cin_real ? a.cin_real : a.Cin)) * a.Cout,
+    ConvRoute r{};
+    r.family = packed ? CONV_PACKED : CONV_RING_PRO;
+    r.operand = packed ? 4 : 0;
+    r.kg = r.pro = 1;
+    const bool rec = prof != nullptr && prof->begin(st);
+    int rc;
+    if (pro) {
+        ConvArgs b = a;
+        b.out_floor = reinterpret_cast<const float*>((size_t)pr.dscale);      // the kernel's pair distance (not a pointer: see conv_ring_kernel.h PRO)
+        if (packed) b.w = w_img;
+        rc = launch_ring_route(r, b, st);
+    } else if (bk32) {
+        rc = mode == 0 ? launch_pair_one<32, 0>(a, pr, st) : launch_pair_one<32, 1>(a, pr, st);
+    } else {
+        rc = mode == 0 ? launch_pair_one<16, 0>(a, pr, st) : launch_pair_one<16, 1>(a, pr, st);
+    }
+    if (rec) prof->end(st, pro ? route_prof_kind(r) : PK_KERNEL_CONV_PAIR + mode * 2 + (bk32 ? 1 : 0), 2.0 * a.M * (double)(a.KH * a.KW * (a.cin_real ? a.cin_real : a.Cin)) * a.Cout,
                        4.0 * ((double)a.N * a.H * a.W * a.Cin + (double)a.K * a.Cout + (double)a.M * a.Cout * a.splitk),
                        a.M, a.Cout, a.K, a.splitk);
     if (rc) return rc;
@@ -716,14 +670,12 @@ bool conv_b2b_supported(const ConvArgs& c2, const ConvArgs& c3) {
     // A LAUNCH strategy the inference plan does not choose by default (STABNET_CONV_B2B_PLAN=1 turns it on, net.hip): measured
     // in the 720p frame it loses to the two launches at every unit it applies to.  The operator
     // itself (stabnet_conv3x3_conv1x1_fwd) is always available.
-    static const int on = env_int("STABNET_CONV_B2B", 1);
-    if (g_ring < 0) g_ring = env_int("STABNET_CONV_RING", 1);
     const bool g2 = c2.KH == 3 && c2.KW == 3 && c2.pad == 1 && c2.up == 1 && !c2.rowrun && (c2.stride == 1 || c2.stride == 2) &&
                     c2.Cin == c2.Cout && (c2.Cout == 64 || c2.Cout == 128) && c2.in_scale_expected == 0 && c2.in_scale == nullptr;
     const bool g3 = c3.KH == 1 && c3.KW == 1 && c3.pad == 0 && c3.stride == 1 && c3.up == 1 && !c3.rowrun && c3.Cin == c2.Cout &&
                     (c3.x_ld == 0 || c3.x_ld == c3.Cin) && c3.Cout % c2.Cout == 0 && c3.N == c2.N && c3.H == c2.Ho && c3.W == c2.Wo &&
                     c3.in_scale_expected == 0 && c3.in_scale == nullptr;
-    return on && g_ring && g2 && g3;
+    return sw().b2b && sw().ring && g2 && g3;
 }
 
 int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof* prof) {
@@ -731,12 +683,8 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
     SN_REQUIRE(c2.div_hw_mul != 0 && c3.div_hw_mul != 0 && c2.M == c3.M, "conv b2b: conv_plan() not called on both convolutions");
     SN_REQUIRE(c2.x && c2.w && c3.w && c3.y && c2.out_scale && c2.out_shift, "conv b2b: null pointer");
     SN_REQUIRE(c2.bias == nullptr && c2.residual == nullptr, "conv b2b: the 3x3 convolution takes no bias / residual");
-    g_bf16_operands = 0;                                              // exact f32 only: the launch's mode, whatever the last launch left
-    const int cus = device_cus();
-    if (cus <= 0) {
-        stabnet_set_error("conv: cannot read the CU count");
-        return STABNET_ERR_LAUNCH;
-    }
+    int cus = 0;
+    if (const int rc = device_cus(cus)) return rc;
     B2bArgs P;
     P.c2 = c2;
     P.c3 = c3;
@@ -745,8 +693,7 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
     const int tiles_m = cdiv(c2.M, 64);
     const bool rec = prof != nullptr && prof->begin(st);
     if (c2.Cout == 64) {
-        static const int wgs = env_int("STABNET_CONV_B2B_WGS_PER_CU", 2);     // 80 KB of LDS each
-        conv_b2b_f32_kernel<2><<<std::min(tiles_m, wgs * usable_cus(cus)), 256, 0, st>>>(P);
+        conv_b2b_f32_kernel<2><<<std::min(tiles_m, sw().b2b_wgs_per_cu * usable_cus(cus)), 256, 0, st>>>(P);
     } else {
         conv_b2b_f32_kernel<4><<<std::min(tiles_m, usable_cus(cus)), 512, 0, st>>>(P);    // 136 KB of LDS
     }
@@ -932,7 +879,6 @@ int stabnet_conv3x3_conv1x1_fwd(const float* x, int x_ld, const float* w2_ohwi, 
     c3.out_scale = out_scale;
     c3.out_shift = out_shift;
     SN_REQUIRE(conv_b2b_supported(c2, c3), "conv3x3_conv1x1_fwd: C must be 64 or 128, Cout a multiple of C, stride 1 or 2");
-    g_bf16_operands = 0;
     return conv_b2b_launch(c2, c3, (hipStream_t)stream);
 }
 

@@ -732,52 +732,8 @@ const char* stabnet_prof_kind_name(int kind) {
                                              "conv_wgrad_same_f32_kernel<0, 0, 1>", "conv_wgrad_same_f32_kernel<0, 1, 1>"};
         return names[kind - PK_KERNEL_WGRAD_SAME];
     }
-    if (kind >= PK_KERNEL_CONV_PAIR && kind < PK_KERNEL_CONV_PAIR + 4) {
-        static const char* const names[4] = {"conv_igemm_f32_pair_kernel<64, 64, 16, 32, 32, 0>", "conv_igemm_f32_pair_kernel<64, 64, 32, 32, 32, 0>",
-                                             "conv_igemm_f32_pair_kernel<64, 64, 16, 32, 32, 1>", "conv_igemm_f32_pair_kernel<64, 64, 32, 32, 32, 1>"};
-        return names[kind - PK_KERNEL_CONV_PAIR];
-    }
-    if (kind == PK_KERNEL_CONV_KG) return "conv_ring_f32_kernel<0, 0, 3, 0>";
-    if (kind == PK_KERNEL_CONV_KG + 1) return "conv_ring_f32_kernel<1, 0, 3, 0>";
-    if (kind == PK_KERNEL_CONV_KG + 2) return "conv_ring_f32_kernel<0, 0, 1, 1>";
-    if (kind == PK_KERNEL_CONV_KG + 3) return "conv_ring_f32_kernel<0, 0, 2, 1>";
-    // names as rocprofv3 prints the template instantiation <MODE, BF16>
-    if (kind == PK_KERNEL_CONV_RING) return "conv_ring_f32_kernel<0, 0, 1, 0>";
-    if (kind == PK_KERNEL_CONV_RING + 1) return "conv_ring_f32_kernel<1, 0, 1, 0>";
-    if (kind == PK_KERNEL_CONV_RING + 2) return "conv_ring_f32_kernel<2, 0, 1, 0>";
-    if (kind == PK_KERNEL_CONV_RING + 3) return "conv_ring_f32_kernel<0, 1, 1, 0>";
-    if (kind == PK_KERNEL_CONV_RING + 4) return "conv_ring_f32_kernel<1, 1, 1, 0>";
-    if (kind == PK_KERNEL_CONV_RING + 5) return "conv_ring_f32_kernel<2, 1, 1, 0>";
-    if (kind >= PK_KERNEL_CONV_PACKED && kind <= PK_KERNEL_CONV_PACKED + 6) {      // conv_ring_f32_kernel<MODE, 4 | 5, KG, PRO>
-        static const int shape[7][3] = {{0, 1, 0}, {1, 1, 0}, {2, 1, 0}, {0, 1, 1}, {0, 2, 0}, {1, 2, 0}, {0, 2, 1}};
-        static thread_local char pbuf[7][48];
-        const int i = kind - PK_KERNEL_CONV_PACKED;
-        snprintf(pbuf[i], sizeof(pbuf[i]), "conv_ring_f32_kernel<%d, %d, %d, %d>", shape[i][0], conv_packed_variant(), shape[i][1], shape[i][2]);
-        return pbuf[i];
-    }
-    if (kind >= PK_KERNEL_CONV_SPLIT && kind < PK_KERNEL_CONV_SPLIT + 16 && (kind - PK_KERNEL_CONV_SPLIT) % 8 < 7) {   // modes 2 / 3
-        static const int shape[7][3] = {{0, 1, 0}, {1, 1, 0}, {2, 1, 0}, {0, 3, 0}, {1, 3, 0}, {0, 1, 1}, {0, 2, 1}};   // MODE, KG, PRO
-        static thread_local char sbuf[16][48];
-        const int i = kind - PK_KERNEL_CONV_SPLIT, s = i % 8;
-        snprintf(sbuf[i], sizeof(sbuf[i]), "conv_ring_f32_kernel<%d, %d, %d, %d>", shape[s][0], 2 + i / 8, shape[s][1], shape[s][2]);
-        return sbuf[i];
-    }
-    if (kind == PK_KERNEL_CONV_B2B) return "conv_b2b_f32_kernel<2>";
-    if (kind == PK_KERNEL_CONV_B2B + 1) return "conv_b2b_f32_kernel<4>";
-    if (kind >= PK_KERNEL_CONV_BASE && kind < PK_KERNEL_CONV_BASE + 144) {
-        // names as rocprofv3 prints the template instantiation: <BM, BN, BK, WM, WN, MODE, NBUF, BF16>
-        // (kind = base + MODE*6 + tile*2 + (BK==32) + 18 if NBUF == 1 + 36 * BF16, conv.hip)
-        static thread_local char buf[96];
-        int k = kind - PK_KERNEL_CONV_BASE;
-        const int bf16 = k / 36;
-        k -= 36 * bf16;
-        const int nbuf = k >= 18 ? 1 : 2;
-        k -= (nbuf == 1) ? 18 : 0;
-        const int mode = k / 6, t = (k % 6) / 2, bk = (k & 1) ? 32 : 16;
-        const int bm = (t == 2) ? 64 : 128, bn = (t == 0) ? 128 : 64, wm = (t == 2) ? 32 : 64, wn = (t == 0) ? 64 : 32;
-        snprintf(buf, sizeof(buf), "conv_igemm_f32_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", bm, bn, bk, wm, wn, mode, nbuf, bf16);
-        return buf;
-    }
+    const char* conv = conv_prof_kind_name(kind);              // the PK_KERNEL_CONV_* kinds: named where they are numbered (conv.hip)
+    if (conv != nullptr) return conv;
     return "?";
 }
 

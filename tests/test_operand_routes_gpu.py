@@ -7,11 +7,15 @@ stabnet_net_set_bf16_operands).  The plan switches are read once per process, so
   b. kernel class: every conv record of the Profiler names an instantiation of the mode (BF16 template argument = the mode;
      mode 4 also runs the exact-f32 kernels wherever no packed kernel takes a launch);
   c. launch accounting: the records of one forward / one deploy step equal stabnet_net_num_launches /
-     stabnet_deploy_frame_launches (the plan-time model of the launcher's routing);
+     stabnet_deploy_frame_launches (conv_route()'s plan-time view of the launcher's routing);
   d. the same bits every time;
   e. guard bands: `fold` and the workspace carry 64 KiB canary tails beyond their queried sizes, `fold` is NaN before
-     stabnet_net_fold_bn and the workspace NaN before every forward -- theta stays finite and within (a)."""
+     stabnet_net_fold_bn and the workspace NaN before every forward -- theta stays finite and within (a);
+  f. the same kernels: the ordered Profiler names of the forward at both shapes and of the deploy step equal
+     tests/golden/conv_routes.json, recorded (twice, with equal results) with this child before conv_route() became the single routing
+     decision of conv.hip.  A change that moves a launch to another kernel has to say so by recording the fixture again."""
 import functools
+import json
 import os
 import re
 import subprocess
@@ -51,14 +55,14 @@ def _ring_family(b):
     return {_ring(m, b) for m in (0, 1, 2)} | {_ring(0, b, 3), _ring(1, b, 3), _ring(0, b, 1, 1), _ring(0, b, 2, 1)}
 
 
-# the packed split kernel (PK_KERNEL_CONV_PACKED, net.hip stabnet_prof_kind_name): <MODE, 4, KG, PRO>
+# the packed split kernel (PK_KERNEL_CONV_PACKED, conv.hip conv_prof_kind_name): <MODE, 4, KG, PRO>
 PACKED = {_ring(m, 4) for m in (0, 1, 2)} | {_ring(0, 4, 1, 1), _ring(0, 4, 2, 0), _ring(1, 4, 2, 0), _ring(0, 4, 2, 1)}
 B2B = {"conv_b2b_f32_kernel<2>", "conv_b2b_f32_kernel<4>"}
 IGEMM = re.compile(r"conv_igemm_f32_kernel<\d+, \d+, \d+, \d+, \d+, \d, \d, (\d)>$")
 # mode -> (allowed ring / fused names, allowed BF16 arguments of the register-staged kernel)
 ALLOWED = {
     0: (_ring_family(0) | B2B, {0}),
-    1: ({_ring(m, 1) for m in (0, 1, 2)}, {1}),          # (no K groups and no PRO form on bf16 operands: conv_kgroups, ring_pro_*)
+    1: ({_ring(m, 1) for m in (0, 1, 2)}, {1}),          # (no K groups and no PRO form on bf16 operands: conv.hip conv_route)
     2: (_ring_family(2), {2}),
     3: (_ring_family(3), {3}),
     4: (_ring_family(0) | B2B | PACKED, {0}),
@@ -125,6 +129,15 @@ def _child(mode, switches, tmp):
     return dict(np.load(out))
 
 
+@functools.lru_cache(maxsize=None)
+def _recorded_routes():
+    """route id -> the three recorded name sequences (forward at SHAPES[0], at SHAPES[1], deploy step) of tests/golden/conv_routes.json:
+    one table of distinct kernel names, and per route three lists of indices into it."""
+    with open(os.path.join(ROOT, "tests", "golden", "conv_routes.json")) as fh:
+        rec = json.load(fh)
+    return {rid: [[rec["names"][i] for i in seq] for seq in seqs] for rid, seqs in rec["routes"].items()}
+
+
 def _errors(d):
     errs = []
     for si, shape in enumerate(SHAPES):
@@ -180,6 +193,13 @@ def test_route_keeps_its_operand_mode(cuda, tmp_path_factory, mode, switches):
     bad = _bad_names(dep, mode)
     if bad:
         problems.append("deploy step: kernels outside mode %d: %s" % (mode, sorted(set(bad))))
+    # f. the recorded kernel sequence
+    ran = [[str(n) for n in d["names_%d" % si]] for si in range(len(SHAPES))] + [dep]
+    for what, got, want in zip(["%s" % (s,) for s in SHAPES] + ["deploy step"], ran, _recorded_routes()["mode%d-%s" % (mode, switches)]):
+        if got != want:
+            first = next((i for i, (g, w) in enumerate(zip(got, want)) if g != w), min(len(got), len(want)))
+            problems.append("%s: %d launches recorded, %d ran; first difference at launch %d: recorded %s, ran %s" % (
+                what, len(want), len(got), first, want[first:first + 1], got[first:first + 1]))
     assert not problems, "\n".join(problems)
 
 
