@@ -46,7 +46,9 @@ __global__ __launch_bounds__(256) void max_pool_kernel(const float* __restrict__
             const int ix = ox * stride - pl + dx;
             if (ix < 0 || ix >= W) continue;
             const float4 v = *reinterpret_cast<const float4*>(x + (((long)n * H + iy) * W + ix) * C + c);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            // at a tie the LATER tap wins: only the sign of a zero maximum can tell, and that is where the oracle puts it (NumPy's
+            // maximum(acc, tap) hands back its second operand); fmaxf prefers +0 over -0 wherever it stands
+            m.x = v.x >= m.x ? v.x : m.x; m.y = v.y >= m.y ? v.y : m.y; m.z = v.z >= m.z ? v.z : m.z; m.w = v.w >= m.w ? v.w : m.w;
         }
     }
     if (scale != nullptr) {

@@ -158,3 +158,94 @@ def conv2d_dgrad(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None):
     _lib.call("stabnet_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), ptr(residual), N, H, W, Cin, Cout, KH, KW, stride, pad,
               ptr(ws), nbytes, stream_ptr(dy.device), device=dy.device)
     return dx
+
+
+# ---- the non-convolution inference layers and the head, one operator per call (the launchers of the plan) ------------------
+
+def pad_channels(x, y):
+    """x [..., C] -> y [..., Cp] (given, Cp % 4 == 0): zeros in the pad channels."""
+    C, Cp = x.shape[-1], y.shape[-1]
+    _lib.call("stabnet_pad_channels", ptr(x), ptr(y), x.numel() // C, C, Cp, stream_ptr(x.device), device=x.device)
+    return y
+
+
+def stem_repack(w, out, cin):
+    """w OHWI [Cout, KH, KW, CinPad] -> out [Cout, KH, roundup(KW * cin, 32)]."""
+    Cout, KH, KW, CinPad = w.shape
+    _lib.call("stabnet_stem_repack", ptr(w), ptr(out), Cout, KH, KW, CinPad, int(cin), stream_ptr(w.device), device=w.device)
+    return out
+
+
+def merge_vectors(b_sc, scale1, shift1, out):
+    """-> out [4, depth + dbn] = [bias | scale | shift | floor] of a merged (shortcut | conv1) launch."""
+    _lib.call("stabnet_merge_vectors", ptr(b_sc), ptr(scale1), ptr(shift1), b_sc.numel(), scale1.numel(), ptr(out),
+              stream_ptr(out.device), device=out.device)
+    return out
+
+
+def bn_fold(gamma, beta, mean, var, eps, scale, shift):
+    _lib.call("stabnet_bn_fold", ptr(gamma), ptr(beta), ptr(mean), ptr(var), float(eps), gamma.numel(), ptr(scale), ptr(shift),
+              stream_ptr(gamma.device), device=gamma.device)
+    return scale, shift
+
+
+def max_pool_fwd(x, y, k, stride, pt, pl, scale=None, shift=None):
+    """x [N,H,W,C] -> y [N,Ho,Wo,C] (Ho, Wo are taken from y); scale, shift: the consumer's folded BN + ReLU on the pooled value."""
+    N, H, W, C = x.shape
+    _lib.call("stabnet_max_pool_fwd", ptr(x), ptr(y), N, H, W, C, y.shape[1], y.shape[2], k, stride, pt, pl, ptr(scale), ptr(shift),
+              stream_ptr(x.device), device=x.device)
+    return y
+
+
+def gap_partial_floats(N, HW, C):
+    return int(_lib.lib().stabnet_gap_partial_floats(N, HW, C))
+
+
+def gap_bn_relu(x, scale, shift, out, partial=None):
+    """x [N,HW,C] -> out [N,C] = mean over HW of relu(x * scale + shift)."""
+    N, HW, C = x.shape
+    if partial is None:
+        partial = empty((gap_partial_floats(N, HW, C),), x)
+    _lib.call("stabnet_gap_bn_relu", ptr(x), ptr(scale), ptr(shift), N, HW, C, ptr(out), ptr(partial), partial.numel(),
+              stream_ptr(x.device), device=x.device)
+    return out
+
+
+def fc_fwd(x, w, b, y, relu):
+    """y [M,Nout] = act(x [M,K] w [Nout,K]^T + b); b may be None."""
+    M, K = x.shape
+    _lib.call("stabnet_fc_fwd", ptr(x), ptr(w), ptr(b), ptr(y), M, K, w.shape[0], int(bool(relu)), stream_ptr(x.device), device=x.device)
+    return y
+
+
+def head_fused_supported(N, C, fc_dims):
+    import ctypes
+    dims = (ctypes.c_int * 5)(*[int(d) for d in fc_dims])
+    return bool(_lib.lib().stabnet_head_fused_supported(N, C, ctypes.addressof(dims)))
+
+
+def head_gap_partial_floats(N, HW, C):
+    return int(_lib.lib().stabnet_head_gap_partial_floats(N, HW, C))
+
+
+def head_gap_fc1(x, scale, shift, w, b, y, gap_out=None, partial=None):
+    """x [N,HW,C] -> y [N,Nout] = relu(fc_1(mean over HW of relu(x * scale + shift))); gap_out [N,C] (optional): the pooled feature."""
+    N, HW, C = x.shape
+    if partial is None:
+        partial = empty((head_gap_partial_floats(N, HW, C),), x)
+    _lib.call("stabnet_head_gap_fc1", ptr(x), ptr(scale), ptr(shift), N, HW, C, ptr(partial), partial.numel(), ptr(gap_out), ptr(w),
+              ptr(b), ptr(y), w.shape[0], stream_ptr(x.device), device=x.device)
+    return y
+
+
+def head_theta_mesh(x, w, b, theta, grid_h=1, grid_w=1, do_crop_rate=1.0, Hs=None, head_adv=None, depth=1, prefetch_src=None,
+                    prefetch_hw=(0, 0), prefetch_ptr=None):
+    """x [N,512] -> theta [N,n_theta] (output layer); Hs [N,gh,gw,9] (optional): the mesh homographies of that theta; head_adv
+    (optional, int32 [1]): advanced by one modulo depth; prefetch_src [N,H,W] (optional): a frame the launch only reads
+    (prefetch_ptr: a raw address in its place)."""
+    N, K = x.shape
+    pf = prefetch_ptr if prefetch_ptr is not None else ptr(prefetch_src)
+    _lib.call("stabnet_head_theta_mesh", ptr(x), ptr(w), ptr(b), N, K, w.shape[0], ptr(theta), int(grid_h), int(grid_w),
+              float(do_crop_rate), ptr(Hs), ptr(head_adv), int(depth), pf, int(prefetch_hw[0]), int(prefetch_hw[1]),
+              stream_ptr(x.device), device=x.device)
+    return theta

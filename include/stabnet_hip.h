@@ -177,6 +177,69 @@ size_t stabnet_net_fold_floats(const void* net);
 int stabnet_backbone_fwd_infer(const void* net, const float* params, const float* fold, const float* x_tensor,
                                float* theta, void* workspace, size_t workspace_bytes, void* stream, void* prof);
 
+/* ---- inference: the non-convolution layers and the head of the plan, one entry per operator -----------------
+ * The launchers that stabnet_backbone_fwd_infer / stabnet_deploy_frame / stabnet_net_fold_bn run, reachable one at a time.
+ * The plan hands them shapes it laid out itself; these entries refuse (STABNET_ERR_BAD_ARG, nothing launched) what the
+ * kernels cannot do: null or host pointers, a pointer the kernel reads as float4 that is not 16-byte aligned, and the shape
+ * limits named per entry.  Every sum is taken in a fixed order: the same call gives the same bits. */
+
+/* x_tensor [npix][C] -> y [npix][Cp], zeros in channels C..Cp (the 13 -> 16 channel stack in front of the stem conv,
+ * s_net_bundle_nobm.py:252).  Cp % 4 == 0, Cp >= C; y 16-byte aligned. */
+int stabnet_pad_channels(const float* x, float* y, long npix, int C, int Cp, void* stream);
+
+/* resnet_v2 `conv1` weights OHWI [Cout][KH][KW][CinPad] -> filter-row runs [Cout][KH][Rp], Rp = roundup(KW*Cin, 32): element
+ * kw*Cin + c, zeros behind (the inference stem reads the unpadded Cin-channel stack). */
+int stabnet_stem_repack(const float* w, float* out, int Cout, int KH, int KW, int CinPad, int Cin, void* stream);
+
+/* Epilogue vectors of a merged (projection shortcut | conv1) launch of resnet_v2 `bottleneck`: out [4][depth + dbn] =
+ * [bias | scale | shift | floor]; shortcut channels (b_sc, 1, 0, -inf), conv1 channels (0, scale1, shift1, 0 = ReLU). */
+int stabnet_merge_vectors(const float* b_sc, const float* scale1, const float* shift1, int depth, int dbn, float* out, void* stream);
+
+/* tf.nn.batch_normalization with moving averages, folded: scale = (1 / sqrt(var + eps)) * gamma, shift = beta - mean * scale,
+ * each operation one correctly rounded float32 operation (what stabnet_net_fold_bn runs over all G channels). */
+int stabnet_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int G, float* scale,
+                    float* shift, void* stream);
+
+/* slim max_pool2d [3,3] stride 2 of resnet_v2 ('pool1'), inference form: y [N,Ho,Wo,C] = max over the in-image taps of the
+ * window at (oy*stride - pt, ox*stride - pl) (out-of-image taps count as -inf); scale, shift [C] (both or neither): the
+ * consumer's folded BN + ReLU on the pooled value, y = max(fma(y, scale, shift), 0).  C % 4 == 0, fewer than 2^32 channel
+ * quads N*Ho*Wo*C/4; x, y, scale, shift 16-byte aligned. */
+int stabnet_max_pool_fwd(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, int k, int stride, int pt, int pl,
+                         const float* scale, const float* shift, void* stream);
+
+/* postnorm batch_norm + relu + tf.reduce_mean(resnet, [1, 2]) (s_net_bundle_nobm.py:254): out [N][C] = mean over HW of
+ * max(fma(x, scale, shift), 0), x [N][HW][C].  Sum order: rows r, r+16, ... of a chunk per lane, the 16 lanes, then the
+ * chunks (min(32, max(1, HW/32)) of ceil(HW/chunks) rows), one division.  partial: stabnet_gap_partial_floats(N, HW, C)
+ * floats of scratch (0 = bad arguments).  C % 4 == 0, N <= 65535; x, scale, shift, partial 16-byte aligned. */
+size_t stabnet_gap_partial_floats(int N, int HW, int C);
+int stabnet_gap_bn_relu(const float* x, const float* scale, const float* shift, int N, int HW, int C, float* out, float* partial,
+                        size_t partial_floats, void* stream);
+
+/* slim.fully_connected / output_layer (s_net_bundle_nobm.py:256-259, resnet.py:44-56): y [M][Nout] = act(x [M][K] w[Nout][K]^T
+ * + b), b may be NULL, relu = 0 | 1.  Per output element the same products in the same order whatever M (rows are staged
+ * in LDS for 9..16 rows of at most 128 KiB, else read in passes of 16 and 8).  K % 4 == 0; x, w 16-byte aligned. */
+int stabnet_fc_fwd(const float* x, const float* w, const float* b, float* y, int M, int K, int Nout, int relu, void* stream);
+
+/* The shortened inference head (batch <= 8).  stabnet_head_fused_supported: 1 when the plan takes it for fc_dims =
+ * [C, 2048, 1024, 512, n_theta] (host ints).
+ * stabnet_head_gap_fc1: the pooling above as partial sums over min(max(1, 8/N), max(1, HW/16)) chunks, then fc_1 (ReLU) whose
+ * input staging adds the chunks and divides by HW: y [N][Nout]; gap_out [N][C] (optional, NULL) receives the pooled feature
+ * ("global_pool").  y has the bits of stabnet_fc_fwd(gap_out, relu = 1).  N <= 8, C % 64 == 0, C <= 2048; partial:
+ * stabnet_head_gap_partial_floats(N, HW, C) floats (0 = bad arguments).
+ * stabnet_head_theta_mesh: output_layer (no activation) theta [N][n_theta] = x [N][K] w[n_theta][K]^T + b, K == 512,
+ * n_theta <= 64; Hs (optional, NULL) [N][gh*gw][9]: get_4_pts + get_Hs of that theta (s_net_bundle_nobm.py:29-71), the bits of
+ * stabnet_get_4_pts on it -- needs n_theta == 2(gh+1)(gw+1), gh*gw <= 64; head_adv (optional, NULL): *head_adv =
+ * (*head_adv + 1) % depth, once per call (the online loop's ring head); prefetch_src (optional, NULL) [N][pf_H][pf_W]: a frame
+ * that extra workgroups only read (cache warm-up for the sampler behind; silently off when pf_W % 4 != 0, pf_H < 8 or the
+ * pointer is not 16-byte aligned). */
+int stabnet_head_fused_supported(int N, int C, const int* fc_dims);
+size_t stabnet_head_gap_partial_floats(int N, int HW, int C);
+int stabnet_head_gap_fc1(const float* x, const float* scale, const float* shift, int N, int HW, int C, float* partial,
+                         size_t partial_floats, float* gap_out, const float* w, const float* b, float* y, int Nout, void* stream);
+int stabnet_head_theta_mesh(const float* x, const float* w, const float* b, int N, int K, int n_theta, float* theta, int grid_h,
+                            int grid_w, float do_crop_rate, float* Hs, int* head_adv, int depth, const float* prefetch_src, int pf_H,
+                            int pf_W, void* stream);
+
 /* ---- the online loop (deploy_bundle.py) ------------------------------------------------------------------ */
 
 /* History ring initialisation: `depth` copies of the first frame and zero masks per stream

@@ -22,7 +22,9 @@ def _setup(N, H, W):
     return cfg, ocfg, P, x
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (1, 90, 130), (1, 288, 512)])
+# (batch 4 and 8: the shortened head at 2 chunks and 1 chunk, fc_1 in 64 KiB of LDS; 9 and 17: the layer-by-layer head, fc_lds_kernel
+# and fc_kernel<16> + <8>)
+@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (1, 90, 130), (1, 288, 512), (4, 64, 96), (8, 64, 96), (9, 64, 96), (17, 64, 96)])
 def test_regressor_taps_and_theta(cuda, N, H, W):
     from stabnet_amd.regressor import Regressor
     cfg, ocfg, P, x = _setup(N, H, W)

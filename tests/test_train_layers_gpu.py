@@ -13,10 +13,10 @@ import pytest
 import torch
 import torch.nn.functional as Fnn
 
+from _guarded import Guarded, _check_all, _same_bits
+
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096                                               # canary words on each side of a buffer
-CANARY = 0x5CA1AB1E
 EPS, DECAY = 1e-5, 0.997                                   # slim resnet_arg_scope (config.Config.bn_eps / bn_decay)
 EPS32 = float(np.float32(EPS))
 OMD = 1.0 - float(np.float32(DECAY))                       # 1 - decay as the kernel forms it in float32 (exact: Sterbenz)
@@ -31,50 +31,8 @@ R_BUCKETS = (0, 1, 3, 8, 16, 32, 100)                      # |mean| / std of a c
 
 
 # ---- plumbing ---------------------------------------------------------------------------------------------------------------
-class Guarded:
-    """n elements between two canary bands.  init: None = NaN (float) / 0xEE (bytes), "canary" = the canary word, or values."""
-
-    def __init__(self, dev, n, init=None, dtype=torch.float32):
-        self.n = int(n)
-        self.words = self.n if dtype == torch.float32 else (self.n + 3) // 4
-        self.buf = torch.full((self.words + 2 * GUARD,), CANARY, dtype=torch.int32, device=dev)
-        inner = self.buf[GUARD:GUARD + self.words]
-        self.t = inner.view(dtype)[:self.n]
-        if isinstance(init, str):
-            assert init == "canary"
-        elif init is None:
-            self.t.fill_(float("nan") if dtype == torch.float32 else 0xEE)
-        else:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init).reshape(-1)).to(dev))
-
-    def check(self, what):
-        lo, hi = self.buf[:GUARD], self.buf[GUARD + self.words:]
-        assert bool((lo == CANARY).all()) and bool((hi == CANARY).all()), "write outside " + what
-
-    def np(self):
-        return self.t.cpu().numpy().copy()
-
-    def untouched(self):
-        return bool((self.buf == CANARY).all())
-
-
-def _check_all(named):
-    torch.cuda.synchronize()
-    for what, b in named.items():
-        if b is not None:
-            b.check(what)
-
-
 def _dev(a, cuda):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(cuda)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same_bits(a, b):
-    return np.array_equal(_bits(a), _bits(b))
 
 
 # ---- a. batch-statistics BN forward -----------------------------------------------------------------------------------------
