@@ -6,7 +6,9 @@
 //                       (sum + 16384) >> 15), BORDER_CONSTANT 0 -- integer arithmetic, bit-exact against the oracle
 // Float32 op order of the two resizes as oracle/stabnet_oracle.py: cv_resize_linear_f32 (-ffp-contract=off).  HBM-bound:
 // per frame 8*H*W (maps in) + 3*H*W (frame, gathered) + 3*H*W (out) bytes.
+#include <cstdlib>
 #include "common.h"
+#include "prof.h"
 
 struct Taps1D { int i0, i1; float w0, w1; };
 
@@ -154,6 +156,144 @@ __global__ __launch_bounds__(256) void remap_color4_kernel(const unsigned char* 
     }
 }
 
+// ---- the same remap at SOURCE resolution: the frame as read ([SH, SW, C], any size, strided rows) warped by the network-size maps ----
+// small = cv2.resize(map, (w, h)) (map_shrink_kernel, as above); big = cv2.resize(small, (SW, SH)); network-pixel coordinate
+// u = (big + 1) / 2 * size as above; source-pixel coordinate under cv2's half-pixel convention p = u * s + c with s = SW / W and
+// c = 0.5 * SW / W - 0.5 (the reference's normalised coordinate counts pixel INDICES: without c an identity mesh would shift the picture
+// by 0.5 * (SW / W - 1) source pixels); both constants rounded once from double by the host, multiply then add, not fused.  Then the
+// fixed-point cv2.remap of remap_color_kernel.  With SH, SW == H, W: s = 1, c = 0 and every bit is stabnet_warp_rev_bundle2's.
+// One workgroup per row segment (grid = segments x SH x N): the vertical taps and the two small-map rows are wave-uniform.
+struct SrcRemapArgs {
+    int SH, SW, C, H, W, h, w;
+    float fW, fH, sx, cx, sy, cy;            // (float)W, (float)H; float32(SW / W), float32(0.5 * SW / W - 0.5), likewise y
+    double xscale, yscale;                   // (double)w / SW, (double)h / SH: cv_taps of the resize back up
+    size_t row_stride, frame_stride;         // bytes
+};
+
+struct SrcCoord { float px, py; int qx, qy; };   // qx, qy: the coordinate in 1/32 px, rounded half to even
+
+__device__ __forceinline__ SrcCoord remap_src_coord(const float* __restrict__ mx, const float* __restrict__ my, const SrcRemapArgs& a,
+                                                    const Taps1D& tx, const Taps1D& ty) {
+    const float xs = cv_resize_at(mx, a.w, tx, ty), ys = cv_resize_at(my, a.w, tx, ty);
+    const float ux = (xs + 1.0f) / 2.0f * a.fW;                     // deploy_bundle.py:142-143
+    const float uy = (ys + 1.0f) / 2.0f * a.fH;
+    SrcCoord c;
+    c.px = ux * a.sx + a.cx;
+    c.py = uy * a.sy + a.cy;
+    const float qx = fminf(fmaxf(c.px * 32.0f, -2.0e9f), 2.0e9f), qy = fminf(fmaxf(c.py * 32.0f, -2.0e9f), 2.0e9f);
+    c.qx = (qx == qx) ? (int)rintf(qx) : -2000000000;
+    c.qy = (qy == qy) ? (int)rintf(qy) : -2000000000;
+    return c;
+}
+
+// coverage: the rounded coordinate lies outside the frame (a NaN map entry too: -2e9)
+__device__ __forceinline__ bool remap_src_black(const SrcCoord& c, int SH, int SW) {
+    return c.qx < 0 || c.qx > 32 * (SW - 1) || c.qy < 0 || c.qy > 32 * (SH - 1);
+}
+
+// grid (cdiv(SW, blockDim.x), SH, N): one pixel per thread, any C, width, stride and alignment; byte loads and stores.
+__global__ __launch_bounds__(256) void remap_src_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a,
+                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
+    if (x >= a.SW) return;
+    const int SH = a.SH, SW = a.SW, C = a.C;
+    const Taps1D tx = cv_taps(x, a.w, a.xscale), ty = cv_taps(y, a.h, a.yscale);
+    const size_t hw = (size_t)a.h * a.w;
+    const SrcCoord c = remap_src_coord(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
+    const size_t pix = ((size_t)n * SH + y) * SW + x;
+    if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
+    const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
+    const int fx = c.qx & 31, fy = c.qy & 31;
+    int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+    if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
+    const unsigned char* im = src + (size_t)n * a.frame_stride;
+    const bool x0 = ix >= 0 && ix < SW, x1 = ix + 1 >= 0 && ix + 1 < SW, y0 = iy >= 0 && iy < SH, y1 = iy + 1 >= 0 && iy + 1 < SH;
+    for (int ch = 0; ch < C; ++ch) {
+        const int v00 = (x0 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)ix * C + ch] : 0;
+        const int v01 = (x1 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
+        const int v10 = (x0 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)ix * C + ch] : 0;
+        const int v11 = (x1 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
+        const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+        out[pix * C + ch] = (unsigned char)min(max(acc, 0), 255);
+    }
+    if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix] += 1;
+}
+
+// bytes p .. p+5 in the low 48 bits (lo <= p, p + 3 <= hi; [lo, hi) = the frame's own bytes): the three aligned dwords that cover
+// them where all three lie inside [lo, hi), funnel-shifted; bytes otherwise (a frame that starts or ends inside a dword: any base
+// pointer and row stride are accepted, and nothing outside the frame is read)
+__device__ __forceinline__ unsigned long long remap_src_load6(const unsigned char* __restrict__ p, const unsigned char* lo,
+                                                              const unsigned char* hi) {
+    const uintptr_t al = (uintptr_t)p & ~(uintptr_t)3;
+    const int sh = 8 * (int)((uintptr_t)p & 3);
+    if (al >= (uintptr_t)lo && al + 12 <= (uintptr_t)hi) {
+        const unsigned* q = reinterpret_cast<const unsigned*>(al);
+        const unsigned d0 = q[0], d1 = q[1], d2 = q[2];
+        const unsigned l = (unsigned)(((((unsigned long long)d1) << 32) | d0) >> sh), h = (unsigned)(((((unsigned long long)d2) << 32) | d1) >> sh);
+        return (((unsigned long long)h) << 32) | l;
+    }
+    unsigned long long r = 0ull;
+    for (int k = 0; k < 6; ++k)
+        if (p + k < hi) r |= ((unsigned long long)p[k]) << (8 * k);
+    return r;
+}
+
+// grid (cdiv(SW / 4, blockDim.x), SH, N): four consecutive pixels per thread, C == 3, SW % 4 == 0, out 4-byte aligned (px_out / py_out
+// 16-byte): the taps of a row as dwords through the funnel shift, the 12 output bytes as three dwords (remap_color4_kernel's traffic).
+__global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a,
+                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
+    if (x0 >= a.SW) return;
+    const int SH = a.SH, SW = a.SW;
+    const Taps1D ty = cv_taps(y, a.h, a.yscale);
+    const size_t hw = (size_t)a.h * a.w;
+    const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
+    const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
+    const unsigned char* im = src + (size_t)n * a.frame_stride;
+    const unsigned char* end = im + (size_t)(SH - 1) * a.row_stride + (size_t)SW * 3;
+    const size_t pix = ((size_t)n * SH + y) * SW + x0;
+    unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
+    float pxs[4], pys[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const Taps1D tx = cv_taps(x0 + e, a.w, a.xscale);
+        const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
+        pxs[e] = c.px; pys[e] = c.py;
+        const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
+        const int fx = c.qx & 31, fy = c.qy & 31;
+        int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+        if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
+        const bool vx0 = ix >= 0 && ix < SW, vx1 = ix + 1 >= 0 && ix + 1 < SW, vy0 = iy >= 0 && iy < SH, vy1 = iy + 1 >= 0 && iy + 1 < SH;
+        // rows iy and iy + 1: 6 bytes from pixel max(ix, 0) on (ix == -1: the first three bytes are tap 1)
+        unsigned long long r0 = 0ull, r1 = 0ull;
+        const int cx = max(ix, 0);
+        if ((vx0 || vx1) && vy0) r0 = remap_src_load6(im + (size_t)iy * a.row_stride + (size_t)cx * 3, im, end);
+        if ((vx0 || vx1) && vy1) r1 = remap_src_load6(im + (size_t)(iy + 1) * a.row_stride + (size_t)cx * 3, im, end);
+        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                  // tap 0 out of frame on the left: what was loaded is tap 1
+        const unsigned long long m0 = vx0 ? 0xffffffull : 0ull, m1 = vx1 ? 0xffffff000000ull : 0ull;
+        r0 &= (vy0 ? (m0 | m1) : 0ull);
+        r1 &= (vy1 ? (m0 | m1) : 0ull);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int v00 = (int)((r0 >> (8 * ch)) & 0xff), v01 = (int)((r0 >> (24 + 8 * ch)) & 0xff);
+            const int v10 = (int)((r1 >> (8 * ch)) & 0xff), v11 = (int)((r1 >> (24 + 8 * ch)) & 0xff);
+            const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+            const unsigned o = (unsigned)min(max(acc, 0), 255);
+            const int byte = e * 3 + ch;
+            ob[byte >> 2] |= o << (8 * (byte & 3));
+        }
+        if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix + e] += 1;
+    }
+    unsigned* op = reinterpret_cast<unsigned*>(out + pix * 3);
+    op[0] = ob[0]; op[1] = ob[1]; op[2] = ob[2];
+    if (px_out != nullptr) {
+        *reinterpret_cast<float4*>(px_out + pix) = make_float4(pxs[0], pxs[1], pxs[2], pxs[3]);
+        *reinterpret_cast<float4*>(py_out + pix) = make_float4(pys[0], pys[1], pys[2], pys[3]);
+    }
+}
+
 // cvt_train2img (deploy_bundle.py:75): ((x + 0.5) * 255).astype(uint8), clipped to [0, 255] first (the network's grey output is a
 // bilinear blend of inputs in [-0.5, 0.5], so the clip only guards the cast).  4 pixels per thread, float4 in, one dword out.
 __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long n) {
@@ -166,6 +306,12 @@ __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restr
     } else {
         for (long j = i; j < n && j < i + 4; ++j) out[j] = (unsigned char)cv(x[j]);
     }
+}
+
+// STABNET_REMAP_VEC4=0: the one-pixel-per-thread kernels everywhere (debug switch; read once)
+static int remap_vec4_enabled() {
+    static const int v4 = []() { const char* v = getenv("STABNET_REMAP_VEC4"); return v ? atoi(v) : 1; }();
+    return v4;
 }
 
 extern "C" {
@@ -182,7 +328,7 @@ int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const
     hipStream_t st = (hipStream_t)stream;
     map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
     SN_LAUNCH_CHECK("map_shrink_kernel");
-    static const int v4 = []() { const char* v = getenv("STABNET_REMAP_VEC4"); return v ? atoi(v) : 1; }();
+    const int v4 = remap_vec4_enabled();
     const bool aligned = (((size_t)img | (size_t)out) & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
     if (v4 && C == 3 && W % 4 == 0 && (long)H * W * 3 >= 8 && aligned) {
         remap_color4_kernel<<<dim3(cdiv((long)H * W / 4, 256), N), 256, 0, st>>>(img, workspace, H, W, h, w, out, px_out, py_out);
@@ -191,6 +337,59 @@ int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const
     }
     remap_color_kernel<<<dim3(cdiv((long)H * W, 256), N), 256, 0, st>>>(img, workspace, H, W, C, h, w, out, px_out, py_out);
     SN_LAUNCH_CHECK("remap_color_kernel");
+    return STABNET_OK;
+}
+
+/* warpRevBundle2 at SOURCE resolution: src uint8 [N,SH,SW,C] (rows row_stride_bytes apart) remapped by the network-size maps
+ * x_map, y_map [N,H,W] -> out uint8 [N,SH,SW,C] dense.  black_count (optional, int32 [N,SH,SW]): += 1 on pixels whose rounded
+ * coordinate lies outside the frame.  px_out/py_out (optional, [N,SH,SW]): the source-pixel coordinates cv2.remap would receive. */
+int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                 const float* x_map, const float* y_map, int H, int W, int rate,
+                                 unsigned char* out, int* black_count, float* workspace,
+                                 float* px_out, float* py_out, void* stream, void* profp) {
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_src: null pointer");
+    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_src: C must be 1 (grey) or 3 (BGR), got %d", C);
+    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_src: batch %d outside 1..65535", N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
+               "warp_rev_bundle2_src: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_src: maps %dx%d leave nothing at rate %d", H, W, rate);
+    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_src: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
+    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_src: px_out and py_out go together");
+    const int h = H / rate, w = W / rate;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = sn_check_device(src, "warp_rev_bundle2_src: src", st);
+    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_src: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_src: workspace", st);
+    if (rc) return rc;
+    Prof* prof = static_cast<Prof*>(profp);
+
+    bool rec = prof && prof->begin(st);
+    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
+    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
+    SN_LAUNCH_CHECK("map_shrink_kernel");
+
+    SrcRemapArgs a;
+    a.SH = SH; a.SW = SW; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
+    a.fW = (float)W; a.fH = (float)H;
+    a.sx = (float)((double)SW / (double)W); a.cx = (float)(0.5 * (double)SW / (double)W - 0.5);
+    a.sy = (float)((double)SH / (double)H); a.cy = (float)(0.5 * (double)SH / (double)H - 0.5);
+    a.xscale = (double)w / SW; a.yscale = (double)h / SH;
+    a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
+    // algorithmic bytes: the frame gathered once, written once, the two small maps
+    const double bytes = (double)N * (2.0 * SH * SW * C + 8.0 * h * w);
+    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
+    rec = prof && prof->begin(st);
+    if (remap_vec4_enabled() && C == 3 && SW % 4 == 0 && aligned) {
+        const int items = SW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
+        remap_src4_kernel<<<dim3(cdiv(items, threads), SH, N), threads, 0, st>>>(src, a, workspace, out, black_count, px_out, py_out);
+        if (rec) prof->end(st, PK_KERNEL_REMAP_SRC4, 0.0, bytes);
+        SN_LAUNCH_CHECK("remap_src4_kernel");
+        return STABNET_OK;
+    }
+    const int threads = SW >= 256 ? 256 : ((SW + 63) & ~63);
+    remap_src_kernel<<<dim3(cdiv(SW, threads), SH, N), threads, 0, st>>>(src, a, workspace, out, black_count, px_out, py_out);
+    if (rec) prof->end(st, PK_KERNEL_REMAP_SRC, 0.0, bytes);
+    SN_LAUNCH_CHECK("remap_src_kernel");
     return STABNET_OK;
 }
 

@@ -271,14 +271,29 @@ class ClipPipeline:
     ingest=FrameIngest: the clip is the RAW one -- run(frames_u8, ...), uint8 [src_h,src_w,C] frames of any size as read from the
     video.  A slot then uploads ONE uint8 frame at source size, and the slot's frame graph starts with the ingest launches
     (csrc/ingest.hip: grey conversion + Pillow resize into the stream's staging buffer; cv2.resize of the colour frame, which the
-    remap then reads).  The host converts nothing."""
+    remap then reads).  The host converts nothing.
 
-    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None):
+    output="source" (needs ingest): the frame that is kept is the frame AS READ, warped at its own size by the network-size maps
+    (csrc/remap.hip, stabnet_warp_rev_bundle2_src) -- the slot's graph then has no colour resize and remaps the upload slot itself.
+    "bgr" is uint8 [src_h,src_w,3] ([src_h,src_w] for a grey source, colour=False) and "jpeg" its encoding; all_black_src (int32
+    [src_h,src_w], zeroed by run) counts per pixel the frames that did not cover it, for warp.max_inscribed_rect.  "output", the maps
+    and the stream's all_black stay at the network's size.  The default, "network", is the reference's order: resize, then remap."""
+
+    def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
+                 output: str = "network"):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
             raise _lib.StabnetError("ClipPipeline: slots must be >= 2")
+        if output not in ("network", "source"):
+            raise _lib.StabnetError("ClipPipeline: output must be 'network' or 'source', got %r" % (output,))
+        if output == "source":
+            if ingest is None:
+                raise _lib.StabnetError("ClipPipeline: output='source' needs ingest=FrameIngest: the raw frame must lie on the device")
+            if not colour and ingest.C != 1:
+                raise _lib.StabnetError("ClipPipeline: output='source' with colour=False needs a grey source, the ingest reads %d channels" % ingest.C)
         self.st, self.colour, self.slots, self.rate = stream, colour, slots, rate
+        self.src_out = output == "source"
         dev = stream.reg.device
         H, W = stream.H, stream.W
         self.dev = dev
@@ -297,7 +312,13 @@ class ClipPipeline:
             self.d_grey = [on((1, H, W), torch.float32) for _ in range(slots)]
         self.h_out = [pin((H, W), torch.uint8) for _ in range(slots)]
         self.d_out = [on((H, W), torch.uint8) for _ in range(slots)]
-        if colour:
+        if self.src_out:
+            # the warped frame has the source's shape; h_warp drops the channel axis of a grey source
+            self.h_warp = [pin(src if ingest.C == 3 else src[:2], torch.uint8) for _ in range(slots)]
+            self.d_warp = [on((1,) + src, torch.uint8) for _ in range(slots)]
+            self.remap_ws = on((2 * (H // rate) * (W // rate),), torch.float32)
+            self.all_black_src = torch.zeros(src[:2], dtype=torch.int32, device=dev)
+        elif colour:
             if ingest is None:
                 self.h_bgr = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_bgr = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
@@ -307,10 +328,10 @@ class ClipPipeline:
         self.enc = None
         if jpeg is not None:
             from .mjpeg import MjpegEncoder
-            C = 3 if colour else 1
-            self.enc = MjpegEncoder(H, W, C, device=dev, **jpeg)
+            eh, ew, C = (ingest.sh, ingest.sw, ingest.C) if self.src_out else (H, W, 3 if colour else 1)
+            self.enc = MjpegEncoder(eh, ew, C, device=dev, **jpeg)
             mb = self.enc.max_bytes
-            self.jpeg_chunk = min(mb, (H * W * C // 4 + 4095) & ~4095)
+            self.jpeg_chunk = min(mb, (eh * ew * C // 4 + 4095) & ~4095)
             self.d_jpeg = [on((1, mb), torch.uint8) for _ in range(slots)]
             self.d_jlen = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(slots)]
             self.h_jpeg = [pin((mb,), torch.uint8) for _ in range(slots)]
@@ -329,18 +350,24 @@ class ClipPipeline:
         if self.ingest is not None:
             # cvt_img2train (config.py:6-21) and cv2.resize (deploy_bundle.py:303) of the raw frame in the upload slot
             self.ingest.grey(self.d_u8[k], out=st.cur)
-            if self.colour:
+            if self.colour and not self.src_out:
                 self.ingest.colour(self.d_u8[k], out=self.d_bgr[k])
             st._enqueue()
         else:
             st._enqueue(cur=self.d_grey[k])                  # the frame reads the upload slot itself: no staging copy
         # cvt_train2img (deploy_bundle.py:75)
         _lib.call("stabnet_cvt_train2img", ptr(st.out_img), ptr(self.d_out[k]), H * W, stream_ptr(self.dev), device=self.dev)
-        if self.colour:
+        if self.src_out:
+            # the raw frame in the upload slot, warped at its own size by the network-size maps; coverage counted on the way
+            ing = self.ingest
+            _lib.call("stabnet_warp_rev_bundle2_src", ptr(self.d_u8[k]), 1, ing.sh, ing.sw, ing.C, ing.sw * ing.C, ptr(st.x_map), ptr(st.y_map),
+                      H, W, self.rate, ptr(self.d_warp[k]), ptr(self.all_black_src), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
+                      device=self.dev)
+        elif self.colour:
             _lib.call("stabnet_warp_rev_bundle2", ptr(self.d_bgr[k]), ptr(st.x_map), ptr(st.y_map), 1, H, W, 3, self.rate,
                       ptr(self.d_warp[k]), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), device=self.dev)
         if self.enc is not None:
-            self.enc.encode(self.d_warp[k] if self.colour else self.d_out[k], out=self.d_jpeg[k], nbytes=self.d_jlen[k])
+            self.enc.encode(self.d_warp[k] if (self.colour or self.src_out) else self.d_out[k], out=self.d_jpeg[k], nbytes=self.d_jlen[k])
         if maps:
             self.d_maps[0][k].copy_(st.x_map.view(H, W)); self.d_maps[1][k].copy_(st.y_map.view(H, W))
             self.d_maps[2][k].copy_(st.black.view(H, W))
@@ -362,7 +389,7 @@ class ClipPipeline:
         r = {"t": t}
         if raw:
             r["output"] = self.h_out[slot].numpy()
-            if self.colour:
+            if self.colour or self.src_out:
                 r["bgr"] = self.h_warp[slot].numpy()
         if self.enc is not None:
             n = int(self.h_jlen[slot][0])
@@ -397,6 +424,8 @@ class ClipPipeline:
             if self.ingest is not None:
                 first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.uint8)).to(self.dev)
                 st.start_u8(first, self.ingest)
+                if self.src_out:
+                    self.all_black_src.zero_()
             else:
                 first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.float32)).to(self.dev)
                 st.start(first[None])
@@ -440,8 +469,8 @@ class ClipPipeline:
                 self.s_out.wait_event(self.ev_run[k])
                 if raw:
                     self.h_out[k].copy_(self.d_out[k], non_blocking=True)
-                    if self.colour:
-                        self.h_warp[k].copy_(self.d_warp[k].view(H, W, 3), non_blocking=True)
+                    if self.colour or self.src_out:
+                        self.h_warp[k].copy_(self.d_warp[k].view(self.h_warp[k].shape), non_blocking=True)
                 if self.enc is not None:
                     self.h_jlen[k].copy_(self.d_jlen[k], non_blocking=True)
                     self.h_jpeg[k][:self.jpeg_chunk].copy_(self.d_jpeg[k][0, :self.jpeg_chunk], non_blocking=True)

@@ -122,6 +122,69 @@ def warpRevBundle2(img: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, 
     return (out, px, py) if return_maps else out
 
 
+def _check_src_u8(u8, what):
+    """uint8 GPU frames [N,SH,SW,C] / [SH,SW,C] / [SH,SW] -> (tensor [N,SH,SW,C] with dense pixels, row stride in bytes, the shape to
+    hand back).  Rows may be strided (a view of a wider buffer is read where it lies), as in ingest.FrameIngest._check."""
+    if not isinstance(u8, torch.Tensor) or not u8.is_cuda:
+        raise _lib.StabnetError("%s: expected a uint8 tensor on the GPU (there is no CPU fallback)" % what)
+    if u8.dtype != torch.uint8:
+        raise _lib.StabnetError("%s: expected uint8, got %s" % (what, u8.dtype))
+    shape = tuple(u8.shape)
+    if u8.dim() == 2:
+        u8 = u8[None, :, :, None]
+    elif u8.dim() == 3:
+        u8 = u8[None]
+    if u8.dim() != 4 or u8.shape[3] not in (1, 3) or min(u8.shape) < 1:
+        raise _lib.StabnetError("%s: expected [N, SH, SW, C] / [SH, SW, C] / [SH, SW] with C = 3 (BGR) or 1 (grey), got %s" % (what, list(shape)))
+    n, sh, sw, c = u8.shape
+    dense = u8.stride(3) == 1 and u8.stride(2) == c and u8.stride(1) >= sw * c and (n == 1 or u8.stride(0) == sh * u8.stride(1))
+    if not dense:
+        u8 = u8.contiguous()
+    return u8, u8.stride(1), shape
+
+
+def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, black_count: torch.Tensor = None,
+                       out: torch.Tensor = None, return_maps: bool = False, prof=None):
+    """warpRevBundle2 at SOURCE resolution (csrc/remap.hip, stabnet_warp_rev_bundle2_src): the frame as read -- uint8 [N,SH,SW,C] /
+    [SH,SW,C] / [SH,SW], any size, rows may be strided -- remapped by the network-size maps x_map, y_map [N,H,W(,1)] / [H,W].
+    -> uint8 of src_u8's shape (with return_maps: (out, px, py), the float32 [N,SH,SW] source-pixel coordinates).
+    black_count: optional int32 [N,SH,SW] (or [SH,SW] for one frame), += 1 where the frame does not cover the pixel -- what
+    max_inscribed_rect reads.  out: optional contiguous uint8 tensor of the result's size.  Nothing synchronises."""
+    what = "warpRevBundle2_src"
+    u8, stride, shape = _check_src_u8(src_u8, what)
+    N, SH, SW, C = u8.shape
+    dev = u8.device
+    xm, ym = dev_f32(x_map, "x_map"), dev_f32(y_map, "y_map")
+    if xm.device != dev or ym.device != dev:
+        raise _lib.StabnetError("%s: maps on %s / %s, frame on %s" % (what, xm.device, ym.device, dev))
+    ms = tuple(xm.shape)
+    if xm.dim() == 4 and ms[3] == 1:
+        ms = ms[:3]
+    elif xm.dim() == 3 and ms[2] == 1 and ms[0] != N:
+        ms = (1,) + ms[:2]
+    elif xm.dim() == 2:
+        ms = (1,) + ms
+    if len(ms) != 3 or ms[0] != N or ym.numel() != xm.numel():
+        raise _lib.StabnetError("%s: maps must be [%d, H, W] like the frames' batch, got %s and %s" % (what, N, list(xm.shape), list(ym.shape)))
+    H, W = ms[1], ms[2]
+    if rate < 1 or H // rate < 1 or W // rate < 1:
+        raise _lib.StabnetError("%s: maps %dx%d leave nothing at rate %d" % (what, H, W, rate))
+    if out is None:
+        out = torch.empty((N, SH, SW, C), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * SH * SW * C or not out.is_contiguous():
+        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, SH, SW, C], dev))
+    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
+                                    or black_count.numel() != N * SH * SW or not black_count.is_contiguous()):
+        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, SH, SW], dev))
+    ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
+    px = empty((N, SH, SW), xm) if return_maps else None
+    py = empty((N, SH, SW), xm) if return_maps else None
+    _lib.call("stabnet_warp_rev_bundle2_src", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), ptr(out), ptr(black_count),
+              ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    res = out.view(shape)
+    return (res, px, py) if return_maps else res
+
+
 def cvt_train2img(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """deploy_bundle.py:75 on the device: uint8((x + 0.5) * 255), clipped; same shape as x."""
     x = dev_f32(x, "x")

@@ -16,6 +16,10 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     own arithmetic (csrc/ingest.hip: cv2.cvtColor + PIL BILINEAR resize + normalisation for the network, cv2.resize for the colour
     frame that is warped and written), so a 720p colour clip run at 288x512 keeps its colour outputs.  The default, --ingest host,
     converts on the host with a two-tap resize and keeps colour only for clips that already have the network's size.
+  * --output-size source (with --ingest device): the frame that is kept is the frame AS READ, warped at its own size by the
+    network-size maps (csrc/remap.hip, stabnet_warp_rev_bundle2_src) instead of the reference's resize-then-warp (deploy_bundle.py:303):
+    a 1080p clip run at 288x512 comes back as a 1080p <name>.avi, <name>_stable_bgr.npy and <name>_cut.*; <name>_stable.npy (the
+    network's grey output) and <name>_maps.npz keep the network's size.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -69,8 +73,19 @@ def build_parser():
                         'stabnet_amd.ingest.FrameIngest, the reference\'s cv2/PIL chain on the GPU for uint8 clips of any size')
     p.add_argument('--gray-weights', default='cv3', choices=['cv3', 'cv4'],
                    help='--ingest device: fixed-point BGR2GRAY weights of OpenCV 3 (the reference\'s era) or OpenCV 4')
+    p.add_argument('--output-size', default='network', choices=['network', 'source'],
+                   help='size of the frames that are written: network = --height x --width, the frame resized and then warped as the '
+                        'reference does; source (needs --ingest device) = the frame as read, warped at its own size by the network-size maps')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.output_size == 'source' and args.ingest != 'device':
+        p.error('--output-size source needs --ingest device: the frame as read must lie on the GPU')
+    return args
 
 
 def grey_train(frame, H, W):
@@ -126,10 +141,11 @@ def jpeg_options(args):
     return dict(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
 
 
-def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None):
+def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
-    uploaded and converted on the GPU inside the step."""
+    uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
+    raw frame is warped at its own size and its coverage counted there."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
@@ -146,7 +162,10 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
         r = stream.step_u8(cur, ing) if ing is not None else stream.step(cur)     # one sess.run-equivalent
         torch.cuda.synchronize()
         tot_time += time.time() - start
-        if ing is not None and ing.C == 3:
+        if black_src is not None:
+            # where the reference resizes the colour frame down and warps it (deploy_bundle.py:303): the frame as read, warped as it is
+            colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src).cpu().numpy())
+        elif ing is not None and ing.C == 3:
             # cv2.resize of the colour frame (deploy_bundle.py:303), then warpRevBundle2, both on the device
             colour_out.append(warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map']).cpu().numpy())
         elif ing is None and is_colour(clip[t], H, W):
@@ -156,7 +175,7 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
         net_output = ((r['output'][0, :, :, 0].cpu().numpy() + 0.5) * 255).clip(0, 255).astype(np.uint8)
         frames_out.append(net_output)
         if jpeg_sink is not None:                                             # the frame that is kept, compressed on the device
-            kept = colour_out[-1] if (ing.C == 3 if ing is not None else is_colour(clip[t], H, W)) else net_output
+            kept = colour_out[-1] if (black_src is not None or (ing.C == 3 if ing is not None else is_colour(clip[t], H, W))) else net_output
             jpeg_sink(enc.encode_bytes(torch.from_numpy(np.ascontiguousarray(kept)).to(dev))[0])
         xmaps.append(r['x_map'][0, :, :, 0].cpu().numpy()); ymaps.append(r['y_map'][0, :, :, 0].cpu().numpy())
         blacks.append(r['black_pix'][0].cpu().numpy().astype(np.uint8))
@@ -167,7 +186,7 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     return length, tot_time
 
 
-def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None):
+def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included."""
     from stabnet_amd.deploy import ClipPipeline
@@ -182,7 +201,7 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
 
     def sink(r):                                                              # views of pinned staging memory: copy out
         frames_out.append(r['output'].copy())
-        if colour:
+        if colour or source:
             colour_out.append(r['bgr'].copy())
         if jpeg_sink is not None:
             jpeg_sink(bytes(r['jpeg']))
@@ -191,18 +210,21 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
             print('length: ' + str(len(frames_out)))
 
     start = time.time()
+    black_src = None
     if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
-        ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing).run(clip, sink=sink, maps=True)
+        pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network')
+        pipe.run(clip, sink=sink, maps=True)
+        black_src = pipe.all_black_src if source else None
     else:
         ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
     tot_time = time.time() - start
     if frames_out:
         print('fps={}'.format(len(frames_out) / tot_time))
-    return len(frames_out), tot_time
+    return len(frames_out), tot_time, black_src
 
 
 def main():
-    args = build_parser().parse_args()
+    args = parse_args()
     import torch
     from stabnet_amd import synthetic, warp
     from stabnet_amd.config import Config
@@ -266,7 +288,7 @@ def main():
         frames_out, xmaps, ymaps, blacks, colour_out = [], [], [], [], []
         stem = os.path.join(out_dir, os.path.splitext(os.path.basename(name))[0])
         writer, enc, fps = None, None, fps_of.get(name, args.fps)
-        ing = None
+        ing, black_src = None, None          # black_src: coverage at source size (--output-size source), int32 on the device
         try:
             if args.ingest == 'device':
                 shp = np.shape(clip[0])
@@ -279,23 +301,34 @@ def main():
                 else:
                     print('note: --ingest device reads uint8 frames; this clip is %s %s: converted on the host as with --ingest host'
                           % (np.asarray(clip[0]).dtype, list(shp)))
+                    if args.output_size == 'source':
+                        print('note: --output-size source needs the uint8 frame on the GPU; this clip is written at the network\'s size')
+            source = args.output_size == 'source' and ing is not None
+            if source:
+                black_src = torch.zeros((ing.sh, ing.sw), dtype=torch.int32, device=dev)
+                print('note: --output-size source: frames are written at %dx%d, warped at that size by the %dx%d maps' % (ing.sw, ing.sh, W, H))
             if args.mjpg:
                 from stabnet_amd.avi import AviMjpegWriter
                 from stabnet_amd.mjpeg import MjpegEncoder
-                if ing is not None:                  # deploy_bundle.py:215: the cv2-resized first frame
+                if source:                           # deploy_bundle.py:215 at the frame's own size: cv2.resize is the identity there
+                    first = np.ascontiguousarray(clip[0], dtype=np.uint8)
+                    first = first[..., 0] if first.ndim == 3 and first.shape[2] == 1 else first
+                elif ing is not None:                # deploy_bundle.py:215: the cv2-resized first frame
                     f0 = torch.from_numpy(np.ascontiguousarray(clip[0], dtype=np.uint8)).to(dev)
                     first = (ing.colour(f0)[0] if ing.C == 3 else ((ing.grey(f0)[0] + 0.5) * 255).round().clamp(0, 255).to(torch.uint8)).cpu().numpy()
                 else:
                     first = first_frame_u8(clip, H, W)
-                enc = MjpegEncoder(H, W, 3 if first.ndim == 3 else 1, device=dev, **jpeg_options(args))
-                writer = AviMjpegWriter(stem + '.avi', W, H, fps)
+                oh, ow = first.shape[:2]             # the network's size, or the source's with --output-size source
+                enc = MjpegEncoder(oh, ow, 3 if first.ndim == 3 else 1, device=dev, **jpeg_options(args))
+                writer = AviMjpegWriter(stem + '.avi', ow, oh, fps)
                 writer.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])          # deploy_bundle.py:215
             sink = writer.write if writer is not None else None
             if args.pipeline:
-                length, tot_time = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
-                                                 jpeg_options(args) if args.mjpg else None, ing)
+                length, tot_time, pipe_black = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
+                                                             jpeg_options(args) if args.mjpg else None, ing, source)
+                black_src = pipe_black if source else None
             else:
-                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing)
+                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -311,7 +344,8 @@ def main():
                 np.savez_compressed(stem + '_maps.npz', x_map=np.stack(xmaps), y_map=np.stack(ymaps), black=np.stack(blacks))
                 print('wrote', stem + '_stable.npy')
                 # max-inscribed black-free rectangle over the whole clip (deploy_bundle.py:344-371), searched on the device
-                ans, area = warp.max_inscribed_rect(stream.all_black[0])
+                # (--output-size source: over the coverage counted at source size, and the frames are cut there)
+                ans, area = warp.max_inscribed_rect(black_src if black_src is not None and colour_out else stream.all_black[0])
                 if ans:
                     src = np.stack(colour_out) if colour_out else np.stack(frames_out)
                     cut = src[:, ans[0]:ans[2] + 1, ans[1]:ans[3] + 1]

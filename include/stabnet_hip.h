@@ -505,6 +505,25 @@ int stabnet_adam_step(float* params, const float* grads, const float* grads2, fl
 int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const float* y_map, int N, int H, int W, int C,
                              int rate, unsigned char* out, float* workspace, float* px_out, float* py_out, void* stream);
 
+/* The same remap at SOURCE resolution: the frame as read, of any size, warped by the network-size maps (nothing in the reference:
+ * it resizes the colour frame down to the network's size first, deploy_bundle.py:303).  src uint8 [N,SH,SW,C], C = 3 BGR or 1 grey,
+ * rows row_stride_bytes apart (>= SW*C), frames SH*row_stride_bytes apart, any base alignment; nothing outside
+ * [src, src + (SH-1)*stride + SW*C) of a frame is read.  x_map, y_map [N,H,W] normalised, h = H/rate, w = W/rate:
+ *   small = cv2.resize(map, (w, h));  big = cv2.resize(small, (SW, SH));  ux = (big_x + 1)/2*W, uy = (big_y + 1)/2*H;
+ *   px = ux*sx + cx, py = uy*sy + cy  (float32 multiply, then add; sx = float32(SW/W), cx = float32(0.5*SW/W - 0.5), likewise y, from double:
+ *   cv2's half-pixel convention -- the normalised coordinate counts pixel indices, so cx is what keeps an identity mesh in place);
+ *   out = cv2.remap(src, px, py, INTER_LINEAR), BORDER_CONSTANT 0, the fixed-point path of stabnet_warp_rev_bundle2.
+ * With SH, SW == H, W the results are stabnet_warp_rev_bundle2's bit for bit.  out uint8 [N,SH,SW,C] dense.  black_count (optional,
+ * int32 [N,SH,SW], what stabnet_crop_search reads): += 1 where the coordinate rounded to 1/32 px lies outside the frame
+ * (qx < 0 || qx > 32*(SW-1) || qy < 0 || qy > 32*(SH-1); NaN maps too) -- a read-modify-write of black pixels only, by the pixel's
+ * own thread.  px_out/py_out optional [N,SH,SW], both or neither.  workspace 2*N*h*w floats.  SH, SW in 1..32767 (the remap's
+ * 16-bit pixel index).  Two launches; nothing allocates, synchronises or copies from the host.  STABNET_REMAP_VEC4=0 selects the
+ * one-pixel-per-thread kernel, as in stabnet_warp_rev_bundle2. */
+int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                 const float* x_map, const float* y_map, int H, int W, int rate,
+                                 unsigned char* out, int* black_count, float* workspace,
+                                 float* px_out, float* py_out, void* stream, void* prof);
+
 /* cvt_train2img (deploy_bundle.py:75): the network's grey output back to 8 bits, out[i] = uint8((x[i] + 0.5) * 255) clipped to
  * [0, 255].  x float [n], out uint8 [n].  The 16-byte path needs both pointers 16-byte aligned (any alignment is accepted). */
 int stabnet_cvt_train2img(const float* x, unsigned char* out, long n, void* stream);

@@ -12,7 +12,14 @@ colour uint8 frames) in, stabilised colour frame + the network's grey output bac
             host beforehand) against ClipPipeline(ingest=FrameIngest): ONE uint8 BGR frame uploaded at the source size
             (--src-height / --src-width, default the network's) and converted in the frame graph (csrc/ingest.hip); the two
             alternate, each repeated --repeats times, fps, host_wait_s and bytes uploaded per frame beside each
-One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg | --ingest]"""
+  --ingest --output-size source   instead of the legs above: three routes from a raw uint8 BGR clip of --src-height x --src-width to a
+            stabilised clip, every one through ClipPipeline(ingest=FrameIngest): (a) network_size: the network at --height x --width,
+            frames kept at that size (resize, then remap); (b) source_size: the same network, output="source" -- the raw frame warped at
+            its own size by the network-size maps (csrc/remap.hip, stabnet_warp_rev_bundle2_src); (c) network_at_source_size: the
+            network itself run at the source's size, the only other way to frames of that size.  With --jpeg every graph also encodes
+            the kept frame and only the compressed frame is downloaded.  The three alternate, each repeated --repeats times; fps,
+            host_wait_s and the bytes that cross PCIe per frame beside each
+One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg | --ingest [--output-size source [--jpeg]]]"""
 import argparse
 import json
 import os
@@ -38,6 +45,7 @@ ap.add_argument("--ingest", action="store_true")
 ap.add_argument("--src-height", type=int, default=None)
 ap.add_argument("--src-width", type=int, default=None)
 ap.add_argument("--jpeg-quality", type=int, default=75)
+ap.add_argument("--output-size", default="network", choices=["network", "source"])
 a = ap.parse_args()
 H, W, T = a.height, a.width, a.frames
 dev = torch.device("cuda", 0)
@@ -162,6 +170,79 @@ def ingest_legs():
     f = legs["uploaded_at_network_size"]["fps"]
     out["uploaded_leg_spread"] = (max(f) - min(f)) / med(f)
 
+
+def source_legs():
+    """frames kept at the network's size / at the source's size by the source-size remap / by running the network at the source's size,
+    alternating in one process."""
+    from stabnet_amd.ingest import FrameIngest
+    sh, sw = a.src_height or H, a.src_width or W
+    src = synthetic.make_clip(sh, sw, 40, seed=1234).astype(np.float32)
+    g8 = ((src + 0.5) * 255).clip(0, 255)
+    raw40 = np.ascontiguousarray(np.stack([g8 * 0.8 + 20, g8, g8 * 0.65 + 60], -1).clip(0, 255).astype(np.uint8))
+
+    class Clip:                                                                   # T frames cycling through the 40 that exist
+        def __init__(self, n):
+            self.n = n
+
+        def __len__(self):
+            return self.n
+
+        def __getitem__(self, t):
+            return raw40[t % len(raw40)]
+
+    opts = dict(quality=a.jpeg_quality, subsampling="420") if a.jpeg else None
+    cfg_s = Config(height=sh, width=sw)
+    params_s = synthetic.make_params(cfg_s, seed=0, theta_scale=0.2)
+    small = lambda: StabNetStream(params, H, W, cfg, device=dev, use_graph=True)
+    pipes = {"network_size": ClipPipeline(small(), colour=True, slots=a.slots, jpeg=opts, ingest=FrameIngest(sh, sw, 3, H, W, device=dev)),
+             "source_size": ClipPipeline(small(), colour=True, slots=a.slots, jpeg=opts, ingest=FrameIngest(sh, sw, 3, H, W, device=dev),
+                                         output="source"),
+             "network_at_source_size": ClipPipeline(StabNetStream(params_s, sh, sw, cfg_s, device=dev, use_graph=True), colour=True, slots=a.slots,
+                                                    jpeg=opts, ingest=FrameIngest(sh, sw, 3, sh, sw, device=dev))}
+    kept = {"network_size": (H, W), "source_size": (sh, sw), "network_at_source_size": (sh, sw)}
+    net = {"network_size": (H, W), "source_size": (H, W), "network_at_source_size": (sh, sw)}
+    legs = {k: {"fps": [], "host_wait_s": [], "bytes_down_per_frame": [], "network": list(net[k]), "kept_frame": list(kept[k]),
+                "bytes_up_per_frame": sh * sw * 3} for k in pipes}
+    got = {k: (np.zeros(kept[k] + (3,), np.uint8), np.zeros(net[k], np.uint8), np.zeros(kept[k][0] * kept[k][1] * 3, np.uint8)) for k in pipes}
+    kw = {"raw": False} if a.jpeg else {}
+    def sink_of(name):
+        c, o, j = got[name]
+        def sink(r):                                                              # the consumer touches everything it was given
+            if "bgr" in r:
+                np.copyto(c, r["bgr"]); np.copyto(o, r["output"])
+            if "jpeg" in r:
+                j[:len(r["jpeg"])] = r["jpeg"]
+        return sink
+    for name, pipe in pipes.items():
+        pipe.run(Clip(min(T, 120)), sink=sink_of(name), **kw)                     # graph capture + warm-up
+    for _ in range(a.repeats):
+        for name, pipe in pipes.items():
+            t0 = time.perf_counter()
+            pipe.run(Clip(T), sink=sink_of(name), **kw)
+            dt = time.perf_counter() - t0
+            legs[name]["fps"].append((T - 1) / dt)
+            legs[name]["host_wait_s"].append(pipe.host_wait_s)
+            raw_bytes = 0 if a.jpeg else kept[name][0] * kept[name][1] * 3 + net[name][0] * net[name][1]
+            legs[name]["bytes_down_per_frame"].append(raw_bytes + getattr(pipe, "jpeg_bytes_down", 0) / (T - 1))
+    med = lambda v: sorted(v)[len(v) // 2]
+    out["source_legs"] = legs
+    out["source"] = [sh, sw]
+    out["jpeg"] = bool(a.jpeg)
+    out["source_size_over_network_at_source_size"] = med(legs["source_size"]["fps"]) / med(legs["network_at_source_size"]["fps"])
+    out["source_size_over_network_size"] = med(legs["source_size"]["fps"]) / med(legs["network_size"]["fps"])
+    for k in legs:
+        f = legs[k]["fps"]
+        legs[k]["spread"] = (max(f) - min(f)) / med(f)
+
+
+if a.output_size == "source" and not a.ingest:
+    ap.error("--output-size source goes with --ingest")
+
+if a.ingest and a.output_size == "source":
+    source_legs()
+    out["slots"] = a.slots
+    print(json.dumps(out))
+    sys.exit(0)
 
 if a.ingest:
     ingest_legs()
