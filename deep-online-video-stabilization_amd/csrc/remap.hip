@@ -6,14 +6,16 @@
 //                       (sum + 16384) >> 15), BORDER_CONSTANT 0 -- integer arithmetic, bit-exact against the oracle
 // Float32 op order of the two resizes as oracle/stabnet_oracle.py: cv_resize_linear_f32 (-ffp-contract=off).  HBM-bound:
 // per frame 8*H*W (maps in) + 3*H*W (frame, gathered) + 3*H*W (out) bytes.
+#include <cmath>
 #include <cstdlib>
 #include "common.h"
 #include "prof.h"
 
 struct Taps1D { int i0, i1; float w0, w1; };
 
-__device__ __forceinline__ Taps1D cv_taps(int d, int n_src, double scale) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
+// e: the destination position in pixel-edge units (pixel d covers [d, d + 1), its centre is d + 0.5)
+__device__ __forceinline__ Taps1D cv_taps_at(double e, int n_src, double scale) {
+    float f = (float)(e * scale - 0.5);
     int s = (int)floorf(f);
     f = f - (float)s;
     if (s < 0) { f = 0.f; s = 0; }
@@ -22,6 +24,8 @@ __device__ __forceinline__ Taps1D cv_taps(int d, int n_src, double scale) {
     t.i0 = s; t.i1 = min(s + 1, n_src - 1); t.w0 = 1.0f - f; t.w1 = f;
     return t;
 }
+
+__device__ __forceinline__ Taps1D cv_taps(int d, int n_src, double scale) { return cv_taps_at((double)d + 0.5, n_src, scale); }
 
 __device__ __forceinline__ float cv_resize_at(const float* __restrict__ src, int sw, const Taps1D& tx, const Taps1D& ty) {
     const float r0 = src[(size_t)ty.i0 * sw + tx.i0] * tx.w0 + src[(size_t)ty.i0 * sw + tx.i1] * tx.w1;
@@ -294,6 +298,106 @@ __global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __
     }
 }
 
+// ---- the same remap through a WINDOW of the stabilised frame: crop and zoom in the one gather ----
+// Output pixel (i, j) of OH x OW is the stabilised frame (SH x SW) sampled at the position, in pixel-edge units,
+//   ex = x0 + (j + 0.5) * (ww / OW),  ey = y0 + (i + 0.5) * (wh / OH)        (double; quotient, multiply, add)
+// and that position takes the place of d + 0.5 in the taps of the resize back up (cv_taps_at); from there on every step is
+// remap_src_kernel's.  With the whole-frame window (0, 0, SH, SW) at OH, OW == SH, SW, ex = j + 0.5 exactly: every bit is
+// stabnet_warp_rev_bundle2_src's; with an integer window at zoom 1, ex = x0 + j + 0.5 exactly: the slice of that result.
+// Coverage is counted at the OUTPUT pixel.  Grid = row segments x OH x N: the vertical taps are wave-uniform.
+struct WinRemapArgs {
+    SrcRemapArgs a;
+    int OH, OW;
+    double x0, y0, xstep, ystep;             // xstep = ww / OW, ystep = wh / OH
+};
+
+// grid (cdiv(OW, blockDim.x), OH, N): one output pixel per thread, any C, size, stride and alignment; byte loads and stores.
+__global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
+                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
+    if (x >= wa.OW) return;
+    const SrcRemapArgs& a = wa.a;
+    const int SH = a.SH, SW = a.SW, C = a.C;
+    const Taps1D tx = cv_taps_at(wa.x0 + ((double)x + 0.5) * wa.xstep, a.w, a.xscale);
+    const Taps1D ty = cv_taps_at(wa.y0 + ((double)y + 0.5) * wa.ystep, a.h, a.yscale);
+    const size_t hw = (size_t)a.h * a.w;
+    const SrcCoord c = remap_src_coord(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
+    const size_t pix = ((size_t)n * wa.OH + y) * wa.OW + x;
+    if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
+    const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
+    const int fx = c.qx & 31, fy = c.qy & 31;
+    int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+    if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
+    const unsigned char* im = src + (size_t)n * a.frame_stride;
+    const bool x0 = ix >= 0 && ix < SW, x1 = ix + 1 >= 0 && ix + 1 < SW, y0 = iy >= 0 && iy < SH, y1 = iy + 1 >= 0 && iy + 1 < SH;
+    for (int ch = 0; ch < C; ++ch) {
+        const int v00 = (x0 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)ix * C + ch] : 0;
+        const int v01 = (x1 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
+        const int v10 = (x0 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)ix * C + ch] : 0;
+        const int v11 = (x1 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
+        const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+        out[pix * C + ch] = (unsigned char)min(max(acc, 0), 255);
+    }
+    if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix] += 1;
+}
+
+// grid (cdiv(OW / 4, blockDim.x), OH, N): four consecutive OUTPUT pixels per thread, C == 3, OW % 4 == 0, out 4-byte aligned (px_out /
+// py_out 16-byte).  The source may have any width, stride and alignment: its taps come through remap_src_load6.
+__global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
+                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
+    if (x0 >= wa.OW) return;
+    const SrcRemapArgs& a = wa.a;
+    const int SH = a.SH, SW = a.SW;
+    const Taps1D ty = cv_taps_at(wa.y0 + ((double)y + 0.5) * wa.ystep, a.h, a.yscale);
+    const size_t hw = (size_t)a.h * a.w;
+    const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
+    const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
+    const unsigned char* im = src + (size_t)n * a.frame_stride;
+    const unsigned char* end = im + (size_t)(SH - 1) * a.row_stride + (size_t)SW * 3;
+    const size_t pix = ((size_t)n * wa.OH + y) * wa.OW + x0;
+    unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
+    float pxs[4], pys[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const Taps1D tx = cv_taps_at(wa.x0 + ((double)(x0 + e) + 0.5) * wa.xstep, a.w, a.xscale);
+        const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
+        pxs[e] = c.px; pys[e] = c.py;
+        const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
+        const int fx = c.qx & 31, fy = c.qy & 31;
+        int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
+        if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
+        const bool vx0 = ix >= 0 && ix < SW, vx1 = ix + 1 >= 0 && ix + 1 < SW, vy0 = iy >= 0 && iy < SH, vy1 = iy + 1 >= 0 && iy + 1 < SH;
+        // rows iy and iy + 1: 6 bytes from pixel max(ix, 0) on (ix == -1: the first three bytes are tap 1)
+        unsigned long long r0 = 0ull, r1 = 0ull;
+        const int cx = max(ix, 0);
+        if ((vx0 || vx1) && vy0) r0 = remap_src_load6(im + (size_t)iy * a.row_stride + (size_t)cx * 3, im, end);
+        if ((vx0 || vx1) && vy1) r1 = remap_src_load6(im + (size_t)(iy + 1) * a.row_stride + (size_t)cx * 3, im, end);
+        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                  // tap 0 out of frame on the left: what was loaded is tap 1
+        const unsigned long long m0 = vx0 ? 0xffffffull : 0ull, m1 = vx1 ? 0xffffff000000ull : 0ull;
+        r0 &= (vy0 ? (m0 | m1) : 0ull);
+        r1 &= (vy1 ? (m0 | m1) : 0ull);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int v00 = (int)((r0 >> (8 * ch)) & 0xff), v01 = (int)((r0 >> (24 + 8 * ch)) & 0xff);
+            const int v10 = (int)((r1 >> (8 * ch)) & 0xff), v11 = (int)((r1 >> (24 + 8 * ch)) & 0xff);
+            const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+            const unsigned o = (unsigned)min(max(acc, 0), 255);
+            const int byte = e * 3 + ch;
+            ob[byte >> 2] |= o << (8 * (byte & 3));
+        }
+        if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix + e] += 1;
+    }
+    unsigned* op = reinterpret_cast<unsigned*>(out + pix * 3);
+    op[0] = ob[0]; op[1] = ob[1]; op[2] = ob[2];
+    if (px_out != nullptr) {
+        *reinterpret_cast<float4*>(px_out + pix) = make_float4(pxs[0], pxs[1], pxs[2], pxs[3]);
+        *reinterpret_cast<float4*>(py_out + pix) = make_float4(pys[0], pys[1], pys[2], pys[3]);
+    }
+}
+
 // cvt_train2img (deploy_bundle.py:75): ((x + 0.5) * 255).astype(uint8), clipped to [0, 255] first (the network's grey output is a
 // bilinear blend of inputs in [-0.5, 0.5], so the clip only guards the cast).  4 pixels per thread, float4 in, one dword out.
 __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long n) {
@@ -390,6 +494,71 @@ int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW
     remap_src_kernel<<<dim3(cdiv(SW, threads), SH, N), threads, 0, st>>>(src, a, workspace, out, black_count, px_out, py_out);
     if (rec) prof->end(st, PK_KERNEL_REMAP_SRC, 0.0, bytes);
     SN_LAUNCH_CHECK("remap_src_kernel");
+    return STABNET_OK;
+}
+
+/* stabnet_warp_rev_bundle2_src through a window of the stabilised frame: out uint8 [N,OH,OW,C] dense, output pixel (i, j) = the
+ * stabilised frame at SH x SW sampled at the fractional position inside window = {y0, x0, wh, ww} (host memory, pixel-edge units,
+ * read during the call).  black_count, px_out/py_out: [N,OH,OW], at the OUTPUT pixel. */
+int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                 const float* x_map, const float* y_map, int H, int W, int rate,
+                                 const double* window, int OH, int OW,
+                                 unsigned char* out, int* black_count, float* workspace,
+                                 float* px_out, float* py_out, void* stream, void* profp) {
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_win: null pointer");
+    SN_REQUIRE(window != nullptr, "warp_rev_bundle2_win: null window");
+    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_win: C must be 1 (grey) or 3 (BGR), got %d", C);
+    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_win: batch %d outside 1..65535", N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
+               "warp_rev_bundle2_win: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
+    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "warp_rev_bundle2_win: output %dx%d outside 1..32767", OH, OW);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_win: maps %dx%d leave nothing at rate %d", H, W, rate);
+    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_win: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
+    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_win: px_out and py_out go together");
+    const double y0 = window[0], x0 = window[1], wh = window[2], ww = window[3];
+    SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
+               "warp_rev_bundle2_win: window (%g, %g, %g, %g) is not finite", y0, x0, wh, ww);
+    SN_REQUIRE(wh > 0.0 && ww > 0.0, "warp_rev_bundle2_win: window %g x %g is empty", wh, ww);
+    // (a centred ratio window may overshoot by a rounding error; the taps clamp at the border anyway)
+    SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
+               "warp_rev_bundle2_win: window (%g, %g, %g, %g) leaves the %dx%d frame", y0, x0, wh, ww, SH, SW);
+    const int h = H / rate, w = W / rate;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = sn_check_device(src, "warp_rev_bundle2_win: src", st);
+    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_win: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_win: workspace", st);
+    if (rc) return rc;
+    Prof* prof = static_cast<Prof*>(profp);
+
+    bool rec = prof && prof->begin(st);
+    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
+    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
+    SN_LAUNCH_CHECK("map_shrink_kernel");
+
+    WinRemapArgs wa;
+    SrcRemapArgs& a = wa.a;
+    a.SH = SH; a.SW = SW; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
+    a.fW = (float)W; a.fH = (float)H;
+    a.sx = (float)((double)SW / (double)W); a.cx = (float)(0.5 * (double)SW / (double)W - 0.5);
+    a.sy = (float)((double)SH / (double)H); a.cy = (float)(0.5 * (double)SH / (double)H - 0.5);
+    a.xscale = (double)w / SW; a.yscale = (double)h / SH;
+    a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
+    wa.OH = OH; wa.OW = OW; wa.x0 = x0; wa.y0 = y0; wa.xstep = ww / (double)OW; wa.ystep = wh / (double)OH;
+    // algorithmic bytes: the window of the frame gathered once, the output written once, the two small maps
+    const double bytes = (double)N * ((wh * ww + (double)OH * OW) * C + 8.0 * h * w);
+    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
+    rec = prof && prof->begin(st);
+    if (remap_vec4_enabled() && C == 3 && OW % 4 == 0 && aligned) {
+        const int items = OW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
+        remap_win4_kernel<<<dim3(cdiv(items, threads), OH, N), threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
+        if (rec) prof->end(st, PK_KERNEL_REMAP_WIN4, 0.0, bytes);
+        SN_LAUNCH_CHECK("remap_win4_kernel");
+        return STABNET_OK;
+    }
+    const int threads = OW >= 256 ? 256 : ((OW + 63) & ~63);
+    remap_win_kernel<<<dim3(cdiv(OW, threads), OH, N), threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
+    if (rec) prof->end(st, PK_KERNEL_REMAP_WIN, 0.0, bytes);
+    SN_LAUNCH_CHECK("remap_win_kernel");
     return STABNET_OK;
 }
 

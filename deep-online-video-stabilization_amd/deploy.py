@@ -277,10 +277,16 @@ class ClipPipeline:
     (csrc/remap.hip, stabnet_warp_rev_bundle2_src) -- the slot's graph then has no colour resize and remaps the upload slot itself.
     "bgr" is uint8 [src_h,src_w,3] ([src_h,src_w] for a grey source, colour=False) and "jpeg" its encoding; all_black_src (int32
     [src_h,src_w], zeroed by run) counts per pixel the frames that did not cover it, for warp.max_inscribed_rect.  "output", the maps
-    and the stream's all_black stay at the network's size.  The default, "network", is the reference's order: resize, then remap."""
+    and the stream's all_black stay at the network's size.  The default, "network", is the reference's order: resize, then remap.
+
+    window=(y0, x0, wh, ww) (warp.ratio_window / warp.fit_window), in pixel-edge units of the kept frame: borderless output.  The kept
+    frame is that window of the stabilised frame, zoomed to the kept frame's own size in the remap's one gather (csrc/remap.hip,
+    stabnet_warp_rev_bundle2_win, where the slot's graph calls the remap today) -- the frame, its JPEG and every buffer keep their
+    sizes.  all_black_win (int32, the kept frame's size, zeroed by run) counts per OUTPUT pixel the frames that did not cover it;
+    all_black_src is then not updated.  A pipeline that keeps no remapped frame (colour=False at the network's size) refuses it."""
 
     def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
-                 output: str = "network"):
+                 output: str = "network", window=None):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
@@ -294,6 +300,20 @@ class ClipPipeline:
                 raise _lib.StabnetError("ClipPipeline: output='source' with colour=False needs a grey source, the ingest reads %d channels" % ingest.C)
         self.st, self.colour, self.slots, self.rate = stream, colour, slots, rate
         self.src_out = output == "source"
+        self.window = None
+        if window is not None:
+            if output != "source" and not colour:
+                raise _lib.StabnetError("ClipPipeline: window needs a remapped frame to cut (colour=True or output='source'); "
+                                        "this pipeline keeps the network's grey output")
+            try:
+                win = tuple(float(v) for v in window)
+            except (TypeError, ValueError):
+                win = ()
+            kh, kw = (ingest.sh, ingest.sw) if output == "source" else (stream.H, stream.W)
+            if len(win) != 4 or not all(np.isfinite(win)) or win[2] <= 0 or win[3] <= 0 or min(win[:2]) < -1e-6 \
+                    or win[0] + win[2] > kh + 1e-6 or win[1] + win[3] > kw + 1e-6:
+                raise _lib.StabnetError("ClipPipeline: window must be (y0, x0, wh, ww) inside the %dx%d kept frame, got %r" % (kh, kw, window))
+            self.window = (ctypes.c_double * 4)(*win)
         dev = stream.reg.device
         H, W = stream.H, stream.W
         self.dev = dev
@@ -325,6 +345,8 @@ class ClipPipeline:
             self.h_warp = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_warp = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
             self.remap_ws = on((2 * (H // rate) * (W // rate),), torch.float32)
+        if self.window is not None:
+            self.all_black_win = torch.zeros(src[:2] if self.src_out else (H, W), dtype=torch.int32, device=dev)
         self.enc = None
         if jpeg is not None:
             from .mjpeg import MjpegEncoder
@@ -357,7 +379,16 @@ class ClipPipeline:
             st._enqueue(cur=self.d_grey[k])                  # the frame reads the upload slot itself: no staging copy
         # cvt_train2img (deploy_bundle.py:75)
         _lib.call("stabnet_cvt_train2img", ptr(st.out_img), ptr(self.d_out[k]), H * W, stream_ptr(self.dev), device=self.dev)
-        if self.src_out:
+        if self.window is not None:
+            # the window of the stabilised frame, zoomed to the kept frame's size in the remap's gather; coverage counted at the output
+            if self.src_out:
+                frame, (sh, sw, C) = self.d_u8[k], (self.ingest.sh, self.ingest.sw, self.ingest.C)
+            else:
+                frame, (sh, sw, C) = self.d_bgr[k], (H, W, 3)
+            _lib.call("stabnet_warp_rev_bundle2_win", ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
+                      self.window, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
+                      device=self.dev)
+        elif self.src_out:
             # the raw frame in the upload slot, warped at its own size by the network-size maps; coverage counted on the way
             ing = self.ingest
             _lib.call("stabnet_warp_rev_bundle2_src", ptr(self.d_u8[k]), 1, ing.sh, ing.sw, ing.C, ing.sw * ing.C, ptr(st.x_map), ptr(st.y_map),
@@ -429,6 +460,8 @@ class ClipPipeline:
             else:
                 first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.float32)).to(self.dev)
                 st.start(first[None])
+            if self.window is not None:
+                self.all_black_win.zero_()
         pending = [None] * K                                  # frame number whose results sit in (or are on their way to) slot k
         for t in range(1, n):
             k = t % K

@@ -7,6 +7,8 @@
 Tensors are torch CUDA(HIP) float32, NHWC.  No CPU fallback."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -143,17 +145,8 @@ def _check_src_u8(u8, what):
     return u8, u8.stride(1), shape
 
 
-def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, black_count: torch.Tensor = None,
-                       out: torch.Tensor = None, return_maps: bool = False, prof=None):
-    """warpRevBundle2 at SOURCE resolution (csrc/remap.hip, stabnet_warp_rev_bundle2_src): the frame as read -- uint8 [N,SH,SW,C] /
-    [SH,SW,C] / [SH,SW], any size, rows may be strided -- remapped by the network-size maps x_map, y_map [N,H,W(,1)] / [H,W].
-    -> uint8 of src_u8's shape (with return_maps: (out, px, py), the float32 [N,SH,SW] source-pixel coordinates).
-    black_count: optional int32 [N,SH,SW] (or [SH,SW] for one frame), += 1 where the frame does not cover the pixel -- what
-    max_inscribed_rect reads.  out: optional contiguous uint8 tensor of the result's size.  Nothing synchronises."""
-    what = "warpRevBundle2_src"
-    u8, stride, shape = _check_src_u8(src_u8, what)
-    N, SH, SW, C = u8.shape
-    dev = u8.device
+def _check_maps(x_map, y_map, N, dev, rate, what):
+    """The network-size maps [N,H,W(,1)] / [H,W] of a batch of N frames on `dev` -> (x_map, y_map as float32 tensors, H, W)."""
     xm, ym = dev_f32(x_map, "x_map"), dev_f32(y_map, "y_map")
     if xm.device != dev or ym.device != dev:
         raise _lib.StabnetError("%s: maps on %s / %s, frame on %s" % (what, xm.device, ym.device, dev))
@@ -169,6 +162,21 @@ def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     H, W = ms[1], ms[2]
     if rate < 1 or H // rate < 1 or W // rate < 1:
         raise _lib.StabnetError("%s: maps %dx%d leave nothing at rate %d" % (what, H, W, rate))
+    return xm, ym, H, W
+
+
+def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, black_count: torch.Tensor = None,
+                       out: torch.Tensor = None, return_maps: bool = False, prof=None):
+    """warpRevBundle2 at SOURCE resolution (csrc/remap.hip, stabnet_warp_rev_bundle2_src): the frame as read -- uint8 [N,SH,SW,C] /
+    [SH,SW,C] / [SH,SW], any size, rows may be strided -- remapped by the network-size maps x_map, y_map [N,H,W(,1)] / [H,W].
+    -> uint8 of src_u8's shape (with return_maps: (out, px, py), the float32 [N,SH,SW] source-pixel coordinates).
+    black_count: optional int32 [N,SH,SW] (or [SH,SW] for one frame), += 1 where the frame does not cover the pixel -- what
+    max_inscribed_rect reads.  out: optional contiguous uint8 tensor of the result's size.  Nothing synchronises."""
+    what = "warpRevBundle2_src"
+    u8, stride, shape = _check_src_u8(src_u8, what)
+    N, SH, SW, C = u8.shape
+    dev = u8.device
+    xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
     if out is None:
         out = torch.empty((N, SH, SW, C), dtype=torch.uint8, device=dev)
     elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * SH * SW * C or not out.is_contiguous():
@@ -182,6 +190,71 @@ def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     _lib.call("stabnet_warp_rev_bundle2_src", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), ptr(out), ptr(black_count),
               ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
     res = out.view(shape)
+    return (res, px, py) if return_maps else res
+
+
+def ratio_window(SH: int, SW: int, r: float):
+    """(y0, x0, wh, ww): the centred window of an SH x SW frame that keeps `r` of each side, 0 < r <= 1."""
+    r = float(r)
+    if not 0.0 < r <= 1.0:
+        raise ValueError("ratio_window: r must lie in (0, 1], got %r" % (r,))
+    wh, ww = SH * r, SW * r
+    return ((SH - wh) / 2, (SW - ww) / 2, wh, ww)
+
+
+def fit_window(rect, OH: int, OW: int):
+    """(y0, x0, wh, ww): the largest window of the output's aspect ratio OW : OH inside rect = [i0, j0, i1, j1] (inclusive, as
+    max_inscribed_rect returns it), centred in it.  Plain Python floats."""
+    i0, j0, i1, j1 = (int(v) for v in rect)
+    rh, rw = i1 - i0 + 1, j1 - j0 + 1
+    if rh < 1 or rw < 1 or OH < 1 or OW < 1:
+        raise ValueError("fit_window: empty rectangle %r or output %dx%d" % (list(rect), OH, OW))
+    if rw * OH > rh * OW:                                # the rectangle is wider than the output: its height binds
+        wh, ww = float(rh), rh * OW / OH
+    else:
+        wh, ww = rw * OH / OW, float(rw)
+    return (i0 + (rh - wh) / 2, j0 + (rw - ww) / 2, wh, ww)
+
+
+def _check_window(window, what):
+    try:
+        win = tuple(float(v) for v in window)
+    except (TypeError, ValueError):
+        win = ()
+    if len(win) != 4:
+        raise _lib.StabnetError("%s: window must be four numbers (y0, x0, wh, ww), got %r" % (what, window))
+    return (ctypes.c_double * 4)(*win)
+
+
+def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, window, out_size=None, rate: int = 4,
+                       black_count: torch.Tensor = None, out: torch.Tensor = None, return_maps: bool = False, prof=None):
+    """warpRevBundle2_src through a WINDOW of the stabilised frame (csrc/remap.hip, stabnet_warp_rev_bundle2_win): crop and zoom in the
+    one gather.  window = (y0, x0, wh, ww) in pixel-edge units of the stabilised frame at the source's size (the whole frame is
+    (0, 0, SH, SW); ratio_window / fit_window make one); out_size = (OH, OW), default the source's size.
+    -> uint8 [N,OH,OW,C] / [OH,OW,C] / [OH,OW] after src_u8's layout (with return_maps: (out, px, py), float32 [N,OH,OW]).
+    black_count: optional int32 [N,OH,OW], += 1 where the frame does not cover the OUTPUT pixel.  Nothing synchronises."""
+    what = "warpRevBundle2_win"
+    u8, stride, shape = _check_src_u8(src_u8, what)
+    N, SH, SW, C = u8.shape
+    dev = u8.device
+    win = _check_window(window, what)
+    OH, OW = (SH, SW) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
+    if OH < 1 or OW < 1:
+        raise _lib.StabnetError("%s: out_size %dx%d is empty" % (what, OH, OW))
+    if out is None:
+        out = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * OH * OW * C or not out.is_contiguous():
+        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, OH, OW, C], dev))
+    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
+                                    or black_count.numel() != N * OH * OW or not black_count.is_contiguous()):
+        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, OH, OW], dev))
+    ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
+    px = empty((N, OH, OW), xm) if return_maps else None
+    py = empty((N, OH, OW), xm) if return_maps else None
+    _lib.call("stabnet_warp_rev_bundle2_win", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, ptr(out),
+              ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    res = out.view({2: (OH, OW), 3: (OH, OW, C), 4: (N, OH, OW, C)}[len(shape)])
     return (res, px, py) if return_maps else res
 
 

@@ -20,6 +20,11 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     network-size maps (csrc/remap.hip, stabnet_warp_rev_bundle2_src) instead of the reference's resize-then-warp (deploy_bundle.py:303):
     a 1080p clip run at 288x512 comes back as a 1080p <name>.avi, <name>_stable_bgr.npy and <name>_cut.*; <name>_stable.npy (the
     network's grey output) and <name>_maps.npz keep the network's size.
+  * --fill R|auto (with --ingest device): borderless output.  The kept frame is a window of the stabilised frame, zoomed to the kept
+    frame's own size in the remap's one gather (csrc/remap.hip, stabnet_warp_rev_bundle2_win).  --fill R (0 < R <= 1) runs online:
+    <name>.avi, <name>_stable_bgr.npy and <name>_cut.* hold the centred window that keeps R of each side.  --fill auto runs a second
+    pass after the clip: the largest window of the output's aspect ratio inside the black-free rectangle, written as <name>_fill.npy
+    and, with --mjpg, <name>_fill.avi; everything else is written as without it.  Both write <name>_fill_window.json.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -76,6 +81,11 @@ def build_parser():
     p.add_argument('--output-size', default='network', choices=['network', 'source'],
                    help='size of the frames that are written: network = --height x --width, the frame resized and then warped as the '
                         'reference does; source (needs --ingest device) = the frame as read, warped at its own size by the network-size maps')
+    p.add_argument('--fill', default=None, metavar='R|auto',
+                   help='borderless output (needs --ingest device): crop-and-zoom the stabilised frame to the kept frame\'s own size in the '
+                        'remap\'s one gather (stabnet_warp_rev_bundle2_win).  R in (0, 1]: online, every kept frame is the centred window that '
+                        'keeps R of each side; auto: a second pass through the largest window of the output\'s aspect ratio inside the '
+                        'clip\'s black-free rectangle, written as <name>_fill.npy / _fill.avi')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
 
@@ -85,6 +95,16 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.output_size == 'source' and args.ingest != 'device':
         p.error('--output-size source needs --ingest device: the frame as read must lie on the GPU')
+    if args.fill is not None:
+        if args.fill != 'auto':
+            try:
+                args.fill = float(args.fill)
+            except ValueError:
+                p.error('--fill takes a ratio in (0, 1] or the word auto, got %r' % (args.fill,))
+            if not 0.0 < args.fill <= 1.0:                     # (a NaN fails both comparisons)
+                p.error('--fill R needs 0 < R <= 1, got %r' % (args.fill,))
+        if args.ingest != 'device':
+            p.error('--fill needs --ingest device: the frame as read must lie on the GPU')
     return args
 
 
@@ -141,11 +161,13 @@ def jpeg_options(args):
     return dict(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
 
 
-def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None):
+def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None,
+               window=None, black_win=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
     uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
-    raw frame is warped at its own size and its coverage counted there."""
+    raw frame is warped at its own size and its coverage counted there.  window, black_win (--fill R): the kept frame is that window of
+    the stabilised frame at the kept frame's size, its coverage counted at the output pixels."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
@@ -162,7 +184,11 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
         r = stream.step_u8(cur, ing) if ing is not None else stream.step(cur)     # one sess.run-equivalent
         torch.cuda.synchronize()
         tot_time += time.time() - start
-        if black_src is not None:
+        if window is not None:
+            # the window of the stabilised frame in the one gather: of the frame as read, or of the cv2-resized colour frame
+            frame = cur if black_src is not None else ing.colour(cur)[0]
+            colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], window, black_count=black_win).cpu().numpy())
+        elif black_src is not None:
             # where the reference resizes the colour frame down and warps it (deploy_bundle.py:303): the frame as read, warped as it is
             colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src).cpu().numpy())
         elif ing is not None and ing.C == 3:
@@ -186,9 +212,11 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     return length, tot_time
 
 
-def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False):
+def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False,
+                  window=None):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
-    three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included."""
+    three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included.
+    -> (frames, seconds, coverage at source size or None, coverage at the output pixels of the window or None)."""
     from stabnet_amd.deploy import ClipPipeline
     colour = ing.C == 3 if ing is not None else is_colour(clip[0], H, W)
 
@@ -210,17 +238,91 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
             print('length: ' + str(len(frames_out)))
 
     start = time.time()
-    black_src = None
+    black_src = black_win = None
     if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
-        pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network')
+        pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network', window=window)
         pipe.run(clip, sink=sink, maps=True)
         black_src = pipe.all_black_src if source else None
+        black_win = pipe.all_black_win if window is not None else None
     else:
         ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
     tot_time = time.time() - start
     if frames_out:
         print('fps={}'.format(len(frames_out) / tot_time))
-    return len(frames_out), tot_time, black_src
+    return len(frames_out), tot_time, black_src, black_win
+
+
+def uncovered_per_frame(frame0, xmaps, ymaps, window, out_size, dev):
+    """[pixels of frame t that the window leaves uncovered], from the maps the run kept: the coverage rule depends on the maps and the
+    window alone, so any frame of the right size stands for the source.  Outside the timed part."""
+    import torch
+    from stabnet_amd import warp
+    cnt = torch.zeros(out_size, dtype=torch.int32, device=dev)
+    per = []
+    for xm, ym in zip(xmaps, ymaps):
+        cnt.zero_()
+        warp.warpRevBundle2_win(frame0, torch.from_numpy(xm).to(dev), torch.from_numpy(ym).to(dev), window, out_size, black_count=cnt)
+        per.append(int(cnt.sum().item()))
+    return per
+
+
+def write_fill_json(stem, mode, window, rect, out_size, uncovered, pixels_ever):
+    import json
+    if pixels_ever is not None:
+        uncovered = dict(uncovered, pixels_ever_uncovered=pixels_ever)
+    with open(stem + '_fill_window.json', 'w') as f:
+        json.dump({'mode': mode, 'window': [float(v) for v in window], 'rect': [int(v) for v in rect] if rect else None,
+                   'output_size': [int(out_size[0]), int(out_size[1])], 'uncovered': uncovered}, f, indent=1)
+        f.write('\n')
+    print('wrote', stem + '_fill_window.json')
+
+
+def fill_report(per_frame, out_size):
+    """The uncovered counts of a --fill run, printed and kept for <name>_fill_window.json."""
+    n, px = len(per_frame), out_size[0] * out_size[1]
+    bad = sum(1 for c in per_frame if c > 0)
+    worst = max(per_frame) / px if per_frame else 0.0
+    print('fill: %d of %d frames (%.1f %%) left some pixel uncovered; the worst frame left %.3f %% of its pixels uncovered'
+          % (bad, n, 100.0 * bad / max(n, 1), 100.0 * worst))
+    return {'frames': n, 'frames_uncovered': bad, 'worst_frame_share': worst, 'per_frame': per_frame}
+
+
+def fill_second_pass(clip, ing, source, xmaps, ymaps, window, out_size, dev, stem, args, fps, first):
+    """--fill auto: every frame again through the window -- the frame as read (or its cv2-resized colour frame) and its maps uploaded,
+    stabnet_warp_rev_bundle2_win, the encoder.  -> [uncovered pixels per frame]."""
+    import torch
+    from stabnet_amd import warp
+    from stabnet_amd.avi import AviMjpegWriter
+    from stabnet_amd.mjpeg import MjpegEncoder
+    oh, ow = out_size
+    enc = writer = None
+    if args.mjpg:
+        enc = MjpegEncoder(oh, ow, 3 if ing.C == 3 else 1, device=dev, **jpeg_options(args))
+        writer = AviMjpegWriter(stem + '_fill.avi', ow, oh, fps)
+        writer.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])       # as <name>.avi: the first frame as read comes first
+    cnt = torch.zeros((oh, ow), dtype=torch.int32, device=dev)
+    filled, per = [], []
+    torch.cuda.synchronize()
+    start = time.time()
+    for t in range(1, len(xmaps) + 1):
+        raw = torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
+        frame = raw if source else ing.colour(raw)[0]
+        xm, ym = torch.from_numpy(xmaps[t - 1]).to(dev), torch.from_numpy(ymaps[t - 1]).to(dev)
+        cnt.zero_()
+        out = warp.warpRevBundle2_win(frame, xm, ym, window, (oh, ow), black_count=cnt)
+        if writer is not None:
+            writer.write(enc.encode_bytes(out)[0])
+        filled.append(out.cpu().numpy())
+        per.append(int(cnt.sum().item()))
+    torch.cuda.synchronize()
+    tot = time.time() - start
+    if writer is not None:
+        writer.close()
+        print('wrote %s (%d frames %dx%d)' % (stem + '_fill.avi', writer.frames_written, ow, oh))
+    np.save(stem + '_fill.npy', np.stack(filled))
+    print('wrote', stem + '_fill.npy')
+    print('fill pass: fps={}'.format(len(filled) / tot))
+    return per
 
 
 def main():
@@ -289,6 +391,8 @@ def main():
         stem = os.path.join(out_dir, os.path.splitext(os.path.basename(name))[0])
         writer, enc, fps = None, None, fps_of.get(name, args.fps)
         ing, black_src = None, None          # black_src: coverage at source size (--output-size source), int32 on the device
+        window, black_win, first, source = None, None, None, False      # --fill R: the window, the coverage at its output pixels
+        fill, kept = None, (H, W)            # --fill as it applies to this clip; the kept frame's size
         try:
             if args.ingest == 'device':
                 shp = np.shape(clip[0])
@@ -307,6 +411,16 @@ def main():
             if source:
                 black_src = torch.zeros((ing.sh, ing.sw), dtype=torch.int32, device=dev)
                 print('note: --output-size source: frames are written at %dx%d, warped at that size by the %dx%d maps' % (ing.sw, ing.sh, W, H))
+            # --fill cuts a remapped frame: the frame as read, or the colour frame at the network's size
+            fill = args.fill if ing is not None and (source or ing.C == 3) else None
+            kept = (ing.sh, ing.sw) if source else (H, W)
+            if args.fill is not None and fill is None:
+                print('note: --fill needs a remapped frame to cut; this clip keeps the network\'s grey output and is written as without it')
+            elif fill is not None and fill != 'auto':
+                window = warp.ratio_window(kept[0], kept[1], fill)
+                black_win = torch.zeros(kept, dtype=torch.int32, device=dev)
+                print('note: --fill %g: every kept frame is the window (y0, x0, wh, ww) = %s of the stabilised frame, at %dx%d'
+                      % (fill, list(window), kept[1], kept[0]))
             if args.mjpg:
                 from stabnet_amd.avi import AviMjpegWriter
                 from stabnet_amd.mjpeg import MjpegEncoder
@@ -324,11 +438,13 @@ def main():
                 writer.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])          # deploy_bundle.py:215
             sink = writer.write if writer is not None else None
             if args.pipeline:
-                length, tot_time, pipe_black = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
-                                                             jpeg_options(args) if args.mjpg else None, ing, source)
+                length, tot_time, pipe_black, pipe_win = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
+                                                                       jpeg_options(args) if args.mjpg else None, ing, source, window)
                 black_src = pipe_black if source else None
+                black_win = pipe_win if window is not None else None
             else:
-                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src)
+                length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src,
+                                              window, black_win)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -345,7 +461,9 @@ def main():
                 print('wrote', stem + '_stable.npy')
                 # max-inscribed black-free rectangle over the whole clip (deploy_bundle.py:344-371), searched on the device
                 # (--output-size source: over the coverage counted at source size, and the frames are cut there)
-                ans, area = warp.max_inscribed_rect(black_src if black_src is not None and colour_out else stream.all_black[0])
+                # (--fill R: over the coverage counted at the window's output pixels)
+                coverage = black_win if window is not None and colour_out else (black_src if black_src is not None and colour_out else stream.all_black[0])
+                ans, area = warp.max_inscribed_rect(coverage)
                 if ans:
                     src = np.stack(colour_out) if colour_out else np.stack(frames_out)
                     cut = src[:, ans[0]:ans[2] + 1, ans[1]:ans[3] + 1]
@@ -358,6 +476,26 @@ def main():
                             for f in cut:
                                 wcut.write(cenc.encode_bytes(torch.from_numpy(np.ascontiguousarray(f)).to(dev))[0])
                         print('wrote %s (%d frames %dx%d)' % (stem + '_cut.avi', len(cut), cw, ch))
+                try:
+                    if window is not None and colour_out:                # --fill R: what the online window left uncovered
+                        f0 = torch.from_numpy(np.ascontiguousarray(colour_out[0])).to(dev)
+                        per = uncovered_per_frame(f0, xmaps, ymaps, window, kept, dev)
+                        if sum(per) != int(black_win.sum().item()):
+                            print('WARNING: the coverage counted online (%d) is not the sum over the frames (%d)' % (int(black_win.sum().item()), sum(per)))
+                        write_fill_json(stem, 'ratio', window, None, kept, fill_report(per, kept), int((black_win > 0).sum().item()))
+                        if tot_time > 0:
+                            print('fps={}'.format(length / tot_time))
+                    elif fill == 'auto' and colour_out:
+                        if not ans:
+                            print('note: --fill auto: no black-free rectangle in this clip; no _fill files are written')
+                        else:
+                            fwin = warp.fit_window(ans, kept[0], kept[1])
+                            print('fill: window (y0, x0, wh, ww) = %s of the stabilised frame inside the rectangle %s, at %dx%d'
+                                  % (list(fwin), ans, kept[1], kept[0]))
+                            per = fill_second_pass(clip, ing, source, xmaps, ymaps, fwin, kept, dev, stem, args, fps, first)
+                            write_fill_json(stem, 'auto', fwin, ans, kept, fill_report(per, kept), None)
+                except Exception:
+                    traceback.print_exc()
 
 
 if __name__ == '__main__':

@@ -524,6 +524,25 @@ int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW
                                  unsigned char* out, int* black_count, float* workspace,
                                  float* px_out, float* py_out, void* stream, void* prof);
 
+/* The same remap through a WINDOW of the stabilised frame (crop and zoom in the one gather; remap_win_kernel / remap_win4_kernel).
+ * The contract is stabnet_warp_rev_bundle2_src's, except that the output has its own size OH x OW (1..32767) and output pixel (i, j)
+ * is the stabilised frame, at SH x SW, sampled at a fractional position inside window = {y0, x0, wh, ww}: four doubles in HOST memory,
+ * read during the call, in pixel-edge units of the stabilised frame -- the window covers [x0, x0 + ww) x [y0, y0 + wh), the whole
+ * frame is {0, 0, SH, SW}.  With w = W / rate, h = H / rate:
+ *   ex = x0 + ((double)j + 0.5) * (ww / OW)           double: the quotient, the product, the sum
+ *   f  = (float)(ex * ((double)w / SW) - 0.5)         then cv2.resize's taps: floor, border clamps with the weight zeroed
+ * and likewise ey from y0, wh, OH, h, SH; from there on every step is _src's.  Hence bit for bit: the whole-frame window at
+ * OH, OW == SH, SW gives _src's frame, coordinates and counts, and an integer window with ww == OW, wh == OH gives the slice
+ * [y0 : y0 + OH, x0 : x0 + OW] of them.  out uint8 [N,OH,OW,C] dense; black_count, px_out, py_out [N,OH,OW], at the OUTPUT pixel
+ * under _src's rule.  The four-pixel kernel needs C == 3, OW % 4 == 0 and a 4-byte aligned out (16-byte px_out / py_out); the
+ * source may have any width, stride and alignment.  Refused: everything _src refuses, a null window, a non-finite entry,
+ * wh <= 0 or ww <= 0, a window that leaves [0, SH] x [0, SW] by more than 1e-6 px. */
+int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                 const float* x_map, const float* y_map, int H, int W, int rate,
+                                 const double* window, int OH, int OW,
+                                 unsigned char* out, int* black_count, float* workspace,
+                                 float* px_out, float* py_out, void* stream, void* prof);
+
 /* cvt_train2img (deploy_bundle.py:75): the network's grey output back to 8 bits, out[i] = uint8((x[i] + 0.5) * 255) clipped to
  * [0, 255].  x float [n], out uint8 [n].  The 16-byte path needs both pointers 16-byte aligned (any alignment is accepted). */
 int stabnet_cvt_train2img(const float* x, unsigned char* out, long n, void* stream);

@@ -18,7 +18,8 @@ colour uint8 frames) in, stabilised colour frame + the network's grey output bac
             its own size by the network-size maps (csrc/remap.hip, stabnet_warp_rev_bundle2_src); (c) network_at_source_size: the
             network itself run at the source's size, the only other way to frames of that size.  With --jpeg every graph also encodes
             the kept frame and only the compressed frame is downloaded.  The three alternate, each repeated --repeats times; fps,
-            host_wait_s and the bytes that cross PCIe per frame beside each
+            host_wait_s and the bytes that cross PCIe per frame beside each.  --fill R adds a fourth leg, source_size_fill: (b) with
+            ClipPipeline(window=ratio_window(.., R)) -- the borderless frame, same size, through stabnet_warp_rev_bundle2_win
 One JSON object on stdout.   python tools/bench_pipeline.py [--frames 300] [--height 720 --width 1280] [--jpeg | --ingest [--output-size source [--jpeg]]]"""
 import argparse
 import json
@@ -46,6 +47,7 @@ ap.add_argument("--src-height", type=int, default=None)
 ap.add_argument("--src-width", type=int, default=None)
 ap.add_argument("--jpeg-quality", type=int, default=75)
 ap.add_argument("--output-size", default="network", choices=["network", "source"])
+ap.add_argument("--fill", type=float, default=None, help="with --ingest --output-size source: a leg with the centred window that keeps this share of each side")
 a = ap.parse_args()
 H, W, T = a.height, a.width, a.frames
 dev = torch.device("cuda", 0)
@@ -201,6 +203,10 @@ def source_legs():
                                                     jpeg=opts, ingest=FrameIngest(sh, sw, 3, sh, sw, device=dev))}
     kept = {"network_size": (H, W), "source_size": (sh, sw), "network_at_source_size": (sh, sw)}
     net = {"network_size": (H, W), "source_size": (H, W), "network_at_source_size": (sh, sw)}
+    if a.fill is not None:
+        pipes["source_size_fill"] = ClipPipeline(small(), colour=True, slots=a.slots, jpeg=opts, ingest=FrameIngest(sh, sw, 3, H, W, device=dev),
+                                                 output="source", window=warp.ratio_window(sh, sw, a.fill))
+        kept["source_size_fill"], net["source_size_fill"] = (sh, sw), (H, W)
     legs = {k: {"fps": [], "host_wait_s": [], "bytes_down_per_frame": [], "network": list(net[k]), "kept_frame": list(kept[k]),
                 "bytes_up_per_frame": sh * sw * 3} for k in pipes}
     got = {k: (np.zeros(kept[k] + (3,), np.uint8), np.zeros(net[k], np.uint8), np.zeros(kept[k][0] * kept[k][1] * 3, np.uint8)) for k in pipes}
@@ -230,6 +236,9 @@ def source_legs():
     out["jpeg"] = bool(a.jpeg)
     out["source_size_over_network_at_source_size"] = med(legs["source_size"]["fps"]) / med(legs["network_at_source_size"]["fps"])
     out["source_size_over_network_size"] = med(legs["source_size"]["fps"]) / med(legs["network_size"]["fps"])
+    if a.fill is not None:
+        out["fill"] = a.fill
+        out["source_size_fill_over_source_size"] = med(legs["source_size_fill"]["fps"]) / med(legs["source_size"]["fps"])
     for k in legs:
         f = legs[k]["fps"]
         legs[k]["spread"] = (max(f) - min(f)) / med(f)
@@ -237,6 +246,8 @@ def source_legs():
 
 if a.output_size == "source" and not a.ingest:
     ap.error("--output-size source goes with --ingest")
+if a.fill is not None and not (a.ingest and a.output_size == "source" and 0.0 < a.fill <= 1.0):
+    ap.error("--fill R (0 < R <= 1) goes with --ingest --output-size source")
 
 if a.ingest and a.output_size == "source":
     source_legs()
