@@ -311,19 +311,22 @@ struct WinRemapArgs {
     double x0, y0, xstep, ystep;             // xstep = ww / OW, ystep = wh / OH
 };
 
+// The window of one launch as the bodies below read it: from the kernel arguments (remap_win_kernel, remap_win4_kernel) or from the
+// stream's four doubles in device memory (remap_win_dev_kernel, remap_win4_dev_kernel).
+struct WinSteps { double x0, y0, xstep, ystep; };
+
 // grid (cdiv(OW, blockDim.x), OH, N): one output pixel per thread, any C, size, stride and alignment; byte loads and stores.
-__global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
-                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+__device__ __forceinline__ void remap_win_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
+                                               const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                               int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
-    if (x >= wa.OW) return;
-    const SrcRemapArgs& a = wa.a;
+    if (x >= OW) return;
     const int SH = a.SH, SW = a.SW, C = a.C;
-    const Taps1D tx = cv_taps_at(wa.x0 + ((double)x + 0.5) * wa.xstep, a.w, a.xscale);
-    const Taps1D ty = cv_taps_at(wa.y0 + ((double)y + 0.5) * wa.ystep, a.h, a.yscale);
+    const Taps1D tx = cv_taps_at(ws.x0 + ((double)x + 0.5) * ws.xstep, a.w, a.xscale);
+    const Taps1D ty = cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale);
     const size_t hw = (size_t)a.h * a.w;
     const SrcCoord c = remap_src_coord(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
-    const size_t pix = ((size_t)n * wa.OH + y) * wa.OW + x;
+    const size_t pix = ((size_t)n * OH + y) * OW + x;
     if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
     const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
     const int fx = c.qx & 31, fy = c.qy & 31;
@@ -344,25 +347,24 @@ __global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __r
 
 // grid (cdiv(OW / 4, blockDim.x), OH, N): four consecutive OUTPUT pixels per thread, C == 3, OW % 4 == 0, out 4-byte aligned (px_out /
 // py_out 16-byte).  The source may have any width, stride and alignment: its taps come through remap_src_load6.
-__global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
-                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+__device__ __forceinline__ void remap_win4_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
+                                                const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
-    if (x0 >= wa.OW) return;
-    const SrcRemapArgs& a = wa.a;
+    if (x0 >= OW) return;
     const int SH = a.SH, SW = a.SW;
-    const Taps1D ty = cv_taps_at(wa.y0 + ((double)y + 0.5) * wa.ystep, a.h, a.yscale);
+    const Taps1D ty = cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale);
     const size_t hw = (size_t)a.h * a.w;
     const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
     const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
     const unsigned char* im = src + (size_t)n * a.frame_stride;
     const unsigned char* end = im + (size_t)(SH - 1) * a.row_stride + (size_t)SW * 3;
-    const size_t pix = ((size_t)n * wa.OH + y) * wa.OW + x0;
+    const size_t pix = ((size_t)n * OH + y) * OW + x0;
     unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
     float pxs[4], pys[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const Taps1D tx = cv_taps_at(wa.x0 + ((double)(x0 + e) + 0.5) * wa.xstep, a.w, a.xscale);
+        const Taps1D tx = cv_taps_at(ws.x0 + ((double)(x0 + e) + 0.5) * ws.xstep, a.w, a.xscale);
         const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
         pxs[e] = c.px; pys[e] = c.py;
         const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
@@ -398,6 +400,114 @@ __global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __
     }
 }
 
+__global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
+                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const WinSteps ws = {wa.x0, wa.y0, wa.xstep, wa.ystep};
+    remap_win_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+}
+
+__global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
+                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const WinSteps ws = {wa.x0, wa.y0, wa.xstep, wa.ystep};
+    remap_win4_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+}
+
+// ---- the window in DEVICE memory: window[n] = {y0, x0, wh, ww}, four doubles per stream, written by an earlier launch on the stream
+// (fill_window_kernel below) -- a captured graph freezes kernel arguments, not what a pointer among them points at.  The loads are
+// workgroup-uniform (n = blockIdx.z); the two quotients are IEEE double divisions, the bits of the host's in stabnet_warp_rev_bundle2_win.
+// A window the host entry would have refused (a non-finite entry, wh <= 0 or ww <= 0, one that leaves the frame by more than 1e-6 px)
+// cannot be refused here: the launch reads the whole frame (0, 0, SH, SW) instead, and no tap is ever derived from a NaN.
+__device__ __forceinline__ WinSteps remap_win_load(const double* __restrict__ window, int n, int SH, int SW, int OH, int OW) {
+    double y0 = window[4 * (size_t)n + 0], x0 = window[4 * (size_t)n + 1], wh = window[4 * (size_t)n + 2], ww = window[4 * (size_t)n + 3];
+    const bool finite = fabs(y0) <= 1.0e300 && fabs(x0) <= 1.0e300 && fabs(wh) <= 1.0e300 && fabs(ww) <= 1.0e300;   // false for NaN and Inf
+    const bool ok = finite && wh > 0.0 && ww > 0.0 && y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6;
+    if (!ok) { y0 = 0.0; x0 = 0.0; wh = (double)SH; ww = (double)SW; }
+    WinSteps ws;
+    ws.x0 = x0; ws.y0 = y0; ws.xstep = ww / (double)OW; ws.ystep = wh / (double)OH;
+    return ws;
+}
+
+// grids and preconditions as remap_win_kernel / remap_win4_kernel; wa.x0, wa.y0, wa.xstep, wa.ystep are not read
+__global__ __launch_bounds__(256) void remap_win_dev_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const double* __restrict__ window,
+                                                            const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                            int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
+    remap_win_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+}
+
+__global__ __launch_bounds__(256) void remap_win4_dev_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const double* __restrict__ window,
+                                                             const float* __restrict__ small_maps, unsigned char* __restrict__ out,
+                                                             int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
+    remap_win4_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+}
+
+// ---- adaptive borderless output: the largest centred window of one frame that is provably free of uncovered pixels ----
+// The remap reads the h x w small maps through bilinear taps with non-negative weights that sum to one (the border clamps put the
+// weight on one node), so the coordinate at ANY output position is a convex combination of the four surrounding nodes' coordinates;
+// "covered" is an axis-aligned box; so a position whose four nodes lie inside the box lies inside it.  Node (a, b) is BAD when its own
+// coordinate (remap_src_coord with the taps i0 = i1 = node, w0 = 1, w1 = 0) leaves the box shrunk by margin_q 1/32 px (the float
+// rounding of the blend moves qx by far less).  A bad node b reaches the positions with tap coordinate f in (b - 1, b + 1); a centred
+// window of ratio r reads f in (w/2 (1 - r) - 0.5, w/2 (1 + r) - 0.5): it avoids the node in x iff r w <= |2b + 1 - w| - 2, in y iff
+// r h <= |2a + 1 - h| - 2, and avoiding it in either axis is enough.  Over the common denominator h w, in int32:
+//   key(a, b) = max((|2b + 1 - w| - 2) h, (|2a + 1 - h| - 2) w),   key = min over the bad nodes (h w when there is none)
+// One workgroup per stream strides over the nodes; min / sum through wave shuffles, then LDS: no atomics, no init launch, one order.
+// Thread 0 then moves the stream's window (plain double arithmetic, in this order):
+//   r_safe = key >= h w ? 1 : key / (h w);   r = fmin(r_safe, state + up);  r = fmax(r, r_min);  r = fmin(r, 1);   state = r
+//   wh = SH r;  ww = SW r;  y0 = (SH - wh) / 2;  x0 = (SW - ww) / 2          (warp.ratio_window's expression)
+// zooming in at once (no uncovered pixel whenever r_safe >= r_min), back out by at most `up` per frame.
+struct FillArgs {
+    SrcRemapArgs a;                          // C and the strides are not read
+    int margin_q;
+    double r_min, up;
+};
+
+__global__ __launch_bounds__(1024) void fill_window_kernel(const float* __restrict__ small_maps, FillArgs fa, double* __restrict__ state,
+                                                           double* __restrict__ window, int* __restrict__ stats) {
+    __shared__ int s_key[16], s_bad[16];
+    const SrcRemapArgs& a = fa.a;
+    const int n = blockIdx.x, h = a.h, w = a.w, nodes = h * w;
+    const float* mx = small_maps + ((size_t)n * 2 + 0) * nodes;
+    const float* my = small_maps + ((size_t)n * 2 + 1) * nodes;
+    const int lo = fa.margin_q, xhi = 32 * (a.SW - 1) - fa.margin_q, yhi = 32 * (a.SH - 1) - fa.margin_q;
+    int key = nodes, bad = 0;
+    for (int q = threadIdx.x; q < nodes; q += blockDim.x) {
+        const int na = q / w, nb = q - na * w;
+        Taps1D tx, ty;
+        tx.i0 = nb; tx.i1 = nb; tx.w0 = 1.0f; tx.w1 = 0.0f;
+        ty.i0 = na; ty.i1 = na; ty.w0 = 1.0f; ty.w1 = 0.0f;
+        const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
+        if (c.qx < lo || c.qx > xhi || c.qy < lo || c.qy > yhi) {
+            key = min(key, max((abs(2 * nb + 1 - w) - 2) * h, (abs(2 * na + 1 - h) - 2) * w));
+            ++bad;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        key = min(key, __shfl_xor(key, off));
+        bad += __shfl_xor(bad, off);
+    }
+    const int wave = threadIdx.x >> 6, waves = blockDim.x >> 6;      // blockDim.x is a multiple of 64, at most 1024
+    if ((threadIdx.x & 63) == 0) { s_key[wave] = key; s_bad[wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 1; k < waves; ++k) { key = min(key, s_key[k]); bad += s_bad[k]; }
+    const double r_safe = key >= nodes ? 1.0 : (double)key / (double)nodes;          // may be <= 0
+    double r = fmin(r_safe, state[n] + fa.up);
+    r = fmax(r, fa.r_min);
+    r = fmin(r, 1.0);
+    state[n] = r;
+    const double wh = (double)a.SH * r, ww = (double)a.SW * r;
+    window[4 * (size_t)n + 0] = ((double)a.SH - wh) / 2.0;
+    window[4 * (size_t)n + 1] = ((double)a.SW - ww) / 2.0;
+    window[4 * (size_t)n + 2] = wh;
+    window[4 * (size_t)n + 3] = ww;
+    stats[2 * (size_t)n + 0] = key;
+    stats[2 * (size_t)n + 1] = bad;
+}
+
 // cvt_train2img (deploy_bundle.py:75): ((x + 0.5) * 255).astype(uint8), clipped to [0, 255] first (the network's grey output is a
 // bilinear blend of inputs in [-0.5, 0.5], so the clip only guards the cast).  4 pixels per thread, float4 in, one dword out.
 __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, long n) {
@@ -416,6 +526,16 @@ __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restr
 static int remap_vec4_enabled() {
     static const int v4 = []() { const char* v = getenv("STABNET_REMAP_VEC4"); return v ? atoi(v) : 1; }();
     return v4;
+}
+
+// the change of coordinates of the source-resolution remaps: every constant computed in double, rounded once
+static void src_remap_args(SrcRemapArgs& a, int SH, int SW, int C, int H, int W, int h, int w, size_t row_stride_bytes) {
+    a.SH = SH; a.SW = SW; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
+    a.fW = (float)W; a.fH = (float)H;
+    a.sx = (float)((double)SW / (double)W); a.cx = (float)(0.5 * (double)SW / (double)W - 0.5);
+    a.sy = (float)((double)SH / (double)H); a.cy = (float)(0.5 * (double)SH / (double)H - 0.5);
+    a.xscale = (double)w / SW; a.yscale = (double)h / SH;
+    a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
 }
 
 extern "C" {
@@ -473,12 +593,7 @@ int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW
     SN_LAUNCH_CHECK("map_shrink_kernel");
 
     SrcRemapArgs a;
-    a.SH = SH; a.SW = SW; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
-    a.fW = (float)W; a.fH = (float)H;
-    a.sx = (float)((double)SW / (double)W); a.cx = (float)(0.5 * (double)SW / (double)W - 0.5);
-    a.sy = (float)((double)SH / (double)H); a.cy = (float)(0.5 * (double)SH / (double)H - 0.5);
-    a.xscale = (double)w / SW; a.yscale = (double)h / SH;
-    a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
+    src_remap_args(a, SH, SW, C, H, W, h, w, row_stride_bytes);
     // algorithmic bytes: the frame gathered once, written once, the two small maps
     const double bytes = (double)N * (2.0 * SH * SW * C + 8.0 * h * w);
     const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
@@ -537,12 +652,7 @@ int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW
 
     WinRemapArgs wa;
     SrcRemapArgs& a = wa.a;
-    a.SH = SH; a.SW = SW; a.C = C; a.H = H; a.W = W; a.h = h; a.w = w;
-    a.fW = (float)W; a.fH = (float)H;
-    a.sx = (float)((double)SW / (double)W); a.cx = (float)(0.5 * (double)SW / (double)W - 0.5);
-    a.sy = (float)((double)SH / (double)H); a.cy = (float)(0.5 * (double)SH / (double)H - 0.5);
-    a.xscale = (double)w / SW; a.yscale = (double)h / SH;
-    a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
+    src_remap_args(a, SH, SW, C, H, W, h, w, row_stride_bytes);
     wa.OH = OH; wa.OW = OW; wa.x0 = x0; wa.y0 = y0; wa.xstep = ww / (double)OW; wa.ystep = wh / (double)OH;
     // algorithmic bytes: the window of the frame gathered once, the output written once, the two small maps
     const double bytes = (double)N * ((wh * ww + (double)OH * OW) * C + 8.0 * h * w);
@@ -559,6 +669,92 @@ int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW
     remap_win_kernel<<<dim3(cdiv(OW, threads), OH, N), threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
     if (rec) prof->end(st, PK_KERNEL_REMAP_WIN, 0.0, bytes);
     SN_LAUNCH_CHECK("remap_win_kernel");
+    return STABNET_OK;
+}
+
+/* stabnet_warp_rev_bundle2_win with the window in DEVICE memory: window double [N,4] = {y0, x0, wh, ww} per stream, read by the
+ * kernels when they run -- what an earlier launch on the stream (stabnet_fill_window_update) wrote is what they see, also when the
+ * launches are replayed from a captured graph.  A window whose values _win would refuse gives the whole frame. */
+int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                     const float* x_map, const float* y_map, int H, int W, int rate,
+                                     const double* window, int OH, int OW,
+                                     unsigned char* out, int* black_count, float* workspace,
+                                     float* px_out, float* py_out, void* stream, void* profp) {
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_win_dev: null pointer");
+    SN_REQUIRE(window != nullptr, "warp_rev_bundle2_win_dev: null window");
+    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_win_dev: C must be 1 (grey) or 3 (BGR), got %d", C);
+    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_win_dev: batch %d outside 1..65535", N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
+               "warp_rev_bundle2_win_dev: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
+    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "warp_rev_bundle2_win_dev: output %dx%d outside 1..32767", OH, OW);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_win_dev: maps %dx%d leave nothing at rate %d", H, W, rate);
+    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_win_dev: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
+    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_win_dev: px_out and py_out go together");
+    const int h = H / rate, w = W / rate;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = sn_check_device(src, "warp_rev_bundle2_win_dev: src", st);
+    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_win_dev: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_win_dev: workspace", st);
+    if (rc == 0) rc = sn_check_device(window, "warp_rev_bundle2_win_dev: window", st);
+    if (rc) return rc;
+    Prof* prof = static_cast<Prof*>(profp);
+
+    bool rec = prof && prof->begin(st);
+    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
+    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
+    SN_LAUNCH_CHECK("map_shrink_kernel");
+
+    WinRemapArgs wa;
+    src_remap_args(wa.a, SH, SW, C, H, W, h, w, row_stride_bytes);
+    wa.OH = OH; wa.OW = OW; wa.x0 = 0.0; wa.y0 = 0.0; wa.xstep = 0.0; wa.ystep = 0.0;    // not read: the kernels load the window
+    // algorithmic bytes: at most the whole frame gathered once (the window is not known here), the output written once, the small maps
+    const double bytes = (double)N * (((double)SH * SW + (double)OH * OW) * C + 8.0 * h * w);
+    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
+    rec = prof && prof->begin(st);
+    if (remap_vec4_enabled() && C == 3 && OW % 4 == 0 && aligned) {
+        const int items = OW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
+        remap_win4_dev_kernel<<<dim3(cdiv(items, threads), OH, N), threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
+        if (rec) prof->end(st, PK_KERNEL_REMAP_WIN4_DEV, 0.0, bytes);
+        SN_LAUNCH_CHECK("remap_win4_dev_kernel");
+        return STABNET_OK;
+    }
+    const int threads = OW >= 256 ? 256 : ((OW + 63) & ~63);
+    remap_win_dev_kernel<<<dim3(cdiv(OW, threads), OH, N), threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
+    if (rec) prof->end(st, PK_KERNEL_REMAP_WIN_DEV, 0.0, bytes);
+    SN_LAUNCH_CHECK("remap_win_dev_kernel");
+    return STABNET_OK;
+}
+
+/* The adaptive window of one frame per stream (fill_window_kernel above): x_map, y_map [N,H,W] as the remap receives them; state
+ * double [N] (the ratio of the previous frame, 1.0 at the start of a clip), window double [N,4], stats int32 [N,2] = {key, bad nodes},
+ * workspace 2*N*h*w floats, all in device memory.  Two launches: the shrink, then one workgroup per stream. */
+int stabnet_fill_window_update(const float* x_map, const float* y_map, int N, int H, int W, int rate, int SH, int SW,
+                               double r_min, double up, int margin_q, double* state, double* window, int* stats,
+                               float* workspace, void* stream) {
+    SN_REQUIRE(x_map && y_map && state && window && stats && workspace, "fill_window_update: null pointer");
+    SN_REQUIRE(N >= 1 && N <= 65535, "fill_window_update: batch %d outside 1..65535", N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
+               "fill_window_update: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "fill_window_update: maps %dx%d leave nothing at rate %d", H, W, rate);
+    SN_REQUIRE((long)(H / rate) * (W / rate) <= (1L << 30), "fill_window_update: %ld nodes overflow the int32 key", (long)(H / rate) * (W / rate));
+    SN_REQUIRE(r_min > 0.0 && r_min <= 1.0, "fill_window_update: r_min %g outside (0, 1]", r_min);
+    SN_REQUIRE(std::isfinite(up) && up >= 0.0, "fill_window_update: up %g must be finite and >= 0", up);
+    SN_REQUIRE(margin_q >= 0 && margin_q <= 16 * (SH < SW ? SH : SW), "fill_window_update: margin_q %d outside 0..16 * min(%d, %d)", margin_q, SH, SW);
+    const int h = H / rate, w = W / rate;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = sn_check_device(state, "fill_window_update: state", st);
+    if (rc == 0) rc = sn_check_device(window, "fill_window_update: window", st);
+    if (rc == 0) rc = sn_check_device(stats, "fill_window_update: stats", st);
+    if (rc == 0) rc = sn_check_device(workspace, "fill_window_update: workspace", st);
+    if (rc) return rc;
+    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
+    SN_LAUNCH_CHECK("map_shrink_kernel");
+    FillArgs fa;
+    src_remap_args(fa.a, SH, SW, 1, H, W, h, w, (size_t)SW);
+    fa.margin_q = margin_q; fa.r_min = r_min; fa.up = up;
+    const int nodes = h * w, threads = nodes >= 1024 ? 1024 : ((nodes + 63) & ~63);
+    fill_window_kernel<<<N, threads, 0, st>>>(workspace, fa, state, window, stats);
+    SN_LAUNCH_CHECK("fill_window_kernel");
     return STABNET_OK;
 }
 

@@ -283,10 +283,17 @@ class ClipPipeline:
     frame is that window of the stabilised frame, zoomed to the kept frame's own size in the remap's one gather (csrc/remap.hip,
     stabnet_warp_rev_bundle2_win, where the slot's graph calls the remap today) -- the frame, its JPEG and every buffer keep their
     sizes.  all_black_win (int32, the kept frame's size, zeroed by run) counts per OUTPUT pixel the frames that did not cover it;
-    all_black_src is then not updated.  A pipeline that keeps no remapped frame (colour=False at the network's size) refuses it."""
+    all_black_src is then not updated.  A pipeline that keeps no remapped frame (colour=False at the network's size) refuses it.
+
+    window='adaptive', fill=dict(r_min=0.5, up=0.002, margin_q=8): the window is chosen per frame ON THE DEVICE, inside the slot's
+    graph: stabnet_fill_window_update (the largest centred window that reads no uncovered small-map node, zooming in at once and back
+    out by `up` per frame, never below r_min) writes the slot's 32-byte window, and stabnet_warp_rev_bundle2_win_dev reads it from
+    there -- both on the stream that carries the frame's launches, so the ratio advances in frame order; no host round trip.  The
+    result carries "window" (float64 [4]: y0, x0, wh, ww) and "fill_stats" (int32 [2]: key, bad nodes; r_safe = key / (h * w), 1 if
+    key >= h * w), downloaded with the slot's other outputs; all_black_win counts as with a fixed window."""
 
     def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
-                 output: str = "network", window=None):
+                 output: str = "network", window=None, fill=None):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
@@ -301,15 +308,28 @@ class ClipPipeline:
         self.st, self.colour, self.slots, self.rate = stream, colour, slots, rate
         self.src_out = output == "source"
         self.window = None
+        self.windowed = window is not None
+        self.adaptive = isinstance(window, str)
+        if self.adaptive and window != "adaptive":
+            raise _lib.StabnetError("ClipPipeline: window must be (y0, x0, wh, ww) or 'adaptive', got %r" % (window,))
+        if fill is not None and not self.adaptive:
+            raise _lib.StabnetError("ClipPipeline: fill=... belongs to window='adaptive'")
         if window is not None:
             if output != "source" and not colour:
                 raise _lib.StabnetError("ClipPipeline: window needs a remapped frame to cut (colour=True or output='source'); "
                                         "this pipeline keeps the network's grey output")
+            kh, kw = (ingest.sh, ingest.sw) if output == "source" else (stream.H, stream.W)
+        if self.adaptive:
+            from .warp import check_fill_params
+            try:
+                self.fill = check_fill_params(SH=kh, SW=kw, **(fill or {}))
+            except (TypeError, ValueError) as e:
+                raise _lib.StabnetError("ClipPipeline: %s" % e)
+        elif window is not None:
             try:
                 win = tuple(float(v) for v in window)
             except (TypeError, ValueError):
                 win = ()
-            kh, kw = (ingest.sh, ingest.sw) if output == "source" else (stream.H, stream.W)
             if len(win) != 4 or not all(np.isfinite(win)) or win[2] <= 0 or win[3] <= 0 or min(win[:2]) < -1e-6 \
                     or win[0] + win[2] > kh + 1e-6 or win[1] + win[3] > kw + 1e-6:
                 raise _lib.StabnetError("ClipPipeline: window must be (y0, x0, wh, ww) inside the %dx%d kept frame, got %r" % (kh, kw, window))
@@ -345,8 +365,16 @@ class ClipPipeline:
             self.h_warp = [pin((H, W, 3), torch.uint8) for _ in range(slots)]
             self.d_warp = [on((1, H, W, 3), torch.uint8) for _ in range(slots)]
             self.remap_ws = on((2 * (H // rate) * (W // rate),), torch.float32)
-        if self.window is not None:
+        if self.windowed:
             self.all_black_win = torch.zeros(src[:2] if self.src_out else (H, W), dtype=torch.int32, device=dev)
+        if self.adaptive:
+            # the ratio of the previous frame (one per pipeline: frames run in order on s_run); per slot the frame's window (4 doubles)
+            # and stats (2 ints) in one 40-byte buffer, so that they come down in one copy
+            self.fill_state = torch.ones(1, dtype=torch.float64, device=dev)
+            self.d_fill = [on((40,), torch.uint8) for _ in range(slots)]
+            self.h_fill = [pin((40,), torch.uint8) for _ in range(slots)]
+            self.d_win = [b[:32].view(torch.float64) for b in self.d_fill]
+            self.d_stats = [b[32:].view(torch.int32) for b in self.d_fill]
         self.enc = None
         if jpeg is not None:
             from .mjpeg import MjpegEncoder
@@ -379,14 +407,22 @@ class ClipPipeline:
             st._enqueue(cur=self.d_grey[k])                  # the frame reads the upload slot itself: no staging copy
         # cvt_train2img (deploy_bundle.py:75)
         _lib.call("stabnet_cvt_train2img", ptr(st.out_img), ptr(self.d_out[k]), H * W, stream_ptr(self.dev), device=self.dev)
-        if self.window is not None:
+        if self.windowed:
             # the window of the stabilised frame, zoomed to the kept frame's size in the remap's gather; coverage counted at the output
             if self.src_out:
                 frame, (sh, sw, C) = self.d_u8[k], (self.ingest.sh, self.ingest.sw, self.ingest.C)
             else:
                 frame, (sh, sw, C) = self.d_bgr[k], (H, W, 3)
-            _lib.call("stabnet_warp_rev_bundle2_win", ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
-                      self.window, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
+            entry, win = "stabnet_warp_rev_bundle2_win", self.window
+            if self.adaptive:
+                # this frame's window, chosen on the device from its maps and the previous frame's ratio; the remap loads it from there
+                r_min, up, margin_q = self.fill
+                _lib.call("stabnet_fill_window_update", ptr(st.x_map), ptr(st.y_map), 1, H, W, self.rate, sh, sw, r_min, up, margin_q,
+                          ptr(self.fill_state), ptr(self.d_win[k]), ptr(self.d_stats[k]), ptr(self.remap_ws), stream_ptr(self.dev),
+                          device=self.dev)
+                entry, win = entry + "_dev", ptr(self.d_win[k])
+            _lib.call(entry, ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
+                      win, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
                       device=self.dev)
         elif self.src_out:
             # the raw frame in the upload slot, warped at its own size by the network-size maps; coverage counted on the way
@@ -432,6 +468,9 @@ class ClipPipeline:
             r["jpeg"] = self.h_jpeg[slot].numpy()[:n]
         if maps:
             r["x_map"], r["y_map"], r["black"] = (m[slot].numpy() for m in self.h_maps)
+        if self.adaptive:
+            r["window"] = self.h_fill[slot][:32].view(torch.float64).numpy()
+            r["fill_stats"] = self.h_fill[slot][32:].view(torch.int32).numpy()
         return r
 
     def run(self, grey, bgr=None, sink=None, maps: bool = False, raw: bool = True):
@@ -460,8 +499,10 @@ class ClipPipeline:
             else:
                 first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.float32)).to(self.dev)
                 st.start(first[None])
-            if self.window is not None:
+            if self.windowed:
                 self.all_black_win.zero_()
+            if self.adaptive:
+                self.fill_state.fill_(1.0)
         pending = [None] * K                                  # frame number whose results sit in (or are on their way to) slot k
         for t in range(1, n):
             k = t % K
@@ -510,6 +551,8 @@ class ClipPipeline:
                 if maps:
                     for h, d in zip(self.h_maps, self.d_maps):
                         h[k].copy_(d[k], non_blocking=True)
+                if self.adaptive:
+                    self.h_fill[k].copy_(self.d_fill[k], non_blocking=True)
                 self.ev_down[k].record(self.s_out)
             pending[k] = t                                    # (the slot's next upload follows the host's wait on ev_down[k])
         order = sorted((p, k) for k, p in enumerate(pending) if p is not None)

@@ -230,14 +230,24 @@ def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
                        black_count: torch.Tensor = None, out: torch.Tensor = None, return_maps: bool = False, prof=None):
     """warpRevBundle2_src through a WINDOW of the stabilised frame (csrc/remap.hip, stabnet_warp_rev_bundle2_win): crop and zoom in the
     one gather.  window = (y0, x0, wh, ww) in pixel-edge units of the stabilised frame at the source's size (the whole frame is
-    (0, 0, SH, SW); ratio_window / fit_window make one); out_size = (OH, OW), default the source's size.
+    (0, 0, SH, SW); ratio_window / fit_window make one); out_size = (OH, OW), default the source's size.  A float64 tensor [4] or [N,4]
+    on the frames' device is a window in DEVICE memory (stabnet_warp_rev_bundle2_win_dev: the kernels load it when they run, so an
+    earlier launch on the stream -- AdaptiveFill.update -- may have written it; values the host entry would refuse give the whole frame).
     -> uint8 [N,OH,OW,C] / [OH,OW,C] / [OH,OW] after src_u8's layout (with return_maps: (out, px, py), float32 [N,OH,OW]).
     black_count: optional int32 [N,OH,OW], += 1 where the frame does not cover the OUTPUT pixel.  Nothing synchronises."""
     what = "warpRevBundle2_win"
     u8, stride, shape = _check_src_u8(src_u8, what)
     N, SH, SW, C = u8.shape
     dev = u8.device
-    win = _check_window(window, what)
+    entry = "stabnet_warp_rev_bundle2_win"
+    if isinstance(window, torch.Tensor):
+        if window.dtype != torch.float64 or window.device != dev or tuple(window.shape) not in ((4,), (N, 4)):
+            raise _lib.StabnetError("%s: a window tensor must be float64 [4] or [%d, 4] on %s, got %s %s on %s"
+                                    % (what, N, dev, window.dtype, list(window.shape), window.device))
+        win_t = window.expand(N, 4).contiguous()             # (kept alive until the launch is enqueued)
+        win, entry = ptr(win_t), entry + "_dev"
+    else:
+        win = _check_window(window, what)
     OH, OW = (SH, SW) if out_size is None else (int(out_size[0]), int(out_size[1]))
     xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
     if OH < 1 or OW < 1:
@@ -252,10 +262,77 @@ def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
     px = empty((N, OH, OW), xm) if return_maps else None
     py = empty((N, OH, OW), xm) if return_maps else None
-    _lib.call("stabnet_warp_rev_bundle2_win", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, ptr(out),
+    _lib.call(entry, ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, ptr(out),
               ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
     res = out.view({2: (OH, OW), 3: (OH, OW, C), 4: (N, OH, OW, C)}[len(shape)])
     return (res, px, py) if return_maps else res
+
+
+def check_fill_params(r_min=0.5, up=0.002, margin_q=8, SH=None, SW=None):
+    """The ranges stabnet_fill_window_update accepts, checked on the host (ValueError): r_min in (0, 1], up finite and >= 0, margin_q an
+    integer in 0 .. 16 * min(SH, SW) (the upper end only when the size is given).  -> (float r_min, float up, int margin_q)."""
+    try:
+        r_min, up, mq = float(r_min), float(up), int(margin_q)
+    except (TypeError, ValueError):
+        raise ValueError("adaptive fill: r_min, up, margin_q must be numbers, got %r, %r, %r" % (r_min, up, margin_q))
+    if not 0.0 < r_min <= 1.0:
+        raise ValueError("adaptive fill: r_min must lie in (0, 1], got %r" % (r_min,))
+    if not (up >= 0.0 and up != float("inf")):
+        raise ValueError("adaptive fill: up must be finite and >= 0, got %r" % (up,))
+    if mq != margin_q or mq < 0 or (SH is not None and mq > 16 * min(int(SH), int(SW))):
+        raise ValueError("adaptive fill: margin_q must be an integer in 0 .. 16 * min(SH, SW), got %r" % (margin_q,))
+    return r_min, up, mq
+
+
+def fill_window_update(x_map: torch.Tensor, y_map: torch.Tensor, SH: int, SW: int, state: torch.Tensor, window: torch.Tensor,
+                       stats: torch.Tensor, r_min: float = 0.5, up: float = 0.002, margin_q: int = 8, rate: int = 4,
+                       workspace: torch.Tensor = None):
+    """The adaptive window of one frame per stream (csrc/remap.hip, stabnet_fill_window_update): from the network-size maps x_map, y_map
+    [N,H,W(,1)] / [H,W] of the frame, the largest centred window of the SH x SW stabilised frame that reads no small-map node whose
+    coordinate leaves the frame shrunk by margin_q / 32 px; zooming in at once, back out by at most `up` per call, never below r_min.
+    state float64 [N] (the previous ratio; 1.0 at the start of a clip) is advanced, window float64 [N,4] = (y0, x0, wh, ww) and
+    stats int32 [N,2] = (key, bad nodes) are written; r_safe = 1 if key >= h * w else key / (h * w).  All on the maps' device;
+    nothing synchronises.  -> window."""
+    what = "fill_window_update"
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float64 or state.dim() != 1 or not state.is_contiguous():
+        raise _lib.StabnetError("%s: state must be a contiguous float64 tensor [N] on the GPU (there is no CPU fallback)" % what)
+    N, dev = state.numel(), state.device
+    xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
+    for t, dt, shape, name in ((window, torch.float64, (N, 4), "window"), (stats, torch.int32, (N, 2), "stats")):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.StabnetError("%s: %s must be a contiguous %s tensor %s on %s" % (what, name, dt, list(shape), dev))
+    n_ws = 2 * N * (H // rate) * (W // rate)
+    if workspace is None:
+        workspace = torch.empty(n_ws, dtype=torch.float32, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.float32 or workspace.numel() < n_ws \
+            or not workspace.is_contiguous():
+        raise _lib.StabnetError("%s: workspace must be a contiguous float32 tensor of >= %d elements on %s" % (what, n_ws, dev))
+    _lib.call("stabnet_fill_window_update", ptr(xm), ptr(ym), N, H, W, int(rate), int(SH), int(SW), float(r_min), float(up), int(margin_q),
+              ptr(state), ptr(window), ptr(stats), ptr(workspace), stream_ptr(dev), device=dev)
+    return window
+
+
+class AdaptiveFill:
+    """The per-frame window of adaptive borderless output for N streams of SH x SW kept frames: `state` float64 [N], `window` float64
+    [N,4], `stats` int32 [N,2] on `device`.  reset() at the start of a clip; update(x_map, y_map) per frame, in frame order, on the
+    stream that carries the frame's launches -> window, which warpRevBundle2_win takes as it is.  No host round trip."""
+
+    def __init__(self, N: int, SH: int, SW: int, r_min: float = 0.5, up: float = 0.002, margin_q: int = 8, device="cuda", rate: int = 4):
+        self.r_min, self.up, self.margin_q = check_fill_params(r_min, up, margin_q, SH, SW)
+        self.N, self.SH, self.SW, self.rate = int(N), int(SH), int(SW), int(rate)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.StabnetError("AdaptiveFill: the window lives on the GPU (there is no CPU fallback), got device %s" % dev)
+        self.state = torch.ones(self.N, dtype=torch.float64, device=dev)
+        self.window = torch.tensor([ratio_window(SH, SW, 1.0)] * self.N, dtype=torch.float64, device=dev)
+        self.stats = torch.zeros((self.N, 2), dtype=torch.int32, device=dev)
+
+    def reset(self):
+        self.state.fill_(1.0)
+
+    def update(self, x_map: torch.Tensor, y_map: torch.Tensor):
+        return fill_window_update(x_map, y_map, self.SH, self.SW, self.state, self.window, self.stats, self.r_min, self.up, self.margin_q,
+                                  self.rate)
 
 
 def cvt_train2img(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:

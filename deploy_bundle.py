@@ -24,7 +24,10 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     frame's own size in the remap's one gather (csrc/remap.hip, stabnet_warp_rev_bundle2_win).  --fill R (0 < R <= 1) runs online:
     <name>.avi, <name>_stable_bgr.npy and <name>_cut.* hold the centred window that keeps R of each side.  --fill auto runs a second
     pass after the clip: the largest window of the output's aspect ratio inside the black-free rectangle, written as <name>_fill.npy
-    and, with --mjpg, <name>_fill.avi; everything else is written as without it.  Both write <name>_fill_window.json.
+    and, with --mjpg, <name>_fill.avi; everything else is written as without it.  --fill adaptive runs online too, with a window
+    chosen per frame on the GPU (stabnet_fill_window_update, then stabnet_warp_rev_bundle2_win_dev): the largest centred window that
+    provably shows no uncovered pixel, never below --fill-min, growing back by at most --fill-up per frame.  All three write
+    <name>_fill_window.json.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -81,11 +84,17 @@ def build_parser():
     p.add_argument('--output-size', default='network', choices=['network', 'source'],
                    help='size of the frames that are written: network = --height x --width, the frame resized and then warped as the '
                         'reference does; source (needs --ingest device) = the frame as read, warped at its own size by the network-size maps')
-    p.add_argument('--fill', default=None, metavar='R|auto',
+    p.add_argument('--fill', default=None, metavar='R|auto|adaptive',
                    help='borderless output (needs --ingest device): crop-and-zoom the stabilised frame to the kept frame\'s own size in the '
                         'remap\'s one gather (stabnet_warp_rev_bundle2_win).  R in (0, 1]: online, every kept frame is the centred window that '
                         'keeps R of each side; auto: a second pass through the largest window of the output\'s aspect ratio inside the '
-                        'clip\'s black-free rectangle, written as <name>_fill.npy / _fill.avi')
+                        'clip\'s black-free rectangle, written as <name>_fill.npy / _fill.avi; adaptive: online, the window is chosen per '
+                        'frame on the GPU (stabnet_fill_window_update): the largest centred one that shows no uncovered pixel')
+    p.add_argument('--fill-min', type=float, default=None, metavar='R',
+                   help='--fill adaptive: the smallest ratio the window may shrink to, in (0, 1] (default 0.5); a frame that needs less '
+                        'is cut at this ratio and may show uncovered pixels')
+    p.add_argument('--fill-up', type=float, default=None, metavar='D',
+                   help='--fill adaptive: how much the ratio may grow back per frame, >= 0 (default 0.002); zooming in is immediate')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
 
@@ -95,12 +104,21 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.output_size == 'source' and args.ingest != 'device':
         p.error('--output-size source needs --ingest device: the frame as read must lie on the GPU')
+    if args.fill != 'adaptive' and (args.fill_min is not None or args.fill_up is not None):
+        p.error('--fill-min / --fill-up belong to --fill adaptive')
+    if args.fill == 'adaptive':
+        args.fill_min = 0.5 if args.fill_min is None else args.fill_min
+        args.fill_up = 0.002 if args.fill_up is None else args.fill_up
+        if not 0.0 < args.fill_min <= 1.0:                     # (a NaN fails both comparisons)
+            p.error('--fill-min needs 0 < R <= 1, got %r' % (args.fill_min,))
+        if not 0.0 <= args.fill_up < float('inf'):
+            p.error('--fill-up needs a finite D >= 0, got %r' % (args.fill_up,))
     if args.fill is not None:
-        if args.fill != 'auto':
+        if args.fill not in ('auto', 'adaptive'):
             try:
                 args.fill = float(args.fill)
             except ValueError:
-                p.error('--fill takes a ratio in (0, 1] or the word auto, got %r' % (args.fill,))
+                p.error('--fill takes a ratio in (0, 1] or one of the words auto, adaptive, got %r' % (args.fill,))
             if not 0.0 < args.fill <= 1.0:                     # (a NaN fails both comparisons)
                 p.error('--fill R needs 0 < R <= 1, got %r' % (args.fill,))
         if args.ingest != 'device':
@@ -162,16 +180,19 @@ def jpeg_options(args):
 
 
 def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None,
-               window=None, black_win=None):
+               window=None, black_win=None, adaptive=None, fill_log=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
     uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
     raw frame is warped at its own size and its coverage counted there.  window, black_win (--fill R): the kept frame is that window of
-    the stabilised frame at the kept frame's size, its coverage counted at the output pixels."""
+    the stabilised frame at the kept frame's size, its coverage counted at the output pixels.  adaptive (--fill adaptive; a
+    warp.AdaptiveFill): the window is the one the GPU chooses for the frame; fill_log gets (window, stats) per frame."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
     raw = lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
+    if adaptive is not None:
+        adaptive.reset()
     if ing is not None:
         stream.start_u8(raw(0), ing)
     else:
@@ -184,10 +205,13 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
         r = stream.step_u8(cur, ing) if ing is not None else stream.step(cur)     # one sess.run-equivalent
         torch.cuda.synchronize()
         tot_time += time.time() - start
-        if window is not None:
+        if window is not None or adaptive is not None:
             # the window of the stabilised frame in the one gather: of the frame as read, or of the cv2-resized colour frame
             frame = cur if black_src is not None else ing.colour(cur)[0]
-            colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], window, black_count=black_win).cpu().numpy())
+            win = window if adaptive is None else adaptive.update(r['x_map'], r['y_map'])     # (on the device: read there by the remap)
+            colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], win, black_count=black_win).cpu().numpy())
+            if adaptive is not None:
+                fill_log.append((adaptive.window[0].cpu().numpy(), adaptive.stats[0].cpu().numpy()))
         elif black_src is not None:
             # where the reference resizes the colour frame down and warps it (deploy_bundle.py:303): the frame as read, warped as it is
             colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src).cpu().numpy())
@@ -213,9 +237,10 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
 
 
 def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False,
-                  window=None):
+                  window=None, fill=None, fill_log=None):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included.
+    window='adaptive' with fill=dict(r_min, up, margin_q): the per-frame window of --fill adaptive; fill_log gets (window, stats).
     -> (frames, seconds, coverage at source size or None, coverage at the output pixels of the window or None)."""
     from stabnet_amd.deploy import ClipPipeline
     colour = ing.C == 3 if ing is not None else is_colour(clip[0], H, W)
@@ -234,13 +259,16 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
         if jpeg_sink is not None:
             jpeg_sink(bytes(r['jpeg']))
         xmaps.append(r['x_map'].copy()); ymaps.append(r['y_map'].copy()); blacks.append(r['black'].copy())
+        if 'window' in r:
+            fill_log.append((r['window'].copy(), r['fill_stats'].copy()))
         if len(frames_out) % 10 == 0:
             print('length: ' + str(len(frames_out)))
 
     start = time.time()
     black_src = black_win = None
     if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
-        pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network', window=window)
+        pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network', window=window,
+                            fill=fill)
         pipe.run(clip, sink=sink, maps=True)
         black_src = pipe.all_black_src if source else None
         black_win = pipe.all_black_win if window is not None else None
@@ -254,14 +282,16 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
 
 def uncovered_per_frame(frame0, xmaps, ymaps, window, out_size, dev):
     """[pixels of frame t that the window leaves uncovered], from the maps the run kept: the coverage rule depends on the maps and the
-    window alone, so any frame of the right size stands for the source.  Outside the timed part."""
+    window alone, so any frame of the right size stands for the source.  window: one for the clip, or a list with one per frame.
+    Outside the timed part."""
     import torch
     from stabnet_amd import warp
     cnt = torch.zeros(out_size, dtype=torch.int32, device=dev)
     per = []
-    for xm, ym in zip(xmaps, ymaps):
+    windows = window if isinstance(window, list) else [window] * len(xmaps)
+    for xm, ym, win in zip(xmaps, ymaps, windows):
         cnt.zero_()
-        warp.warpRevBundle2_win(frame0, torch.from_numpy(xm).to(dev), torch.from_numpy(ym).to(dev), window, out_size, black_count=cnt)
+        warp.warpRevBundle2_win(frame0, torch.from_numpy(xm).to(dev), torch.from_numpy(ym).to(dev), win, out_size, black_count=cnt)
         per.append(int(cnt.sum().item()))
     return per
 
@@ -273,6 +303,22 @@ def write_fill_json(stem, mode, window, rect, out_size, uncovered, pixels_ever):
     with open(stem + '_fill_window.json', 'w') as f:
         json.dump({'mode': mode, 'window': [float(v) for v in window], 'rect': [int(v) for v in rect] if rect else None,
                    'output_size': [int(out_size[0]), int(out_size[1])], 'uncovered': uncovered}, f, indent=1)
+        f.write('\n')
+    print('wrote', stem + '_fill_window.json')
+
+
+def write_fill_adaptive_json(stem, params, fill_log, nodes, out_size, uncovered, pixels_ever):
+    """<name>_fill_window.json of --fill adaptive: the parameters, and per frame the window the GPU chose, r_safe (the largest ratio its
+    rule proves free of uncovered pixels; <= 0: none) and the number of bad nodes.  held_at_min: the frames whose r_safe lay below
+    r_min -- cut at r_min, the only ones that may show uncovered pixels."""
+    import json
+    r_safe = [1.0 if int(st[0]) >= nodes else float(int(st[0])) / float(nodes) for _, st in fill_log]
+    with open(stem + '_fill_window.json', 'w') as f:
+        json.dump({'mode': 'adaptive', 'params': params, 'output_size': [int(out_size[0]), int(out_size[1])],
+                   'windows': [[float(v) for v in w] for w, _ in fill_log], 'r_safe': r_safe,
+                   'bad_nodes': [int(st[1]) for _, st in fill_log],
+                   'held_at_min': sum(1 for r in r_safe if r < params['r_min']),
+                   'uncovered': dict(uncovered, pixels_ever_uncovered=pixels_ever)}, f, indent=1)
         f.write('\n')
     print('wrote', stem + '_fill_window.json')
 
@@ -393,6 +439,7 @@ def main():
         ing, black_src = None, None          # black_src: coverage at source size (--output-size source), int32 on the device
         window, black_win, first, source = None, None, None, False      # --fill R: the window, the coverage at its output pixels
         fill, kept = None, (H, W)            # --fill as it applies to this clip; the kept frame's size
+        adaptive, fill_params, fill_log = None, None, []     # --fill adaptive: the window's state on the device; (window, stats) per frame
         try:
             if args.ingest == 'device':
                 shp = np.shape(clip[0])
@@ -416,6 +463,14 @@ def main():
             kept = (ing.sh, ing.sw) if source else (H, W)
             if args.fill is not None and fill is None:
                 print('note: --fill needs a remapped frame to cut; this clip keeps the network\'s grey output and is written as without it')
+            elif fill == 'adaptive':
+                fill_params = dict(r_min=args.fill_min, up=args.fill_up, margin_q=8)
+                black_win = torch.zeros(kept, dtype=torch.int32, device=dev)
+                if not args.pipeline:
+                    adaptive = warp.AdaptiveFill(1, kept[0], kept[1], device=dev, **fill_params)
+                print('note: --fill adaptive: every kept frame is the largest centred window of the stabilised frame that shows no uncovered '
+                      'pixel (ratio >= %g, growing back by <= %g per frame), chosen on the GPU, at %dx%d'
+                      % (args.fill_min, args.fill_up, kept[1], kept[0]))
             elif fill is not None and fill != 'auto':
                 window = warp.ratio_window(kept[0], kept[1], fill)
                 black_win = torch.zeros(kept, dtype=torch.int32, device=dev)
@@ -439,12 +494,13 @@ def main():
             sink = writer.write if writer is not None else None
             if args.pipeline:
                 length, tot_time, pipe_black, pipe_win = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
-                                                                       jpeg_options(args) if args.mjpg else None, ing, source, window)
+                                                                       jpeg_options(args) if args.mjpg else None, ing, source,
+                                                                       'adaptive' if fill_params else window, fill_params, fill_log)
                 black_src = pipe_black if source else None
-                black_win = pipe_win if window is not None else None
+                black_win = pipe_win if (window is not None or fill_params) else None
             else:
                 length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src,
-                                              window, black_win)
+                                              window, black_win, adaptive, fill_log)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -462,7 +518,7 @@ def main():
                 # max-inscribed black-free rectangle over the whole clip (deploy_bundle.py:344-371), searched on the device
                 # (--output-size source: over the coverage counted at source size, and the frames are cut there)
                 # (--fill R: over the coverage counted at the window's output pixels)
-                coverage = black_win if window is not None and colour_out else (black_src if black_src is not None and colour_out else stream.all_black[0])
+                coverage = black_win if (window is not None or fill_params) and colour_out else (black_src if black_src is not None and colour_out else stream.all_black[0])
                 ans, area = warp.max_inscribed_rect(coverage)
                 if ans:
                     src = np.stack(colour_out) if colour_out else np.stack(frames_out)
@@ -483,6 +539,15 @@ def main():
                         if sum(per) != int(black_win.sum().item()):
                             print('WARNING: the coverage counted online (%d) is not the sum over the frames (%d)' % (int(black_win.sum().item()), sum(per)))
                         write_fill_json(stem, 'ratio', window, None, kept, fill_report(per, kept), int((black_win > 0).sum().item()))
+                        if tot_time > 0:
+                            print('fps={}'.format(length / tot_time))
+                    elif fill_params and colour_out:                      # --fill adaptive: each frame recounted through its own window
+                        f0 = torch.from_numpy(np.ascontiguousarray(colour_out[0])).to(dev)
+                        per = uncovered_per_frame(f0, xmaps, ymaps, [tuple(float(v) for v in w) for w, _ in fill_log], kept, dev)
+                        if sum(per) != int(black_win.sum().item()):
+                            print('WARNING: the coverage counted online (%d) is not the sum over the frames (%d)' % (int(black_win.sum().item()), sum(per)))
+                        write_fill_adaptive_json(stem, fill_params, fill_log, (H // 4) * (W // 4), kept, fill_report(per, kept),
+                                                 int((black_win > 0).sum().item()))
                         if tot_time > 0:
                             print('fps={}'.format(length / tot_time))
                     elif fill == 'auto' and colour_out:

@@ -543,6 +543,37 @@ int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW
                                  unsigned char* out, int* black_count, float* workspace,
                                  float* px_out, float* py_out, void* stream, void* prof);
 
+/* stabnet_warp_rev_bundle2_win with the window in DEVICE memory (remap_win_dev_kernel / remap_win4_dev_kernel: the bodies of the _win
+ * kernels): window double [N,4], {y0, x0, wh, ww} per stream, loaded by the kernels when they RUN -- so an earlier launch on the stream
+ * (stabnet_fill_window_update) may write it, and a captured graph replays with whatever it holds then.  The kernels form
+ * xstep = ww / OW and ystep = wh / OH in double (IEEE division: the host's bits), hence frame, coordinates and counts are _win's bit
+ * for bit for the same window.  The window's VALUES cannot be refused by the host: a stream whose window has a non-finite entry,
+ * wh <= 0 or ww <= 0, or leaves [0, SH] x [0, SW] by more than 1e-6 px, is read through the whole frame {0, 0, SH, SW}; no tap is
+ * ever derived from a NaN.  Everything else -- the other refusals, the choice between the two kernels, STABNET_REMAP_VEC4,
+ * black_count / px_out / py_out -- is _win's. */
+int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                     const float* x_map, const float* y_map, int H, int W, int rate,
+                                     const double* window, int OH, int OW,
+                                     unsigned char* out, int* black_count, float* workspace,
+                                     float* px_out, float* py_out, void* stream, void* prof);
+
+/* Adaptive borderless output: per stream, the largest centred window of the stabilised frame that is provably free of uncovered
+ * pixels, rate-limited on the way back out (fill_window_kernel).  x_map, y_map [N,H,W] as the remap receives them; h = H / rate,
+ * w = W / rate.  Node (a, b) of the h x w small maps is BAD when its own coordinate (the remap's arithmetic with all the weight on the
+ * node) rounded to 1/32 px has qx < margin_q, qx > 32*(SW-1) - margin_q, or the same in y (a NaN entry: -2e9, bad).  Every output
+ * coordinate is a convex combination of its four nodes, so a window that reads no bad node shows no uncovered pixel:
+ *   key(a, b) = max((|2b+1-w| - 2) * h, (|2a+1-h| - 2) * w)      key = min over the bad nodes, h*w when there is none   (int32)
+ *   r_safe = key >= h*w ? 1.0 : (double)key / (double)(h*w)      (may be <= 0)
+ *   r = fmin(r_safe, state[n] + up);  r = fmax(r, r_min);  r = fmin(r, 1.0);  state[n] = r
+ *   wh = SH*r;  ww = SW*r;  window[n] = {(SH - wh)/2, (SW - ww)/2, wh, ww};  stats[n] = {key, number of bad nodes}
+ * state double [N] (set to 1.0 at the start of a clip), window double [N,4], stats int32 [N,2], workspace 2*N*h*w floats: device
+ * memory.  Two launches (the shrink; one workgroup per stream, shuffles and LDS, no atomics): deterministic, nothing allocates,
+ * synchronises or copies.  Refused before any launch: null pointers, the sizes _src refuses, more than 2^30 nodes, r_min outside
+ * (0, 1], up negative or not finite, margin_q outside 0..16*min(SH, SW). */
+int stabnet_fill_window_update(const float* x_map, const float* y_map, int N, int H, int W, int rate, int SH, int SW,
+                               double r_min, double up, int margin_q, double* state, double* window, int* stats,
+                               float* workspace, void* stream);
+
 /* cvt_train2img (deploy_bundle.py:75): the network's grey output back to 8 bits, out[i] = uint8((x[i] + 0.5) * 255) clipped to
  * [0, 255].  x float [n], out uint8 [n].  The 16-byte path needs both pointers 16-byte aligned (any alignment is accepted). */
 int stabnet_cvt_train2img(const float* x, unsigned char* out, long n, void* stream);
