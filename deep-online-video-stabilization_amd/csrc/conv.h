@@ -47,7 +47,12 @@ struct Prof;
 // are read (conv_kernel.h, sn_split3).  bf16_operands = 4 with w_img: the weights come as a pre-split fragment-major image
 // (conv_weight_image_floats / launch_weight_split_image), only the A fragments are split at run time; launches the packed ring
 // kernel cannot take (register-staged path, in-workgroup split-K) run the exact f32 MFMA kernels on a.w as before.
-int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof = nullptr, int bf16_operands = 0, const float* w_img = nullptr);
+// lowk_ring (with a weight image only): 1x1 launches over 64 input channels, which conv_route() otherwise keeps on the register-staged
+// exact-f32 kernel (two K steps: more resident workgroups for the epilogues), take the packed split kernel as well.  The training
+// step's dgrad asks for it, so that every stride-1 dgrad of a split-operand step runs one arithmetic; measured on the block-1 conv1
+// dgrads of the 8 x 288 x 512 step (M = 147 456): 26.5 us packed against 27.8 us (64 channels out), 71 against 68 - 74 us (256 out).
+int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof = nullptr, int bf16_operands = 0, const float* w_img = nullptr,
+                bool lowk_ring = false);
 
 // Which kernel a convolution runs: decided ONCE, by conv_route(), for the launcher (conv_launch), for the plan-time launch count
 // (conv_reduce_launches) and for the Profiler's kernel name alike.
@@ -73,7 +78,7 @@ struct ConvRoute {
 // a.in_scale_expected and every condition on a pointer that is bound later (in_scale / in_shift, out_scale, partial; out_floor is
 // read as the plan holds it) counts as met -- `reduce` is then the launcher's for every launch a plan makes.  Reads nothing but its
 // arguments, the once-per-process STABNET_CONV_* switches and the tuning hooks (stabnet_conv_tuning_*).
-ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound);
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound, bool lowk_ring = false /* see conv_launch() */);
 // Kernel name of a PK_KERNEL_CONV_* Profiler kind as rocprofv3 prints the instantiation; null for any other kind.
 const char* conv_prof_kind_name(int kind);
 // Pre-split weight image of a convolution whose weights are [Cout][K] rows (K % 32 == 0): per (64-channel N tile, 32-deep K step)

@@ -203,11 +203,12 @@ static void igemm_variant(const ConvArgs& a, int bm, int bn, int bk, int mode, i
 }
 
 // LDS-DMA ring kernel (conv_ring_kernel.h): no A-operand prologue, stride-free addressing, Cin % 32 == 0, 64x64 tile.
-static bool ring_eligible(const ConvArgs& a, int tile, bool has_prologue) {
+static bool ring_eligible(const ConvArgs& a, int tile, bool has_prologue, bool lowk_ring = false) {
     if (a.rowrun) return true;                              // the row-run A operand exists only in the ring kernel
     // two-step tiles (1x1, K = 64) with a plain epilogue are 2 us faster per launch on the register-staged kernel (more resident
     // workgroups to overlap the 16 KB epilogues: 33.4 vs 35.3 us at M = 57 600, N = 256); the merged shortcut|conv1 launch stays here
-    if (sw().lowk_igemm && a.KH == 1 && a.KW == 1 && a.Cin == 64 && a.x_ld == a.Cin && a.out_floor == nullptr) return false;
+    // (lowk_ring: the training step's dgrad with a weight image -- there the packed split kernel is level with it, conv.h)
+    if (!lowk_ring && sw().lowk_igemm && a.KH == 1 && a.KW == 1 && a.Cin == 64 && a.x_ld == a.Cin && a.out_floor == nullptr) return false;
     return sw().ring && tile == T64x64 && !has_prologue && a.up == 1 && a.Cin % 32 == 0 && !sw().bk16;
 }
 
@@ -266,7 +267,7 @@ static int route_prof_kind(const ConvRoute& r) {
     return split ? split + 3 + r.mode : PK_KERNEL_CONV_KG + r.mode;
 }
 
-ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound) {
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound, bool lowk_ring) {
     const ConvSwitches& s = sw();
     const bool image = operand_mode == 4 && has_image;
     const int op = operand_mode == 4 ? 0 : operand_mode;     // every kernel but the packed one runs mode 4 as exact f32
@@ -274,7 +275,7 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
     const int t = pick_tile(a, splitk_unused);
     const bool t64 = t == T64x64, bk32 = conv_bk(a) == 32;
     const bool has_pro = bound ? a.in_scale != nullptr : a.in_scale_expected != 0;
-    const bool ring = ring_eligible(a, t, has_pro);
+    const bool ring = ring_eligible(a, t, has_pro, lowk_ring && image);
     const bool slabs = !bound || a.splitk == 1 || a.partial != nullptr;
     int kg = t64 ? conv_kgroups(a, op, ring, has_pro) : 1;
     // the packed split kernel has no three-way in-workgroup split-K (60 KiB of ring per group): a ring launch that would split K three
@@ -564,14 +565,14 @@ int launch_weight_split_image(const float* w, int Cout, int K, float* img, hipSt
     return STABNET_OK;
 }
 
-int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands, const float* w_img) {
+int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands, const float* w_img, bool lowk_ring) {
     SN_REQUIRE(a.rowrun || a.Cin % 16 == 0, "conv: Cin=%d must be a multiple of 16 (pad the channels)", a.Cin);
     SN_REQUIRE(!a.rowrun || (a.in_scale == nullptr && a.up == 1 && a.KH <= 8 && cdiv(a.KW * a.Cin, 32) <= 4),
                "conv: row-run operand needs no prologue, KH <= 8 and KW*Cin <= 128");
     SN_REQUIRE(a.Cout % 4 == 0, "conv: Cout=%d must be a multiple of 4", a.Cout);
     SN_REQUIRE(a.splitk >= 1 && a.steps_per_split >= 1 && a.div_hw_mul != 0, "conv: conv_plan() not called");
     SN_REQUIRE(a.splitk == 1 || a.partial != nullptr, "conv: split-K needs a workspace");
-    const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, true);
+    const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, true, lowk_ring);
     SN_REQUIRE(r.family != CONV_IGEMM || a.x_ld == a.Cin, "conv: a strided input (x_ld %d != Cin %d) needs the ring kernel", a.x_ld, a.Cin);
     const bool rec = prof != nullptr && prof->begin(st);
     int rc;

@@ -672,7 +672,7 @@ int pack_dgrad_weights(const float* w, float* wt, int Cout, int KH, int KW, int 
 // re-packed weights wt [Cin][KH][KW][Cout].  residual (optional, same shape as dX) is added (gradient accumulation).
 int dgrad_launch(const float* dy, const float* wt, float* dx, const float* residual, int N, int H, int W, int Cin,
                  int Cout, int KH, int KW, int stride, int pad, float* splitk_ws, size_t splitk_bytes, hipStream_t st,
-                 Prof* prof, const float* wt_img) {
+                 Prof* prof, const float* wt_img, int* packed_out) {
     ConvArgs a{};
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     a.x = dy; a.w = wt; a.y = dx; a.residual = residual;
@@ -686,7 +686,12 @@ int dgrad_launch(const float* dy, const float* wt, float* dx, const float* resid
         return STABNET_ERR_WORKSPACE;
     }
     a.partial = splitk_ws;
-    return conv_launch(a, st, prof, wt_img != nullptr ? 4 : 0, wt_img);
+    if (packed_out != nullptr) {                             // the route conv_launch() is about to take, for the operator tests
+        const int family = conv_route(a, wt_img != nullptr ? 4 : 0, wt_img != nullptr, true, true).family;
+        *packed_out = (family == CONV_PACKED || family == CONV_PACKED_KG2) ? 1 : 0;
+    }
+    // (with an image every launch the packed split kernel can take goes there, the two-step 1x1 ones included: conv.h, lowk_ring)
+    return conv_launch(a, st, prof, wt_img != nullptr ? 4 : 0, wt_img, true);
 }
 
 extern "C" {

@@ -160,6 +160,77 @@ def conv2d_dgrad(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None):
     return dx
 
 
+# ---- convolution backward in the forms a backward stage of the training step runs (the step's own launchers) ----------------
+
+def _wgrad_layers_args(layers):
+    """layers: [(geom, towers, dw_off, bias_off, bias_off2)] with geom = (N, H, W, Cin, Cout, KH, KW, stride, pad) and
+    towers = [(x, dy, in_scale, in_shift)] per tower -> the host arrays of stabnet_conv2d_wgrad_layers."""
+    import ctypes
+    L, T = len(layers), len(layers[0][1])
+    assert all(len(ly[0]) == 9 and len(ly[1]) == T for ly in layers)
+    geom = (ctypes.c_int * (9 * L))(*[int(v) for ly in layers for v in ly[0]])
+    tensors = (ctypes.c_void_p * (4 * T * L))(*[ptr(t) or None for ly in layers for tw in ly[1] for t in tw])
+    dw_off = (ctypes.c_long * L)(*[int(ly[2]) for ly in layers])
+    bias_off = (ctypes.c_long * (2 * L))(*[int(-1 if b is None else b) for ly in layers for b in ly[3:5]])
+    return L, T, geom, tensors, dw_off, bias_off
+
+
+def conv2d_wgrad_layers_workspace_bytes(layers):
+    L, T, geom, _, _, bias_off = _wgrad_layers_args(layers)
+    return int(_lib.lib().stabnet_conv2d_wgrad_layers_workspace_bytes(L, T, geom, bias_off))
+
+
+def conv2d_wgrad_layers(layers, grads, workspace=None):
+    """The weight (and fused bias) gradients of several layers over one or two towers, accumulated into the flat float32 buffer
+    `grads` at each layer's offsets: one launch per layer, one shared reduce table (`layers` as _wgrad_layers_args takes them)."""
+    L, T, geom, tensors, dw_off, bias_off = _wgrad_layers_args(layers)
+    if workspace is None:
+        workspace = torch.empty(max(conv2d_wgrad_layers_workspace_bytes(layers) // 4, 4), dtype=torch.float32, device=grads.device)
+    _lib.call("stabnet_conv2d_wgrad_layers", L, T, geom, tensors, ptr(grads), grads.numel(), dw_off, bias_off, ptr(workspace),
+              workspace.numel() * workspace.element_size(), stream_ptr(grads.device), device=grads.device)
+    return grads
+
+
+def pack_dgrad_weights_table(params, wt, entries):
+    """entries: [(w_off, Cout, K, Cin, stride)] -> the dgrad weights of every entry, one after the other in `wt`, by one launch."""
+    import ctypes
+    L = len(entries)
+    w_off = (ctypes.c_long * L)(*[int(e[0]) for e in entries])
+    dims = (ctypes.c_int * (4 * L))(*[int(v) for e in entries for v in e[1:5]])
+    _lib.call("stabnet_pack_dgrad_weights_table", ptr(params), params.numel(), ptr(wt), wt.numel(), L, w_off, dims,
+              stream_ptr(wt.device), device=wt.device)
+    return wt
+
+
+def conv_weight_split_images_table(w_base, img_base, entries):
+    """entries: [(w_off, img_off, Cout, K)] -> the three-term bf16 images of the [Cout][K] matrices at w_base + w_off, by one launch."""
+    import ctypes
+    L = len(entries)
+    w_off = (ctypes.c_long * L)(*[int(e[0]) for e in entries])
+    img_off = (ctypes.c_long * L)(*[int(e[1]) for e in entries])
+    dims = (ctypes.c_int * (2 * L))(*[int(v) for e in entries for v in e[2:4]])
+    _lib.call("stabnet_conv_weight_split_images_table", ptr(w_base), w_base.numel(), ptr(img_base), img_base.numel(), L, w_off, img_off,
+              dims, stream_ptr(w_base.device), device=w_base.device)
+    return img_base
+
+
+def conv2d_dgrad_split(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None, dx=None, workspace=None):
+    """conv2d_dgrad as the training step runs it with split operands: -> (dx, packed), packed = True if the launch went to a packed
+    split kernel (False: the exact-f32 kernels took it).  residual may be dx (given)."""
+    import ctypes
+    N, H, W, Cin = x_shape
+    Cout, KH, KW, _ = w_ohwi.shape
+    if dx is None:
+        dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    nbytes = int(_lib.lib().stabnet_conv2d_dgrad_split_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dy.device)
+    route = ctypes.c_int(-1)
+    _lib.call("stabnet_conv2d_dgrad_split", ptr(dy), ptr(w_ohwi), ptr(dx), ptr(residual), N, H, W, Cin, Cout, KH, KW, stride, pad,
+              ptr(workspace), workspace.numel() * workspace.element_size(), ctypes.byref(route), stream_ptr(dy.device), device=dy.device)
+    return dx, bool(route.value)
+
+
 # ---- the non-convolution inference layers and the head, one operator per call (the launchers of the plan) ------------------
 
 def pad_channels(x, y):

@@ -378,6 +378,42 @@ int stabnet_conv2d_dgrad(const float* dy, const float* w_ohwi, float* dx, const 
                          int Cin, int Cout, int KH, int KW, int stride, int pad, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* The forms of the above that a backward stage of the training step runs, on the step's own launchers (operator tests).
+ *
+ * stabnet_conv2d_wgrad_layers: the weight gradients of L >= 1 layers over T = 1 or 2 towers as the step takes them: one launch per
+ * layer for all towers (slabs [tower][split]), ONE reduce table and slab cursor shared by the layers, one ordered reduction at
+ * the end (and one whenever the table is full).  Host arrays: geom [L][9] = N, H, W, Cin, Cout, KH, KW, stride, pad;
+ * tensors [L][T][4] = the device pointers x, dy, in_scale, in_shift of each tower (prologue: both vectors for every tower, or none);
+ * dw_off [L]: where the layer's dW (OHWI, ACCUMULATED into) starts in `grads`, in floats; bias_off [L][2] or NULL: where the column
+ * sums of dy are accumulated (-1 = nowhere; the second is another destination of the same sums, the projection shortcut's bias).
+ * Destinations of different layers must not overlap.  workspace: exactly stabnet_conv2d_wgrad_layers_workspace_bytes() are used
+ * (0 for a bad geometry).  STABNET_ERR_BAD_ARG, before anything is written: T outside 1..2, a bias on a layer that is not a 1x1
+ * stride-1 layer with Cout % 256 == 0 on the stride-1 kernel, a destination outside `grads` or not 16-byte aligned, a workspace
+ * that is too small. */
+size_t stabnet_conv2d_wgrad_layers_workspace_bytes(int L, int T, const int* geom, const long* bias_off);
+int stabnet_conv2d_wgrad_layers(int L, int T, const int* geom, const float* const* tensors, float* grads, size_t grads_floats,
+                                const long* dw_off, const long* bias_off, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The dgrad weights of L <= 56 layers by one launch: entry i (host arrays: w_off [L], dims [L][4] = Cout, K, Cin, stride) is
+ * params[w_off ...] OHWI [Cout][K][K][Cin]; its re-pack wt[ci][kh][kw][co] = w[co][K-1-kh][K-1-kw][ci] follows entry i - 1's in
+ * `wt` (3x3 filters of stride-2 layers keep their tap rows kh in the order 1, 0, 2).  STABNET_ERR_BAD_ARG for L > 56. */
+int stabnet_pack_dgrad_weights_table(const float* params, size_t params_floats, float* wt, size_t wt_floats, int L, const long* w_off,
+                                     const int* dims, void* stream);
+
+/* stabnet_conv_weight_split_image for L <= 64 matrices by one launch: matrix i (host arrays: dims [L][2] = Cout, K with K % 32 == 0)
+ * is w_base[w_off[i] ...] as [Cout][K], its image goes to img_base[img_off[i] ...] (offsets in floats, multiples of 4). */
+int stabnet_conv_weight_split_images_table(const float* w_base, size_t w_floats, float* img_base, size_t img_floats, int L,
+                                           const long* w_off, const long* img_off, const int* dims, void* stream);
+
+/* stabnet_conv2d_dgrad as the step runs it in operand mode 4: the table re-pack, the image of the re-packed weights where one
+ * exists (KH * KW * Cout % 32 == 0; no image otherwise, as in the step) and dgrad on the packed split kernels wherever they take
+ * the launch (exact float32 elsewhere).  residual may be dx.  *packed_route (host, optional) = 1 if the launch went to a packed
+ * split kernel, 0 if it ran the exact-f32 kernels. */
+size_t stabnet_conv2d_dgrad_split_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int stabnet_conv2d_dgrad_split(const float* dy, const float* w_ohwi, float* dx, const float* residual, int N, int H, int W, int Cin,
+                               int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t workspace_bytes,
+                               int* packed_route, void* stream);
+
 /* ---- training: the regressor tower (get_resnet(is_training=True) and its autodiff) -------------------------
  * The plan must be created with keep_activations = 1.  One workspace per tower (activations are kept between the
  * forward and the backward of the same tower; the siamese step runs two towers, train_bundle_nobm.py:107-108). */
