@@ -62,7 +62,9 @@ enum ConvFamily {
     CONV_RING_KG,      // ... K groups inside the workgroup: <mode, operand, 3, 0>, or <0, operand, 2, 1> with the fragment prologue
     CONV_RING_PRO,     // ... fragment prologue, <0, operand, 1, 1>
     CONV_PACKED,       // packed split kernel on the pre-split weight image, <mode, 4, 1, pro>
-    CONV_PACKED_KG2    // ... two K groups inside the workgroup, <mode, 4, 2, pro>
+    CONV_PACKED_KG2,   // ... two K groups inside the workgroup, <mode, 4, 2, pro>
+    CONV_ASTAT         // A-stationary packed kernel (conv_astat_kernel.h), conv_astat_f32_kernel<astat_bm>: the wide 1x1 launches over
+                       // K <= 256 that CONV_PACKED would take without a K split -- the same arithmetic, bit for bit
 };
 struct ConvRoute {
     int family;        // ConvFamily
@@ -72,6 +74,7 @@ struct ConvRoute {
     int kg, pro;       // ring kernels: K groups inside the workgroup, fragment prologue
     int reduce;        // 1: a split-K reduce launch follows
     int prof_kind;     // PK_KERNEL_CONV_* (prof.h)
+    int astat_bm;      // CONV_ASTAT: rows of M per workgroup (the kernel's BM: 32 is the one instantiation built)
 };
 // operand_mode: conv_launch's bf16_operands; has_image: the launch comes with a pre-split weight image (mode 4 without one is mode 0).
 // bound = true, the launcher's view: the pointers of `a` are the launch's.  bound = false, the plan-time view: the prologue is

@@ -24,6 +24,7 @@
 
 #include "conv_kernel.h"
 #include "conv_ring_kernel.h"
+#include "conv_astat_kernel.h"
 #include "conv_b2b_kernel.h"
 
 // Sums the split-K partial slabs in a fixed order and applies the epilogue.  One thread per 4 channels.
@@ -107,6 +108,10 @@ struct ConvSwitches {
     int packed_kg2 = env_int("STABNET_CONV_PACKED_KG2", 1), packed_kg3 = env_int("STABNET_CONV_PACKED_KG3", 1);
     int packed_pro = env_int("STABNET_CONV_PACKED_PRO", 1);
     int packed_wgs_per_cu = env_int("STABNET_CONV_PACKED_WGS_PER_CU", 2);                        // 60 KiB of LDS each
+    // A-stationary packed kernel: on / off; the smallest M it takes (0: the rule in conv_route(), never below 2048) and the smallest
+    // Cout (tests lower both to reach the kernel with small shapes)
+    int astat = env_int("STABNET_CONV_ASTAT", 1), astat_min_m = env_int("STABNET_CONV_ASTAT_MIN_M", 0);
+    int astat_min_cout = env_int("STABNET_CONV_ASTAT_MIN_COUT", 256);
     int b2b = env_int("STABNET_CONV_B2B", 1), b2b_wgs_per_cu = env_int("STABNET_CONV_B2B_WGS_PER_CU", 2);   // 80 KB of LDS each
 };
 static const ConvSwitches& sw() {
@@ -257,6 +262,7 @@ static int route_prof_kind(const ConvRoute& r) {
             return PK_KERNEL_CONV_BASE + r.mode * 6 + r.tile * 2 + (r.bk == 32 ? 1 : 0) + (r.nbuf == 1 ? 18 : 0) + 36 * r.operand;
         case CONV_PACKED: return PK_KERNEL_CONV_PACKED + (r.pro ? 3 : r.mode);
         case CONV_PACKED_KG2: return PK_KERNEL_CONV_PACKED + (r.pro ? 6 : 4 + r.mode);
+        case CONV_ASTAT: return PK_KERNEL_CONV_ASTAT;
         default: break;
     }
     // the read-time split modes (2 / 3) have kinds of their own (PK_KERNEL_CONV_SPLIT): their ring, K-group and PRO launches
@@ -291,6 +297,18 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
     // a two-way K split with equal halves runs inside the packed workgroup (no slabs, no reduce launch)
     const bool packed_kg2 = packed && s.packed_kg2 && a.splitk == 2 && !a.rowrun && a.steps_per_split * 2 == conv_total_steps(a);
     if (packed_kg2) kg = 2;
+    // A-stationary packed kernel: plain packed 1x1 launches (no prologue, no K split of any kind) over K <= 256 with many 32-column
+    // blocks to reuse the split A tile on; the training step's dgrad (lowk_ring) keeps its kernels.  Smallest M (measured in the 720p
+    // frame): with fewer M tiles than resident slots N is cut into groups, every group loads and
+    // splits the A tile again, and a wave is left with one or two column blocks -- at M = 3600 that still pays for Cout x K = 1024 x
+    // 256 (21.5 -> 20.4 us) and loses for 512 x 128 (12.1 -> 12.6 us), which wins at M = 14400 (26.5 -> 20.9 us).  The cut between
+    // those two measured points is REASONED, not measured: 8192 rows = 256 M tiles = one per CU, from where on N is no longer cut
+    // (the 1080p frame's 8160 x 512 x 128 launch falls 32 rows short of it and was never tried on this kernel); below 2048 the ring
+    // kernel's N-parallel tiles fill the chip better in any case
+    const int astat_min_m = s.astat_min_m > 0 ? s.astat_min_m : ((long)a.Cout * a.K >= 128 * 1024 ? 2048 : 8192);
+    const bool astat = packed && !packed_pro && !packed_kg2 && kg == 1 && a.splitk == 1 && s.astat && !lowk_ring && !a.rowrun &&
+                       a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.up == 1 && a.K <= 256 && a.Cout >= s.astat_min_cout &&
+                       a.M >= astat_min_m;
 
     ConvRoute r{};
     r.tile = t;
@@ -299,7 +317,11 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
     r.operand = op;
     r.kg = kg;
     r.reduce = (a.splitk > 1 && kg == 1) ? 1 : 0;
-    if (packed) {
+    if (astat) {
+        r.family = CONV_ASTAT;
+        r.operand = 4;
+        r.astat_bm = 32;                                     // (64 rows measured level at K = 128 and do not fit at K = 256: not built)
+    } else if (packed) {
         r.family = packed_kg2 ? CONV_PACKED_KG2 : CONV_PACKED;
         r.operand = 4;
         r.pro = packed_pro ? 1 : 0;
@@ -345,6 +367,12 @@ const char* conv_prof_kind_name(int kind) {
         for (int mode = 0; mode < 3; ++mode) ring(CONV_PACKED, mode, 4, 1, 0);
         ring(CONV_PACKED, 0, 4, 1, 1);
         ring(CONV_PACKED_KG2, 0, 4, 2, 0); ring(CONV_PACKED_KG2, 1, 4, 2, 0); ring(CONV_PACKED_KG2, 0, 4, 2, 1);
+        {
+            ConvRoute r{};
+            r.family = CONV_ASTAT; r.astat_bm = 32;
+            snprintf(buf, sizeof(buf), "conv_astat_f32_kernel<%d>", r.astat_bm);
+            v[route_prof_kind(r)] = buf;
+        }
         for (int i = 0; i < 144; ++i) {                      // <BM, BN, BK, WM, WN, MODE, NBUF, BF16>
             ConvRoute r{};
             r.family = CONV_IGEMM;
@@ -481,6 +509,24 @@ static int launch_ring_route(const ConvRoute& r, const ConvArgs& a, hipStream_t 
     return STABNET_OK;
 }
 
+// The A-stationary packed kernel: grid = (M tiles, N groups).  A group is a multiple of four 32-column blocks (one per wave and pass);
+// N is cut into groups only as far as it takes to fill the resident slots (two workgroups of 64 KB of LDS per CU): every further
+// group splits the A tile once more.
+static int launch_astat(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
+    int cus = 0;
+    if (const int rc = device_cus(cus)) return rc;
+    const int bm = r.astat_bm;
+    SN_REQUIRE(bm == 32 && a.K % 32 == 0 && (size_t)bm * a.K * 6 <= (size_t)SN_ASTAT_A_BYTES && a.splitk == 1,
+               "conv: the A-stationary kernel takes BM %d x K %d without a K split only if the planes fit %d bytes", bm, a.K, SN_ASTAT_A_BYTES);
+    const int mtiles = cdiv(a.M, bm), nblk = 2 * cdiv(a.Cout, 64);
+    int groups = (int)std::min<long>(cdiv(nblk, 4), std::max<long>(1, 2L * usable_cus(cus) / mtiles));
+    groups = cdiv(nblk, 4 * cdiv(cdiv(nblk, groups), 4));            // as the kernel derives the group size from it: no empty group
+    const dim3 grid(mtiles, groups);
+    conv_astat_f32_kernel<32><<<grid, 256, 0, st>>>(a);
+    SN_LAUNCH_CHECK("conv_astat_f32_kernel");
+    return STABNET_OK;
+}
+
 // ---- pre-split weight image (conv.h) -----------------------------------------------------------------------------------
 size_t conv_weight_image_floats(int Cout, int K) { return (size_t)cdiv(Cout, 64) * (size_t)(K / 32) * 3072; }
 
@@ -583,6 +629,12 @@ int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands
             ConvArgs b = a;
             b.w = w_img;
             rc = launch_ring_route(r, b, st);
+            break;
+        }
+        case CONV_ASTAT: {
+            ConvArgs b = a;
+            b.w = w_img;
+            rc = launch_astat(r, b, st);
             break;
         }
         default: rc = launch_ring_route(r, a, st); break;
@@ -826,6 +878,29 @@ int stabnet_conv_weight_split_image(const float* w_ohwi, int Cout, int KH, int K
     return launch_weight_split_image(w_ohwi, Cout, KH * KW * Cin, w_img, (hipStream_t)stream);
 }
 
+/* conv_plan() with the caller's K split (splitk > 0) instead of the planned one; returns the workspace bytes */
+static size_t plan_packed(ConvArgs& a, int splitk) {
+    size_t need = conv_plan(a);
+    if (splitk > 0) {
+        const int total = conv_total_steps(a);
+        a.steps_per_split = cdiv(total, std::min(splitk, total));
+        a.splitk = cdiv(total, a.steps_per_split);
+        need = a.splitk > 1 ? (size_t)a.splitk * a.M * a.Cout * sizeof(float) : 0;
+    }
+    return need;
+}
+
+/* The Profiler kind (stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry: conv_route()'s
+ * plan-time view, with (prologue != 0) or without an input BN + ReLU.  Host only; < 0 on a bad geometry. */
+int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int prologue, int splitk) {
+    ConvArgs a;
+    if (fill_args(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, N, H, W, Cin, Cout, KH, KW, stride, pad, 0))
+        return STABNET_ERR_BAD_ARG;
+    a.in_scale_expected = prologue ? 1 : 0;
+    (void)plan_packed(a, splitk);
+    return conv_route(a, 4, true, false).prof_kind;       // (the call always comes with an image pointer)
+}
+
 int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
                               const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,
                               const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
@@ -837,13 +912,7 @@ int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* 
     int rc = fill_args(a, x, w_ohwi, bias, in_scale, in_shift, residual, res_H, res_W, res_stride, y, N, H, W, Cin, Cout,
                        KH, KW, stride, pad, relu_out);
     if (rc) return rc;
-    size_t need = conv_plan(a);
-    if (splitk > 0) {                                        // the caller's K split instead of the planned one
-        const int total = conv_total_steps(a);
-        a.steps_per_split = cdiv(total, std::min(splitk, total));
-        a.splitk = cdiv(total, a.steps_per_split);
-        need = a.splitk > 1 ? (size_t)a.splitk * a.M * a.Cout * sizeof(float) : 0;
-    }
+    const size_t need = plan_packed(a, splitk);
     if (need > workspace_bytes || (need > 0 && workspace == nullptr)) {
         stabnet_set_error("conv2d_fwd_packed: workspace %zu B < %zu B needed", workspace_bytes, need);
         return STABNET_ERR_WORKSPACE;

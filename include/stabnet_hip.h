@@ -107,6 +107,9 @@ int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* 
                               const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
                               int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* The Profiler kind (see stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry, with
+ * (prologue != 0) or without in_scale / in_shift: which kernel the call runs.  Host only, no GPU needed; < 0 on a bad geometry. */
+int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int prologue, int splitk);
 /* The tail of a slim bottleneck_v2 unit as ONE launch (resnet_v2 `bottleneck`, called at s_net_bundle_nobm.py:252-253; what the
  * inference plan runs for the block-1 / block-2 units of a frame): conv2 (3x3, pad 1, stride 1 | 2, C -> C channels, C = 64 | 128,
  * no bias) -> folded batch_norm (mid_scale, mid_shift) + ReLU -> conv3 (1x1, C -> Cout, Cout % C == 0) with conv2d_fwd_ex's
