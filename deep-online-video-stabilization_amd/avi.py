@@ -96,7 +96,7 @@ class AviMjpegWriter:
 
 
 class AviMjpegReader:
-    """Frame count, fps, size and the JPEG bytes of frame i of an MJPG AVI; frames() decodes with Pillow."""
+    """Frame count, fps, size and the JPEG bytes of frame i of an MJPG AVI; frames() decodes with Pillow, device_clip() on the GPU."""
 
     def __init__(self, path):
         self.path = path
@@ -171,3 +171,9 @@ class AviMjpegReader:
     def frames(self):
         for i in range(len(self)):
             yield self.frame(i)
+
+    def device_clip(self, device="cuda:0"):
+        """The same frames decoded on the device from jpeg(i), bit for bit what frame(i) gives where Pillow is built on libjpeg-turbo
+        (mjpeg.DeviceClip; raises mjpeg.Unsupported for streams outside the device decoder's scope)."""
+        from .mjpeg import DeviceClip
+        return DeviceClip(self, device)

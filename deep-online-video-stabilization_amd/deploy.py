@@ -1,7 +1,8 @@
 """Host side of the online loop (deploy_bundle.py:183-342, the network + feedback part): an on-device history ring
 per stream and ONE C call per frame (StabNetStream); ClipPipeline drives it from a clip in HOST memory with the PCIe copies
 of neighbouring frames overlapped, the colour remap (warpRevBundle2) and, when asked for, the JPEG encoding of the stabilised frame
-(mjpeg.MjpegEncoder) on the device.  Video decode and the container (avi.py) stay on the host."""
+(mjpeg.MjpegEncoder) on the device, and so is the decoding of Motion-JPEG input (mjpeg.MjpegDecoder).  The container (avi.py)
+stays on the host."""
 from __future__ import annotations
 
 import ctypes
@@ -290,10 +291,15 @@ class ClipPipeline:
     out by `up` per frame, never below r_min) writes the slot's 32-byte window, and stabnet_warp_rev_bundle2_win_dev reads it from
     there -- both on the stream that carries the frame's launches, so the ratio advances in frame order; no host round trip.  The
     result carries "window" (float64 [4]: y0, x0, wh, ww) and "fill_stats" (int32 [2]: key, bad nodes; r_safe = key / (h * w), 1 if
-    key >= h * w), downloaded with the slot's other outputs; all_black_win counts as with a fixed window."""
+    key >= h * w), downloaded with the slot's other outputs; all_black_win counts as with a fixed window.
+
+    decoder=mjpeg.MjpegDecoder (needs ingest): the clip is a Motion-JPEG one -- run(clip, ...) with clip.jpeg(t) the compressed frame
+    (mjpeg.DeviceClip).  A slot then uploads the compressed bytes and their parsed description in one copy on the upload stream, and
+    the slot's frame graph starts with the decode launches (csrc/mjpeg_decode.hip) into the buffer the ingest reads.  The frame's
+    status word comes down with its outputs; a frame that does not decode raises StabnetError naming it."""
 
     def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
-                 output: str = "network", window=None, fill=None):
+                 output: str = "network", window=None, fill=None, decoder=None):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
         if slots < 2:
@@ -345,7 +351,8 @@ class ClipPipeline:
                 raise _lib.StabnetError("ClipPipeline: colour=True needs a BGR source, the ingest reads %d channel(s)" % ingest.C)
             stream._bind_ingest(ingest)
             src = (ingest.sh, ingest.sw, ingest.C)
-            self.h_u8 = [pin(src, torch.uint8) for _ in range(slots)]
+            if decoder is None:
+                self.h_u8 = [pin(src, torch.uint8) for _ in range(slots)]
             self.d_u8 = [on((1,) + src, torch.uint8) for _ in range(slots)]
         else:
             self.h_grey = [pin((H, W), torch.float32) for _ in range(slots)]
@@ -375,6 +382,14 @@ class ClipPipeline:
             self.h_fill = [pin((40,), torch.uint8) for _ in range(slots)]
             self.d_win = [b[:32].view(torch.float64) for b in self.d_fill]
             self.d_stats = [b[32:].view(torch.int32) for b in self.d_fill]
+        self.decoder = decoder
+        if decoder is not None:
+            if ingest is None or (decoder.H, decoder.W, decoder.C) != (ingest.sh, ingest.sw, ingest.C):
+                raise _lib.StabnetError("ClipPipeline: decoder=... needs ingest=FrameIngest of the decoder's frame size and channels")
+            self.h_jin = [pin((decoder.in_stride,), torch.uint8) for _ in range(slots)]
+            self.d_jin = [on((1, decoder.in_stride), torch.uint8) for _ in range(slots)]
+            self.d_jstat = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(slots)]
+            self.h_jstat = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(slots)]
         self.enc = None
         if jpeg is not None:
             from .mjpeg import MjpegEncoder
@@ -397,6 +412,9 @@ class ClipPipeline:
     def _frame(self, k: int, maps: bool):
         """Everything frame-shaped of slot k on the current stream: the frame, its results into the slot's buffers."""
         st, H, W = self.st, self.st.H, self.st.W
+        if self.decoder is not None:
+            # the compressed frame in the upload slot -> the raw frame, where an uploaded one would lie
+            self.decoder.enqueue(self.d_jin[k], 1, self.d_u8[k], self.d_jstat[k])
         if self.ingest is not None:
             # cvt_img2train (config.py:6-21) and cv2.resize (deploy_bundle.py:303) of the raw frame in the upload slot
             self.ingest.grey(self.d_u8[k], out=st.cur)
@@ -454,6 +472,8 @@ class ClipPipeline:
 
     def _result(self, slot: int, t: int, maps: bool, raw: bool = True):
         r = {"t": t}
+        if self.decoder is not None:
+            self.decoder.check(self.h_jstat[slot], t)
         if raw:
             r["output"] = self.h_out[slot].numpy()
             if self.colour or self.src_out:
@@ -492,7 +512,10 @@ class ClipPipeline:
         torch.cuda.synchronize(self.dev)
         with torch.cuda.stream(self.s_run):
             if self.ingest is not None:
-                first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.uint8)).to(self.dev)
+                if self.decoder is not None:
+                    first = self.decoder.decode([grey.jpeg(0)])[0]
+                else:
+                    first = torch.from_numpy(np.ascontiguousarray(grey[0], dtype=np.uint8)).to(self.dev)
                 st.start_u8(first, self.ingest)
                 if self.src_out:
                     self.all_black_src.zero_()
@@ -512,14 +535,18 @@ class ClipPipeline:
                 self.host_wait_s += time.perf_counter() - w0
                 emit(self._result(k, pending[k], maps, raw))
                 pending[k] = None
-            if self.ingest is not None:
+            if self.decoder is not None:
+                used = self.decoder.stage(grey.jpeg(t), self.h_jin[k], frame=t)
+            elif self.ingest is not None:
                 self.h_u8[k].numpy()[...] = np.asarray(grey[t]).reshape(self.h_u8[k].shape)
             else:
                 self.h_grey[k].numpy()[...] = grey[t]
                 if self.colour:
                     self.h_bgr[k].numpy()[...] = bgr[t]
             with torch.cuda.stream(self.s_in):
-                if self.ingest is not None:
+                if self.decoder is not None:
+                    self.d_jin[k][0, :used].copy_(self.h_jin[k][:used], non_blocking=True)
+                elif self.ingest is not None:
                     self.d_u8[k].copy_(self.h_u8[k].view(self.d_u8[k].shape), non_blocking=True)
                 else:
                     self.d_grey[k].copy_(self.h_grey[k].view(1, H, W), non_blocking=True)
@@ -551,6 +578,8 @@ class ClipPipeline:
                 if maps:
                     for h, d in zip(self.h_maps, self.d_maps):
                         h[k].copy_(d[k], non_blocking=True)
+                if self.decoder is not None:
+                    self.h_jstat[k].copy_(self.d_jstat[k], non_blocking=True)
                 if self.adaptive:
                     self.h_fill[k].copy_(self.d_fill[k], non_blocking=True)
                 self.ev_down[k].record(self.s_out)

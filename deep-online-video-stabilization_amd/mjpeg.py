@@ -1,5 +1,7 @@
 """Baseline JPEG encoding of uint8 frames on the device (csrc/mjpeg.hip): the last step of the reference's deploy loop
-(deploy_bundle.py:197-198,305: cv2.VideoWriter with fourcc MJPG), done where the stabilised frame already lies."""
+(deploy_bundle.py:197-198,305: cv2.VideoWriter with fourcc MJPG), done where the stabilised frame already lies -- and its mirror
+image, MjpegDecoder (csrc/mjpeg_decode.hip): the frames of a Motion-JPEG clip decoded where the ingest reads them, bit for bit what
+libjpeg-turbo (Pillow, OpenCV) decodes."""
 from __future__ import annotations
 
 import ctypes
@@ -104,3 +106,160 @@ class MjpegEncoder:
         out, nbytes = self.encode(img)
         lens = nbytes.cpu().tolist()
         return [out[i, :n].cpu().numpy().tobytes() for i, n in enumerate(lens)]
+
+
+class Unsupported(_lib.StabnetError):
+    """A JPEG stream the device decoder does not take (progressive, 4:2:2, 12-bit, several scans ...): decode it with Pillow."""
+
+
+def parse(jpeg, blob_ptr=0, blob_cap=0):
+    """stabnet_mjpeg_parse -> dict(H, W, C, subsampling, restart (0: no DRI), intervals, mcus, scan, eoi, blob_bytes, has_dht, blocks).
+    Raises Unsupported for a stream outside the decoder's scope, StabnetError for one that is no complete JPEG stream."""
+    jpeg = bytes(jpeg)
+    info = (ctypes.c_int * 16)()
+    rc = _lib.lib().stabnet_mjpeg_parse(jpeg, len(jpeg), info, blob_ptr, blob_cap)
+    if rc != 0:
+        msg = _lib.lib().stabnet_last_error()
+        msg = msg.decode() if msg else "?"
+        raise (Unsupported if rc == 1 else _lib.StabnetError)(msg)
+    keys = ("H", "W", "C", "subsampling", "restart", "intervals", "mcus", "scan", "eoi", "blob_bytes", "has_dht", "blocks")
+    return dict(zip(keys, list(info)))
+
+
+class MjpegDecoder:
+    """Owns the pinned staging slots, their device copies, the workspace and the status words of one frame geometry.
+
+    decode(list_of_bytes) -> uint8 [N,H,W,3] BGR ([N,H,W] for grey streams) on the device.  Per frame the parsed description (tables,
+    restart-interval offsets: stabnet_mjpeg_parse) and the compressed bytes travel in ONE copy; streams with restart intervals (DRI)
+    are entropy-decoded on the device, one lane per interval.  host_entropy=True (the default for a decoder made from a stream
+    without DRI, which is a single interval): the coefficients are decoded on the CPU by the same routine and uploaded instead; the
+    IDCT and colour stages are the device's either way, so the pixels are the same.
+    enqueue(...) only launches (capturable in a hipGraph); decode(...) also checks the status words, which synchronises."""
+
+    def __init__(self, H: int, W: int, channels: int = 3, subsampling="420", device="cuda:0", batch: int = 1, host_entropy: bool = False,
+                 max_bytes=None):
+        self.H, self.W, self.C = int(H), int(W), int(channels)
+        self.subsampling = int(subsampling) if self.C == 3 else 0
+        self.device = torch.device(device)
+        self.host_entropy = bool(host_entropy)
+        L = _lib.lib()
+        self.blob_max = L.stabnet_mjpeg_decode_blob_bytes(self.H, self.W, self.C, self.subsampling)
+        if self.blob_max == 0:
+            _lib.check(-1, "stabnet_mjpeg_decode_blob_bytes")
+        lay = (ctypes.c_size_t * 10)()
+        _lib.call("stabnet_mjpeg_decode_layout", self.H, self.W, self.C, self.subsampling, lay)
+        self.layout = dict(zip(("frame", "coef", "blocks", "y", "cb", "cr", "yh", "yw", "ch", "cw"), [int(v) for v in lay]))
+        self.coef_count = self.layout["blocks"] * 64
+        # a JPEG frame is rarely longer than the raw one; a longer one makes the slots grow
+        payload = 2 * self.coef_count if self.host_entropy else int(max_bytes or (self.H * self.W * self.C + 4096))
+        self.in_stride = (self.blob_max + payload + 15) & ~15
+        self._batch = 0
+        self._ev = None
+        self._reserve(batch)
+
+    @classmethod
+    def for_stream(cls, jpeg, device="cuda:0", batch: int = 1, host_entropy=None):
+        """A decoder for streams shaped like this one (raises Unsupported)."""
+        i = parse(jpeg)
+        return cls(i["H"], i["W"], i["C"], i["subsampling"] or 420, device=device, batch=batch,
+                   host_entropy=(i["restart"] == 0) if host_entropy is None else host_entropy)
+
+    def _reserve(self, n: int, in_stride=None):
+        if n <= self._batch and in_stride is None:
+            return
+        if self._ev is not None:
+            self._ev.synchronize()
+        n = max(n, self._batch)
+        self.in_stride = in_stride or self.in_stride
+        self.h_in = torch.zeros((n, self.in_stride), dtype=torch.uint8).pin_memory()
+        self.d_in = torch.zeros((n, self.in_stride), dtype=torch.uint8, device=self.device)
+        ws = _lib.lib().stabnet_mjpeg_decode_workspace_bytes(n, self.H, self.W, self.C, self.subsampling)
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
+        self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.out = torch.empty((n, self.H, self.W, self.C), dtype=torch.uint8, device=self.device)
+        self._batch = n
+
+    def slot_bytes(self, nbytes: int) -> int:
+        return self.blob_max + (2 * self.coef_count if self.host_entropy else int(nbytes))
+
+    def stage(self, jpeg, slot, frame=None) -> int:
+        """Parse one stream into a pinned slot (uint8 [>= in_stride]: blob, then the bytes or the host-decoded coefficients).
+        -> the bytes of the slot to upload.  `frame` names the frame in errors."""
+        jpeg = bytes(jpeg)
+        what = "MjpegDecoder" if frame is None else "MjpegDecoder: frame %s" % (frame,)
+        base = slot.data_ptr()
+        try:
+            i = parse(jpeg, base, self.blob_max)
+        except _lib.StabnetError as e:
+            raise type(e)("%s: %s" % (what, e))
+        if (i["H"], i["W"], i["C"], i["subsampling"]) != (self.H, self.W, self.C, self.subsampling):
+            raise _lib.StabnetError("%s is %dx%dx%d sampled %d, the decoder was made for %dx%dx%d sampled %d"
+                                    % (what, i["W"], i["H"], i["C"], i["subsampling"], self.W, self.H, self.C, self.subsampling))
+        used = self.slot_bytes(len(jpeg))
+        if used > slot.numel():
+            raise _lib.StabnetError("%s: %d bytes do not fit the slot of %d" % (what, used, slot.numel()))
+        if self.host_entropy:
+            rc = _lib.lib().stabnet_mjpeg_entropy_host(jpeg, len(jpeg), base, i["blob_bytes"], base + self.blob_max, self.coef_count)
+            if rc != 0:
+                msg = _lib.lib().stabnet_last_error()
+                raise _lib.StabnetError("%s: %s" % (what, msg.decode() if msg else "?"))
+        else:
+            slot[self.blob_max:used].numpy()[...] = np.frombuffer(jpeg, np.uint8)
+        return used
+
+    def enqueue(self, d_in, n: int, out, status, stages: int = 3):
+        """The launches alone, on the current stream: d_in uint8 [n, in_stride] as uploaded, out uint8 [n,H,W,C] (rows and frames at
+        its strides), status int32 [n]."""
+        _lib.call("stabnet_mjpeg_decode", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling, int(self.host_entropy),
+                  ptr(out), out.stride(1) if out is not None else 0, out.stride(0) if out is not None else 0, ptr(status),
+                  ptr(self.workspace), self.workspace.numel(), stages, stream_ptr(self.device), device=self.device)
+
+    def check(self, status, first_frame: int = 0):
+        bad = [(first_frame + i, int(v)) for i, v in enumerate(status.cpu().tolist()) if v]
+        if bad:
+            raise _lib.StabnetError("MjpegDecoder: frame %d does not decode on the device (status %d: 1 data ran out, 2 no such Huffman "
+                                    "code, 4 run past coefficient 63, 8 bad description)" % bad[0])
+
+    def decode(self, jpegs, out=None, first_frame: int = 0, check: bool = True):
+        """jpegs: list of bytes of one geometry.  out: the caller's uint8 [N,H,W,C] device tensor instead of the decoder's own."""
+        if isinstance(jpegs, (bytes, bytearray, memoryview)):
+            jpegs = [jpegs]
+        n = len(jpegs)
+        need = max(self.slot_bytes(len(j)) for j in jpegs)
+        self._reserve(n, ((need + 4095) & ~4095) if need > self.in_stride else None)
+        if self._ev is not None:
+            self._ev.synchronize()                     # the staging slots are free again once their last upload has landed
+        used = [self.stage(j, self.h_in[k], first_frame + k) for k, j in enumerate(jpegs)]
+        for k, u in enumerate(used):
+            self.d_in[k, :u].copy_(self.h_in[k, :u], non_blocking=True)
+        self._ev = torch.cuda.Event()
+        self._ev.record(torch.cuda.current_stream(self.device))
+        if out is None:
+            out = self.out[:n]
+        self.enqueue(self.d_in, n, out.view(n, self.H, self.W, self.C), self.status[:n])
+        if check:
+            self.check(self.status[:n], first_frame)
+        return out if self.C == 3 else out.view(n, self.H, self.W)
+
+
+class DeviceClip:
+    """The frames of an MJPG .avi (avi.AviMjpegReader) decoded on the device as they are asked for: what crosses PCIe per frame is the
+    compressed frame.  device_frame(t) -> uint8 [H,W,3] BGR / [H,W] grey in the decoder's own buffer (valid until the next call):
+    the tensor the ingest reads.  clip[t] is the same frame downloaded (NumPy), for the few places that want it on the host.
+    Raises Unsupported when the first frame is outside the decoder's scope."""
+
+    def __init__(self, reader, device="cuda:0"):
+        self.reader = reader
+        self.decoder = MjpegDecoder.for_stream(reader.jpeg(0), device=device)
+
+    def __len__(self):
+        return len(self.reader)
+
+    def jpeg(self, t: int) -> bytes:
+        return self.reader.jpeg(t)
+
+    def device_frame(self, t: int):
+        return self.decoder.decode([self.reader.jpeg(t)], first_frame=t)[0]
+
+    def __getitem__(self, t: int):
+        return self.device_frame(t).cpu().numpy()

@@ -28,6 +28,10 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     chosen per frame on the GPU (stabnet_fill_window_update, then stabnet_warp_rev_bundle2_win_dev): the largest centred window that
     provably shows no uncovered pixel, never below --fill-min, growing back by at most --fill-up per frame.  All three write
     <name>_fill_window.json.
+  * --decode device: the frames of a Motion-JPEG .avi are not decoded up front with Pillow; per frame the compressed bytes and their
+    parsed description are uploaded in one copy and decoded on the GPU (csrc/mjpeg_decode.hip: bit for bit libjpeg-turbo's pixels)
+    into the buffer the ingest reads.  Implies --ingest device.  A clip the decoder does not take (progressive, 4:2:2 ...) is read
+    with Pillow as with --decode host, and a note says so.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -79,6 +83,9 @@ def build_parser():
     p.add_argument('--ingest', default='host', choices=['host', 'device'],
                    help='where a frame becomes the network input: host = NumPy (two-tap resize, colour only at the network size); device = '
                         'stabnet_amd.ingest.FrameIngest, the reference\'s cv2/PIL chain on the GPU for uint8 clips of any size')
+    p.add_argument('--decode', default='host', choices=['host', 'device'],
+                   help='where the frames of a Motion-JPEG .avi are decoded: host = Pillow, the whole clip up front; device = '
+                        'stabnet_amd.mjpeg.MjpegDecoder, frame by frame on the GPU from the uploaded compressed bytes (implies --ingest device)')
     p.add_argument('--gray-weights', default='cv3', choices=['cv3', 'cv4'],
                    help='--ingest device: fixed-point BGR2GRAY weights of OpenCV 3 (the reference\'s era) or OpenCV 4')
     p.add_argument('--output-size', default='network', choices=['network', 'source'],
@@ -102,6 +109,8 @@ def build_parser():
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if args.decode == 'device':
+        args.ingest = 'device'                                 # the decoded frame lies on the GPU: that is where it is converted
     if args.output_size == 'source' and args.ingest != 'device':
         p.error('--output-size source needs --ingest device: the frame as read must lie on the GPU')
     if args.fill != 'adaptive' and (args.fill_min is not None or args.fill_up is not None):
@@ -190,7 +199,8 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
-    raw = lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
+    # the frame as read on the device: uploaded, or (--decode device) decoded there from its compressed bytes
+    raw = (lambda t: clip.device_frame(t)) if hasattr(clip, 'device_frame') else (lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev))
     if adaptive is not None:
         adaptive.reset()
     if ing is not None:
@@ -268,7 +278,7 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
     black_src = black_win = None
     if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
         pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network', window=window,
-                            fill=fill)
+                            fill=fill, decoder=getattr(clip, 'decoder', None))
         pipe.run(clip, sink=sink, maps=True)
         black_src = pipe.all_black_src if source else None
         black_win = pipe.all_black_win if window is not None else None
@@ -420,9 +430,22 @@ def main():
                 elif os.path.exists(path) and path.lower().endswith('.avi'):
                     from stabnet_amd.avi import AviMjpegReader
                     rd = AviMjpegReader(path)
-                    clips.append((name, np.stack(list(rd.frames()))))
+                    dclip = None
+                    if args.decode == 'device':
+                        from stabnet_amd.mjpeg import Unsupported
+                        try:
+                            dclip = rd.device_clip(dev)
+                        except Unsupported as e:
+                            print('note: --decode device: %s: %s; this clip is decoded on the host with Pillow' % (path, e))
                     if rd.fps > 0:
                         fps_of[name] = rd.fps
+                    if dclip is not None:
+                        clips.append((name, dclip))
+                        print('read %s: %d MJPG frames %dx%d at %.3f fps, decoded on the GPU frame by frame (%s)'
+                              % (path, len(rd), rd.width, rd.height, rd.fps, 'coefficients from the host: the streams have no restart '
+                                 'intervals' if dclip.decoder.host_entropy else 'one lane per restart interval'))
+                        continue
+                    clips.append((name, np.stack(list(rd.frames()))))
                     print('read %s: %d MJPG frames %dx%d at %.3f fps, decoded on the host with Pillow (outside the timed part)'
                           % (path, len(rd), rd.width, rd.height, rd.fps))
                 else:

@@ -664,6 +664,44 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
                          int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
                          size_t workspace_bytes, void* stream, void* prof);
 
+/* ---- in front of the ingest: Motion-JPEG decoding of the frame as read (the reference reads its clips with cv2.VideoCapture) ----
+ * Baseline JPEG (SOF0, 8-bit samples, 8-bit DQT, Huffman tables of the stream's own DHT or Annex K when it has none; grey 1x1,
+ * 4:4:4, 4:2:0; one interleaved scan; any restart interval) decoded on the device, bit for bit what libjpeg-turbo's default decoder
+ * (JDCT_ISLOW, fancy upsampling: what Pillow and OpenCV run) gives: T.81 entropy decoding, dequantisation, jidctint's 13-bit integer
+ * IDCT, + 128, clamp; h2v2 fancy upsampling with the neighbours clamped at the true chroma size ceil(H/2) x ceil(W/2); jdcolor's
+ * 16-bit fixed-point YCbCr -> RGB, stored B, G, R.  RANGE: libjpeg looks the IDCT's result up in a table that wraps (& 1023) for
+ * values no real encoder produces; here it is a plain clamp to [0, 255].
+ * Host side (plain C++, no GPU): stabnet_mjpeg_parse reads SOI, DQT, SOF0, DHT, DRI, SOS and scans for the restart markers.  It
+ * returns 0, STABNET_MJPEG_UNSUPPORTED = 1 (progressive / any SOF but 0, arithmetic coding, 12-bit samples, 16-bit DQT, 4:2:2 or any
+ * other sampling, several scans, Huffman table ids above 1, Adobe / RGB colour, a restart marker count that disagrees with DRI) or -1
+ * (not a JPEG stream, truncated, no EOI; bad arguments).  info16: H, W, C, subsampling (420 | 444; 0 grey), DRI (0: none), intervals,
+ * MCUs, offset of the scan data, offset of EOI, blob bytes, 1 if the stream has a DHT, blocks.  blob (may be NULL: only info16;
+ * 4-byte aligned, blob_cap >= info16[9], at most stabnet_mjpeg_decode_blob_bytes): what the kernels read -- geometry, table
+ * selectors, quantiser tables in natural order, four Huffman tables as 9-bit lookup + maxcode / valptr / huffval, and the offset of
+ * every restart interval.  stabnet_mjpeg_entropy_host decodes the coefficients (int16 [mcu][block of the MCU][64], natural order, not
+ * dequantised; coef_count >= 64 * info16[11]) on the CPU with the routine the entropy kernel runs -- for streams without DRI, which
+ * are one interval; -1 when the scan does not decode.
+ * Device side: slot n of `in` (in + n * in_stride; both 16-byte aligned) holds the blob at offset 0 and, at offset
+ * stabnet_mjpeg_decode_blob_bytes, the whole stream (coef_uploaded = 0) or the coefficients of stabnet_mjpeg_entropy_host
+ * (coef_uploaded = 1: no entropy launch).  out uint8 [N,H,W,C] with rows row_stride bytes and frames frame_stride bytes apart (what
+ * stabnet_ingest_* reads); status int32 [N] on the device: 0, or the OR of 1 (an interval's bytes ran out), 2 (no such Huffman
+ * code), 4 (a run past coefficient 63), 8 (the blob does not fit H, W, C, subsampling or in_stride).  Every byte read is bounded by
+ * its interval, every coefficient index by 63, every block by its interval's count: whatever the bytes are, nothing is read or
+ * written out of bounds; a lane that meets a violation sets the status and stops.  stages: 3 = the frame; 2 = stop after the IDCT
+ * (planes in the workspace), 1 = after the entropy decoding (coefficients in the workspace) -- for tests.  One memset node (status)
+ * and three launches (two with coef_uploaded); nothing allocates, synchronises or copies from the host inside decode. */
+size_t stabnet_mjpeg_decode_blob_bytes(int H, int W, int C, int subsampling);                    /* host; 0 = bad arguments */
+int stabnet_mjpeg_parse(const unsigned char* jpeg, size_t nbytes, int* info16, unsigned char* blob, size_t blob_cap);       /* host */
+int stabnet_mjpeg_entropy_host(const unsigned char* jpeg, size_t nbytes, const unsigned char* blob, size_t blob_bytes, short* coef,
+                               size_t coef_count);                                                                          /* host */
+size_t stabnet_mjpeg_decode_workspace_bytes(int N, int H, int W, int C, int subsampling);
+/* host; layout10: per-frame workspace bytes, offset of the coefficients, blocks, offsets of the Y, Cb, Cr planes, Y rows, Y row
+ * bytes, chroma rows, chroma row bytes (planes at MCU-padded size). */
+int stabnet_mjpeg_decode_layout(int H, int W, int C, int subsampling, size_t* layout10);
+int stabnet_mjpeg_decode(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, int coef_uploaded,
+                         unsigned char* out, size_t row_stride, size_t frame_stride, int* status, void* workspace, size_t workspace_bytes,
+                         int stages, void* stream);
+
 /* ---- in front of the path: frame ingest (config.py:6-21 cvt_img2train; deploy_bundle.py:215,303 cv2.resize) ----
  * A uint8 frame as read from the video, of any size, to the network's grey input and the network-size colour frame.
  * img uint8 [N,sh,sw,C], C = 3 BGR or C = 1 grey, rows row_stride_bytes apart (>= sw*C), frames sh*row_stride_bytes apart.  Every
