@@ -731,6 +731,7 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_REMAP_WIN4: return "remap_win4_kernel";
         case PK_KERNEL_REMAP_WIN_DEV: return "remap_win_dev_kernel";
         case PK_KERNEL_REMAP_WIN4_DEV: return "remap_win4_dev_kernel";
+        case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

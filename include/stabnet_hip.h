@@ -738,6 +738,24 @@ int stabnet_ingest_colour(const unsigned char* img, int N, int sh, int sw, int C
                           const int* xofs_dev, const short* xcoef_dev, const int* yofs_dev, const short* ycoef_dev, unsigned char* out,
                           void* stream, void* prof);
 
+/* ---- behind the decoder, in front of the augmentation: the reference's get_img (get_data_mini_after.py:149-156) ----
+ * Decoded uint8 BGR frames to channels of a training tensor dst float32 [N,H,W,C], one launch per destination tensor:
+ * tf.image.rgb_to_grayscale, convert_image_dtype(float32), resize_images(method=0), - 0.5 with TensorFlow 1.3's arithmetic
+ * [external: restated, not linked]: c = float(u8) * float(1/255); s = (r*0.2989f + g*0.5870f) + b*0.1140f, summed left to right,
+ * every operation rounded to float32, no fused multiply-add; u = uint8(trunc(s * 255.5f)); f = float(u) * float(1/255); the legacy
+ * bilinear resize (align_corners = False, no half-pixel centres): scale = float(in)/float(out), in_y = float(y)*scale,
+ * top = floor(in_y), bottom = in_y < in-1 ? ceil(in_y) : in-1, lerp = in_y - floor(in_y), t = tl + (tr-tl)*xl, b = bl + (br-bl)*xl,
+ * out = t + (b-t)*yl; then - 0.5f.
+ * table_dev: int64 [n_entries][6] ON THE DEVICE = (byte offset of the frame from frames_u8, sh, sw, row stride in bytes, n, c):
+ * the frame (pixels B, G, R, dense; rows strided) that fills dst[n, :, :, c].  One frame may be named by several entries, the
+ * frames of one launch may differ in size.  When two entries name the same (n, c) the later one counts.  An entry whose frame does
+ * not lie inside [frames_u8, frames_u8 + frames_bytes) (or sh, sw > 65536, stride < 3*sw) or whose (n, c) lies outside dst is not
+ * followed: nothing is read or written out of bounds whatever the table holds.  A channel (n, c) that no entry names keeps what it
+ * held.  C <= 32.  One launch, organised by destination (a workgroup owns 256 consecutive pixels of one n and stores them as dense
+ * rows of C floats); no atomics, no workspace, nothing allocates, synchronises or copies from the host: capturable in a hipGraph. */
+int stabnet_tf_get_img(const unsigned char* frames_u8, size_t frames_bytes, const int64_t* table_dev, int n_entries, float* dst, int N,
+                       int H, int W, int C, void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,12 +3,14 @@
 
 Flags of the reference (train_bundle_nobm.py:34-37) are kept; the loop mirrors train_bundle_nobm.py:216-348:
 loss-schedule gates from the step index, display every disp_freq, checkpoint every save_freq, 10 held-out batches
-every test_freq, Adam with the staircase learning rate.  Differences forced by the offline image:
-  * no TFRecord dataset / ImageNet resnet_v2_50.ckpt exists here: batches come from the seeded synthetic generator
-    (SURVEY.md 8d); the ImageNet checkpoint is read (stabnet_amd/tf_checkpoint.py, no TensorFlow needed) when present,
-    otherwise weights start from the seeded initialiser; checkpoints are `.npz` of TF-named variables.
-  * data parallel (new): launch with torchrun, one process per GPU; each rank generates its own shard of the global
-    batch, BN statistics stay local, gradients are summed over RCCL.
+every test_freq, Adam with the staircase learning rate.  --data-dir DIR is the reference's data_dir: DIR/train/ feeds the steps and DIR/test/ the ten
+held-out batches, from the reference's own TFRecord files and numbered JPEG frames (stabnet_amd/dataset.py: the frames are decoded
+and converted on the GPU, the random crop / flip / jitter / masks follow there as with --augment); without it the batches come from
+the seeded synthetic generator.  Differences forced by the offline image:
+  * the ImageNet resnet_v2_50.ckpt is read (stabnet_amd/tf_checkpoint.py, no TensorFlow needed) when present, otherwise weights
+    start from the seeded initialiser; checkpoints are `.npz` of TF-named variables.
+  * data parallel (new): launch with torchrun, one process per GPU; each rank generates (or, with --data-dir, reads) its own
+    shard of the global batch, BN statistics stay local, gradients are summed over RCCL.
 """
 import argparse
 import os
@@ -41,6 +43,12 @@ def build_parser():
     p.add_argument('--augment', action='store_true',
                    help='assemble every batch on the device from un-augmented pair material with the reference\'s random '
                         'crop / flip / contrast / brightness / homography masks (get_data_mini_after.py)')
+    p.add_argument('--data-dir', default=None,
+                   help='the reference\'s data_dir: DIR/train/list.txt and DIR/test/list.txt name TFRecord files whose records name '
+                        'folders of numbered .jpg frames (tools/make_dataset.py writes such a folder).  Implies --augment')
+    p.add_argument('--data-workers', type=int, default=8, help='--data-dir: host threads that read and entropy-decode frames (at most 16)')
+    p.add_argument('--data-prefetch', type=int, default=1, choices=[0, 1],
+                   help='--data-dir: 1 = the host work of the next batch runs beside the training step, 0 = everything inline')
     return p
 
 
@@ -103,13 +111,39 @@ def main():
     st_step = tr.global_step
     training_iter = args.iters if args.iters is not None else cfg.training_iter
 
+    datasets = {}
+
+    def dataset(split):
+        if split not in datasets:
+            from stabnet_amd._lib import StabnetError
+            from stabnet_amd.dataset import PairDataset
+            try:
+                datasets[split] = PairDataset(args.data_dir, split, cfg, H, W, N, device=dev, rank=rank, world=world,
+                                              seed=1234 if split == 'train' else 987654, shuffle=True,
+                                              prefetch=args.data_prefetch, workers=args.data_workers)
+            except StabnetError as e:
+                raise SystemExit('train_bundle_nobm.py: --data-dir %s: %s' % (args.data_dir, e))
+            if rank == 0:
+                print('note: %s/%s: %d records, %d for this rank' % (args.data_dir, split, len(datasets[split].records),
+                                                                      len(datasets[split].shard)))
+        return datasets[split]
+
     def batch_for(step, split):
         seed = (1234 if split == 'train' else 987654) + step * world + rank       # every rank its own shard
-        if args.augment:
+        if args.data_dir is not None or args.augment:
             from stabnet_amd import data
-            raw = synthetic.make_raw_pairs(cfg, N, H, W, seed)
+            if args.data_dir is not None:
+                from stabnet_amd._lib import StabnetError
+                try:
+                    raw = dataset(split).next_batch()
+                except StabnetError as e:
+                    for d in datasets.values():
+                        d.close()
+                    raise SystemExit('train_bundle_nobm.py: --data-dir %s: %s' % (args.data_dir, e))
+            else:
+                raw = synthetic.make_raw_pairs(cfg, N, H, W, seed)
             para, jitter, Hs = data.draw(np.random.default_rng(seed), cfg, N, H, W)
-            t = lambda k: torch.from_numpy(raw[k]).to(dev)
+            t = lambda k: raw[k] if torch.is_tensor(raw[k]) else torch.from_numpy(raw[k]).to(dev)
             x1, y1, x2, y2, flow, fm1, mk1, fm2, mk2 = data.augment_pairs(
                 t('stable'), t('unstable'), t('flow'), t('matches1'), raw['n1'], t('matches2'), raw['n2'], para, jitter, Hs, cfg)
             return {'x1': x1, 'y1': y1, 'x2': x2, 'y2': y2, 'flow': flow, 'matches1': fm1, 'mask1': mk1, 'matches2': fm2,
@@ -154,6 +188,8 @@ def main():
         tot_train_time += time.time() - t1
     if rank == 0 and tr.last is not None:
         print('final loss', tr.losses()['total_loss'])
+    for d in datasets.values():
+        d.close()
     if pg is not None:
         import torch.distributed as dist
         dist.destroy_process_group()
