@@ -1,9 +1,8 @@
 // Colour-frame remap with smoothed maps (deploy_bundle.py:136-146 warpRevBundle2), gfx950.
 // The reference does this on the host with OpenCV after every sess.run; here the maps never leave the device:
 //   map_shrink_kernel : cv2.resize(map, (W/rate, H/rate)) INTER_LINEAR (half-pixel centres, float32, h-pass then v-pass)
-//   remap_color_kernel: cv2.resize back to (W, H) fused with (m+1)/2*size and cv2.remap(..., INTER_LINEAR) on the uint8
-//                       BGR frame: OpenCV's FIXED-POINT bilinear path (1/32 px coordinates, 15-bit integer weight table,
-//                       (sum + 16384) >> 15), BORDER_CONSTANT 0 -- integer arithmetic, bit-exact against the oracle
+//   remap_*_kernel    : cv2.resize back up fused with (m+1)/2*size and cv2.remap(..., INTER_LINEAR) on the uint8 frame: OpenCV's
+//                       FIXED-POINT bilinear path, BORDER_CONSTANT 0 -- integer arithmetic, bit-exact against the oracle
 // Float32 op order of the two resizes as oracle/stabnet_oracle.py: cv_resize_linear_f32 (-ffp-contract=off).  HBM-bound:
 // per frame 8*H*W (maps in) + 3*H*W (frame, gathered) + 3*H*W (out) bytes.
 #include <cmath>
@@ -45,128 +44,13 @@ __global__ __launch_bounds__(256) void map_shrink_kernel(const float* __restrict
     small_maps[((size_t)n * 2 + 1) * h * w + q] = cv_resize_at(y_map + (size_t)n * H * W, W, tx, ty);
 }
 
-__global__ __launch_bounds__(256) void remap_color_kernel(const unsigned char* __restrict__ img, const float* __restrict__ small_maps,
-                                                          int H, int W, int C, int h, int w, unsigned char* __restrict__ out,
-                                                          float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    const int n = blockIdx.y;
-    if (q >= H * W) return;
-    const int y = q / W, x = q - y * W;
-    const Taps1D tx = cv_taps(x, w, (double)w / W), ty = cv_taps(y, h, (double)h / H);
-    const float xs = cv_resize_at(small_maps + ((size_t)n * 2 + 0) * h * w, w, tx, ty);
-    const float ys = cv_resize_at(small_maps + ((size_t)n * 2 + 1) * h * w, w, tx, ty);
-    const float px = (xs + 1.0f) / 2.0f * (float)W;                 // deploy_bundle.py:142-143
-    const float py = (ys + 1.0f) / 2.0f * (float)H;
-    if (px_out != nullptr) { px_out[(size_t)n * H * W + q] = px; py_out[(size_t)n * H * W + q] = py; }
-    // OpenCV's 8-bit bilinear remap (imgwarp.cpp: RemapInvoker + remapBilinear<FixedPtCast<int, uchar, 15>, RemapVec_8u, short>;
-    // oracle cv_remap_linear_u8 / cv_bilinear_tab_i): coordinates quantised to 1/32 px (cvRound: half to even), integer part
-    // saturated to int16, 15-bit integer weights wy[k1] * wx[k2] * 32768 -- all exact multiples of 32 except the table's entry
-    // (0, 0), whose weight 1.0 saturates to 32767 and whose repair loop puts the missing 1 on tap [1][1] -- integer accumulate,
-    // (sum + 16384) >> 15.  (A float beyond the int range is out of frame either way: clamped before the conversion.)
-    const float qx = fminf(fmaxf(px * 32.0f, -2.0e9f), 2.0e9f), qy = fminf(fmaxf(py * 32.0f, -2.0e9f), 2.0e9f);
-    const int sx = (qx == qx) ? (int)rintf(qx) : -2000000000, sy = (qy == qy) ? (int)rintf(qy) : -2000000000;
-    const int ix = min(max(sx >> 5, -32768), 32767), iy = min(max(sy >> 5, -32768), 32767);
-    const int fx = sx & 31, fy = sy & 31;
-    int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-    if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
-    const unsigned char* im = img + (size_t)n * H * W * C;
-    const bool x0 = ix >= 0 && ix < W, x1 = ix + 1 >= 0 && ix + 1 < W, y0 = iy >= 0 && iy < H, y1 = iy + 1 >= 0 && iy + 1 < H;
-    for (int c = 0; c < C; ++c) {
-        const int v00 = (x0 && y0) ? (int)im[((size_t)iy * W + ix) * C + c] : 0;
-        const int v01 = (x1 && y0) ? (int)im[((size_t)iy * W + ix + 1) * C + c] : 0;
-        const int v10 = (x0 && y1) ? (int)im[((size_t)(iy + 1) * W + ix) * C + c] : 0;
-        const int v11 = (x1 && y1) ? (int)im[((size_t)(iy + 1) * W + ix + 1) * C + c] : 0;
-        const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-        out[((size_t)n * H * W + q) * C + c] = (unsigned char)min(max(acc, 0), 255);
-    }
-}
-
-// Four consecutive pixels per thread (C == 3, W % 4 == 0: the colour frames of the path).  The byte traffic of the one-pixel kernel
-// above -- 12 one-byte gathers and 3 one-byte stores per pixel -- becomes 4-byte traffic: the two taps of a row are 6 CONTIGUOUS bytes
-// (BGR BGR), fetched as the three aligned dwords that cover them and funnel-shifted into place; the 12 output bytes of the four pixels
-// leave as three 4-byte stores of one thread (12 contiguous bytes).  Same integer arithmetic, same results (tests/test_remap_gpu.py: exact against the oracle).
-__device__ __forceinline__ unsigned long long remap_load6(const unsigned char* __restrict__ im, long b, long total) {
-    // bytes b .. b+5 of the frame in the low 48 bits (b >= 0, b + 3 <= total: at least the first tap is in the buffer): the three
-    // aligned dwords that cover them (b may sit at byte 3 of its dword), funnel-shifted; the last pixels of the frame, whose third
-    // dword would lie past the buffer, take the bytes one by one
-    const long al = b & ~3L;
-    const int sh = 8 * (int)(b & 3);
-    if (al + 12 <= total) {
-        const unsigned* p = reinterpret_cast<const unsigned*>(im + al);
-        const unsigned d0 = p[0], d1 = p[1], d2 = p[2];
-        const unsigned lo = (unsigned)(((((unsigned long long)d1) << 32) | d0) >> sh), hi = (unsigned)(((((unsigned long long)d2) << 32) | d1) >> sh);
-        return (((unsigned long long)hi) << 32) | lo;
-    }
-    unsigned long long r = 0ull;
-    for (int k = 0; k < 6; ++k)
-        if (b + k < total) r |= ((unsigned long long)im[b + k]) << (8 * k);
-    return r;
-}
-
-__global__ __launch_bounds__(256) void remap_color4_kernel(const unsigned char* __restrict__ img, const float* __restrict__ small_maps,
-                                                           int H, int W, int h, int w, unsigned char* __restrict__ out,
-                                                           float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int q4 = blockIdx.x * 256 + threadIdx.x;           // group of four pixels
-    const int n = blockIdx.y;
-    const int W4 = W >> 2;
-    if (q4 >= H * W4) return;
-    const int y = q4 / W4, x0 = (q4 - y * W4) * 4;
-    const Taps1D ty = cv_taps(y, h, (double)h / H);
-    const float* mx = small_maps + ((size_t)n * 2 + 0) * h * w;
-    const float* my = small_maps + ((size_t)n * 2 + 1) * h * w;
-    const unsigned char* im = img + (size_t)n * H * W * 3;
-    const long total = (long)H * W * 3;
-    unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
-    float pxs[4], pys[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const Taps1D tx = cv_taps(x0 + e, w, (double)w / W);
-        const float xs = cv_resize_at(mx, w, tx, ty), ys = cv_resize_at(my, w, tx, ty);
-        const float px = (xs + 1.0f) / 2.0f * (float)W;                 // deploy_bundle.py:142-143
-        const float py = (ys + 1.0f) / 2.0f * (float)H;
-        pxs[e] = px; pys[e] = py;
-        const float qx = fminf(fmaxf(px * 32.0f, -2.0e9f), 2.0e9f), qy = fminf(fmaxf(py * 32.0f, -2.0e9f), 2.0e9f);
-        const int sx = (qx == qx) ? (int)rintf(qx) : -2000000000, sy = (qy == qy) ? (int)rintf(qy) : -2000000000;
-        const int ix = min(max(sx >> 5, -32768), 32767), iy = min(max(sy >> 5, -32768), 32767);
-        const int fx = sx & 31, fy = sy & 31;
-        int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-        if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
-        const bool vx0 = ix >= 0 && ix < W, vx1 = ix + 1 >= 0 && ix + 1 < W, vy0 = iy >= 0 && iy < H, vy1 = iy + 1 >= 0 && iy + 1 < H;
-        // rows iy and iy + 1: 6 bytes from pixel max(ix, 0) on (ix == -1: the first three bytes are tap 1)
-        unsigned long long r0 = 0ull, r1 = 0ull;
-        const int cx = max(ix, 0);
-        if ((vx0 || vx1) && vy0) r0 = remap_load6(im, ((long)iy * W + cx) * 3, total);
-        if ((vx0 || vx1) && vy1) r1 = remap_load6(im, ((long)(iy + 1) * W + cx) * 3, total);
-        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                  // tap 0 out of frame on the left: what was loaded is tap 1
-        const unsigned long long m0 = vx0 ? 0xffffffull : 0ull, m1 = vx1 ? 0xffffff000000ull : 0ull;
-        r0 &= (vy0 ? (m0 | m1) : 0ull);
-        r1 &= (vy1 ? (m0 | m1) : 0ull);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int v00 = (int)((r0 >> (8 * c)) & 0xff), v01 = (int)((r0 >> (24 + 8 * c)) & 0xff);
-            const int v10 = (int)((r1 >> (8 * c)) & 0xff), v11 = (int)((r1 >> (24 + 8 * c)) & 0xff);
-            const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-            const unsigned o = (unsigned)min(max(acc, 0), 255);
-            const int byte = e * 3 + c;
-            ob[byte >> 2] |= o << (8 * (byte & 3));
-        }
-    }
-    const size_t pix = (size_t)n * H * W + (size_t)y * W + x0;
-    unsigned* op = reinterpret_cast<unsigned*>(out + pix * 3);
-    op[0] = ob[0]; op[1] = ob[1]; op[2] = ob[2];
-    if (px_out != nullptr) {
-        *reinterpret_cast<float4*>(px_out + pix) = make_float4(pxs[0], pxs[1], pxs[2], pxs[3]);
-        *reinterpret_cast<float4*>(py_out + pix) = make_float4(pys[0], pys[1], pys[2], pys[3]);
-    }
-}
-
-// ---- the same remap at SOURCE resolution: the frame as read ([SH, SW, C], any size, strided rows) warped by the network-size maps ----
-// small = cv2.resize(map, (w, h)) (map_shrink_kernel, as above); big = cv2.resize(small, (SW, SH)); network-pixel coordinate
-// u = (big + 1) / 2 * size as above; source-pixel coordinate under cv2's half-pixel convention p = u * s + c with s = SW / W and
+// ---- the remap itself, stated once for all eight kernels below ----
+// small = cv2.resize(map, (w, h)) (map_shrink_kernel); big = cv2.resize(small, (SW, SH)); network-pixel coordinate
+// u = (big + 1) / 2 * size; then cv2.remap(..., INTER_LINEAR) on the uint8 frame.  At SOURCE resolution (the frame as read: [SH, SW, C],
+// any size, strided rows) the source-pixel coordinate under cv2's half-pixel convention is p = u * s + c with s = SW / W and
 // c = 0.5 * SW / W - 0.5 (the reference's normalised coordinate counts pixel INDICES: without c an identity mesh would shift the picture
-// by 0.5 * (SW / W - 1) source pixels); both constants rounded once from double by the host, multiply then add, not fused.  Then the
-// fixed-point cv2.remap of remap_color_kernel.  With SH, SW == H, W: s = 1, c = 0 and every bit is stabnet_warp_rev_bundle2's.
-// One workgroup per row segment (grid = segments x SH x N): the vertical taps and the two small-map rows are wave-uniform.
+// by 0.5 * (SW / W - 1) source pixels); both constants rounded once from double by the host, multiply then add, not fused.  With
+// SH, SW == H, W: s = 1, c = 0, and the network-size kernels (AFFINE = false) skip the step: p is u's own bits.
 struct SrcRemapArgs {
     int SH, SW, C, H, W, h, w;
     float fW, fH, sx, cx, sy, cy;            // (float)W, (float)H; float32(SW / W), float32(0.5 * SW / W - 0.5), likewise y
@@ -176,14 +60,17 @@ struct SrcRemapArgs {
 
 struct SrcCoord { float px, py; int qx, qy; };   // qx, qy: the coordinate in 1/32 px, rounded half to even
 
-__device__ __forceinline__ SrcCoord remap_src_coord(const float* __restrict__ mx, const float* __restrict__ my, const SrcRemapArgs& a,
-                                                    const Taps1D& tx, const Taps1D& ty) {
+// The coordinate cv2.remap receives, and OpenCV's quantisation of it to 1/32 px (cvRound: half to even).  (A float beyond the int range
+// is out of frame either way: clamped before the conversion.)
+template <bool AFFINE = true>
+__device__ __forceinline__ SrcCoord remap_src_coord(const float* __restrict__ mx, const float* __restrict__ my,
+        const SrcRemapArgs& a, const Taps1D& tx, const Taps1D& ty) {
     const float xs = cv_resize_at(mx, a.w, tx, ty), ys = cv_resize_at(my, a.w, tx, ty);
     const float ux = (xs + 1.0f) / 2.0f * a.fW;                     // deploy_bundle.py:142-143
     const float uy = (ys + 1.0f) / 2.0f * a.fH;
     SrcCoord c;
-    c.px = ux * a.sx + a.cx;
-    c.py = uy * a.sy + a.cy;
+    c.px = AFFINE ? ux * a.sx + a.cx : ux;
+    c.py = AFFINE ? uy * a.sy + a.cy : uy;
     const float qx = fminf(fmaxf(c.px * 32.0f, -2.0e9f), 2.0e9f), qy = fminf(fmaxf(c.py * 32.0f, -2.0e9f), 2.0e9f);
     c.qx = (qx == qx) ? (int)rintf(qx) : -2000000000;
     c.qy = (qy == qy) ? (int)rintf(qy) : -2000000000;
@@ -195,40 +82,50 @@ __device__ __forceinline__ bool remap_src_black(const SrcCoord& c, int SH, int S
     return c.qx < 0 || c.qx > 32 * (SW - 1) || c.qy < 0 || c.qy > 32 * (SH - 1);
 }
 
-// grid (cdiv(SW, blockDim.x), SH, N): one pixel per thread, any C, width, stride and alignment; byte loads and stores.
-__global__ __launch_bounds__(256) void remap_src_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a,
-                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
-    if (x >= a.SW) return;
-    const int SH = a.SH, SW = a.SW, C = a.C;
-    const Taps1D tx = cv_taps(x, a.w, a.xscale), ty = cv_taps(y, a.h, a.yscale);
-    const size_t hw = (size_t)a.h * a.w;
-    const SrcCoord c = remap_src_coord(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
-    const size_t pix = ((size_t)n * SH + y) * SW + x;
-    if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
-    const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
+// OpenCV's 8-bit bilinear remap (imgwarp.cpp: RemapInvoker + remapBilinear<FixedPtCast<int, uchar, 15>, RemapVec_8u, short>;
+// oracle cv_remap_linear_u8 / cv_bilinear_tab_i) of a coordinate in 1/32 px: integer part saturated to int16, 15-bit integer weights
+// wy[k1] * wx[k2] * 32768 -- all exact multiples of 32 except the table's entry (0, 0), whose weight 1.0 saturates to 32767 and whose
+// repair loop puts the missing 1 on tap [1][1] -- BORDER_CONSTANT 0 for the taps outside the frame, integer accumulate, (sum + 16384) >> 15.
+struct RemapTaps { int ix, iy, w00, w01, w10, w11; };          // top-left pixel, the weights of taps [row][column]
+__device__ __forceinline__ RemapTaps remap_taps(const SrcCoord& c) {
+    RemapTaps t; t.ix = min(max(c.qx >> 5, -32768), 32767); t.iy = min(max(c.qy >> 5, -32768), 32767);
     const int fx = c.qx & 31, fy = c.qy & 31;
-    int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-    if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
+    t.w00 = (32 - fy) * (32 - fx) * 32; t.w01 = (32 - fy) * fx * 32; t.w10 = fy * (32 - fx) * 32; t.w11 = fy * fx * 32;
+    if ((fx | fy) == 0) { t.w00 = 32767; t.w11 = 1; }
+    return t;
+}
+
+__device__ __forceinline__ unsigned remap_blend(int v00, int v01, int v10, int v11, int w00, int w01, int w10, int w11) {
+    const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+    return (unsigned)min(max(acc, 0), 255);
+}
+
+// One pixel: output pixel `pix` of stream n, its taps into the small maps given.  Any C, width, stride and alignment; byte loads and stores.
+template <bool AFFINE>
+__device__ __forceinline__ void remap_pixel(const unsigned char* __restrict__ src, const SrcRemapArgs& a,
+        const float* __restrict__ small_maps, int n, const Taps1D& tx, const Taps1D& ty, size_t pix, unsigned char* __restrict__ out,
+        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int C = a.C;
+    const size_t hw = (size_t)a.h * a.w;
+    const SrcCoord c = remap_src_coord<AFFINE>(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
+    if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
+    const RemapTaps t = remap_taps(c);
+    const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
     const unsigned char* im = src + (size_t)n * a.frame_stride;
-    const bool x0 = ix >= 0 && ix < SW, x1 = ix + 1 >= 0 && ix + 1 < SW, y0 = iy >= 0 && iy < SH, y1 = iy + 1 >= 0 && iy + 1 < SH;
     for (int ch = 0; ch < C; ++ch) {
-        const int v00 = (x0 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)ix * C + ch] : 0;
-        const int v01 = (x1 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
-        const int v10 = (x0 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)ix * C + ch] : 0;
-        const int v11 = (x1 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
-        const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-        out[pix * C + ch] = (unsigned char)min(max(acc, 0), 255);
+        const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)t.ix * C + ch] : 0;
+        const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
+        const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)t.ix * C + ch] : 0;
+        const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
+        out[pix * C + ch] = (unsigned char)remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
     }
-    if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix] += 1;
+    if (black_count != nullptr && remap_src_black(c, a.SH, a.SW)) black_count[pix] += 1;
 }
 
 // bytes p .. p+5 in the low 48 bits (lo <= p, p + 3 <= hi; [lo, hi) = the frame's own bytes): the three aligned dwords that cover
-// them where all three lie inside [lo, hi), funnel-shifted; bytes otherwise (a frame that starts or ends inside a dword: any base
-// pointer and row stride are accepted, and nothing outside the frame is read)
-__device__ __forceinline__ unsigned long long remap_src_load6(const unsigned char* __restrict__ p, const unsigned char* lo,
-                                                              const unsigned char* hi) {
+// them where all three lie inside [lo, hi) (p may sit at byte 3 of its dword), funnel-shifted; bytes otherwise (a frame that starts or
+// ends inside a dword: any base pointer and row stride are accepted, and nothing outside the frame is read)
+__device__ __forceinline__ unsigned long long remap_src_load6(const unsigned char* __restrict__ p, const unsigned char* lo, const unsigned char* hi) {
     const uintptr_t al = (uintptr_t)p & ~(uintptr_t)3;
     const int sh = 8 * (int)((uintptr_t)p & 3);
     if (al >= (uintptr_t)lo && al + 12 <= (uintptr_t)hi) {
@@ -243,28 +140,29 @@ __device__ __forceinline__ unsigned long long remap_src_load6(const unsigned cha
     return r;
 }
 
-// grid (cdiv(SW / 4, blockDim.x), SH, N): four consecutive pixels per thread, C == 3, SW % 4 == 0, out 4-byte aligned (px_out / py_out
-// 16-byte): the taps of a row as dwords through the funnel shift, the 12 output bytes as three dwords (remap_color4_kernel's traffic).
-__global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a,
-                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
-    if (x0 >= a.SW) return;
+// Four consecutive output pixels from `pix` on (C == 3, the row's width % 4 == 0, out 4-byte aligned, px_out / py_out 16-byte: the colour
+// frames of the path); taps_x(e) gives the horizontal taps of pixel e.  The byte traffic of remap_pixel -- 12 one-byte gathers and 3
+// one-byte stores per pixel -- becomes 4-byte traffic: the two taps of a row are 6 CONTIGUOUS bytes (BGR BGR), fetched through
+// remap_src_load6 (the source may have any width, stride and alignment); the 12 output bytes of the four pixels leave as three 4-byte
+// stores of one thread.  Same integer arithmetic, same results.
+template <bool AFFINE, class TapsX>
+__device__ __forceinline__ void remap_pixel4(const unsigned char* __restrict__ src, const SrcRemapArgs& a,
+        const float* __restrict__ small_maps, int n, TapsX taps_x, const Taps1D& ty, size_t pix, unsigned char* __restrict__ out,
+        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
     const int SH = a.SH, SW = a.SW;
-    const Taps1D ty = cv_taps(y, a.h, a.yscale);
     const size_t hw = (size_t)a.h * a.w;
     const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
     const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
     const unsigned char* im = src + (size_t)n * a.frame_stride;
     const unsigned char* end = im + (size_t)(SH - 1) * a.row_stride + (size_t)SW * 3;
-    const size_t pix = ((size_t)n * SH + y) * SW + x0;
     unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
     float pxs[4], pys[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const Taps1D tx = cv_taps(x0 + e, a.w, a.xscale);
-        const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
+        const SrcCoord c = remap_src_coord<AFFINE>(mx, my, a, taps_x(e), ty);
         pxs[e] = c.px; pys[e] = c.py;
+        // remap_taps' statements in place: through the function the compiler orders the last pixel's instructions differently, and
+        // remap_win4_dev_kernel then measured half a timer tick over the parent's range (profiles/remap_refactor_ab.txt)
         const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
         const int fx = c.qx & 31, fy = c.qy & 31;
         int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
@@ -275,16 +173,14 @@ __global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __
         const int cx = max(ix, 0);
         if ((vx0 || vx1) && vy0) r0 = remap_src_load6(im + (size_t)iy * a.row_stride + (size_t)cx * 3, im, end);
         if ((vx0 || vx1) && vy1) r1 = remap_src_load6(im + (size_t)(iy + 1) * a.row_stride + (size_t)cx * 3, im, end);
-        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                  // tap 0 out of frame on the left: what was loaded is tap 1
+        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                // tap 0 out of frame on the left: what was loaded is tap 1
         const unsigned long long m0 = vx0 ? 0xffffffull : 0ull, m1 = vx1 ? 0xffffff000000ull : 0ull;
         r0 &= (vy0 ? (m0 | m1) : 0ull);
         r1 &= (vy1 ? (m0 | m1) : 0ull);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const int v00 = (int)((r0 >> (8 * ch)) & 0xff), v01 = (int)((r0 >> (24 + 8 * ch)) & 0xff);
-            const int v10 = (int)((r1 >> (8 * ch)) & 0xff), v11 = (int)((r1 >> (24 + 8 * ch)) & 0xff);
-            const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-            const unsigned o = (unsigned)min(max(acc, 0), 255);
+            const unsigned o = remap_blend((int)((r0 >> (8 * ch)) & 0xff), (int)((r0 >> (24 + 8 * ch)) & 0xff), (int)((r1 >> (8 * ch)) & 0xff),
+                                           (int)((r1 >> (24 + 8 * ch)) & 0xff), w00, w01, w10, w11);
             const int byte = e * 3 + ch;
             ob[byte >> 2] |= o << (8 * (byte & 3));
         }
@@ -298,120 +194,71 @@ __global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __
     }
 }
 
-// ---- the same remap through a WINDOW of the stabilised frame: crop and zoom in the one gather ----
+// ---- at the network's size: img [N, H, W, C] dense, a built for SH, SW == H, W (no coverage count).  Flat grid (cdiv(H * W, 256), N) ----
+__global__ __launch_bounds__(256) void remap_color_kernel(const unsigned char* __restrict__ img, SrcRemapArgs a, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int q = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
+    if (q >= a.SH * a.SW) return;
+    const int y = q / a.SW, x = q - y * a.SW;
+    remap_pixel<false>(img, a, small_maps, n, cv_taps(x, a.w, a.xscale), cv_taps(y, a.h, a.yscale), (size_t)n * a.SH * a.SW + q, out, nullptr,
+                       px_out, py_out);
+}
+
+// grid (cdiv(H * W / 4, 256), N): C == 3, W % 4 == 0, img and out 4-byte aligned (px_out / py_out 16-byte)
+__global__ __launch_bounds__(256) void remap_color4_kernel(const unsigned char* __restrict__ img, SrcRemapArgs a,
+        const float* __restrict__ small_maps, unsigned char* __restrict__ out, float* __restrict__ px_out, float* __restrict__ py_out) {
+    const int q4 = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y, W4 = a.SW >> 2;           // q4: group of four pixels
+    if (q4 >= a.SH * W4) return;
+    const int y = q4 / W4, x0 = (q4 - y * W4) * 4;
+    remap_pixel4<false>(img, a, small_maps, n, [&](int e) { return cv_taps(x0 + e, a.w, a.xscale); }, cv_taps(y, a.h, a.yscale),
+                        (size_t)n * a.SH * a.SW + (size_t)y * a.SW + x0, out, nullptr, px_out, py_out);
+}
+
+// ---- at SOURCE resolution, and through a WINDOW of the stabilised frame (crop and zoom in the one gather) ----
 // Output pixel (i, j) of OH x OW is the stabilised frame (SH x SW) sampled at the position, in pixel-edge units,
 //   ex = x0 + (j + 0.5) * (ww / OW),  ey = y0 + (i + 0.5) * (wh / OH)        (double; quotient, multiply, add)
-// and that position takes the place of d + 0.5 in the taps of the resize back up (cv_taps_at); from there on every step is
-// remap_src_kernel's.  With the whole-frame window (0, 0, SH, SW) at OH, OW == SH, SW, ex = j + 0.5 exactly: every bit is
-// stabnet_warp_rev_bundle2_src's; with an integer window at zoom 1, ex = x0 + j + 0.5 exactly: the slice of that result.
-// Coverage is counted at the OUTPUT pixel.  Grid = row segments x OH x N: the vertical taps are wave-uniform.
-struct WinRemapArgs {
-    SrcRemapArgs a;
-    int OH, OW;
-    double x0, y0, xstep, ystep;             // xstep = ww / OW, ystep = wh / OH
-};
+// and that position takes the place of d + 0.5 in the taps of the resize back up (cv_taps_at); every other step is the same.  With the
+// whole-frame window (0, 0, SH, SW) at OH, OW == SH, SW, ex = j + 0.5 exactly: every bit is stabnet_warp_rev_bundle2_src's (whose
+// kernels take d + 0.5 itself: WINDOW = false); with an integer window at zoom 1, ex = x0 + j + 0.5 exactly: the slice of that result.
+// And _src with SH, SW == H, W is stabnet_warp_rev_bundle2, bit for bit.  Coverage is counted at the OUTPUT pixel.
+// The window of one launch as the body reads it: from the kernel arguments (remap_win_kernel, remap_win4_kernel) or from the stream's
+// four doubles in device memory (remap_win_dev_kernel, remap_win4_dev_kernel).
+struct WinSteps { double x0, y0, xstep, ystep; };      // xstep = ww / OW, ystep = wh / OH
+struct WinRemapArgs { SrcRemapArgs a; int OH, OW; WinSteps ws; };
 
-// The window of one launch as the bodies below read it: from the kernel arguments (remap_win_kernel, remap_win4_kernel) or from the
-// stream's four doubles in device memory (remap_win_dev_kernel, remap_win4_dev_kernel).
-struct WinSteps { double x0, y0, xstep, ystep; };
-
-// grid (cdiv(OW, blockDim.x), OH, N): one output pixel per thread, any C, size, stride and alignment; byte loads and stores.
-__device__ __forceinline__ void remap_win_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
-                                               const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                               int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
+// grid (cdiv(OW / PX, blockDim.x), OH, N), one workgroup per row segment: the vertical taps and the two small-map rows are wave-uniform.
+// PX consecutive output pixels per thread: 1, or 4 under remap_pixel4's preconditions on OW and out.
+template <int PX, bool WINDOW>
+__device__ __forceinline__ void remap_row_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
+        const float* __restrict__ small_maps, unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out,
+        float* __restrict__ py_out) {
+    const int x = (blockIdx.x * blockDim.x + threadIdx.x) * PX, y = blockIdx.y, n = blockIdx.z;
     if (x >= OW) return;
-    const int SH = a.SH, SW = a.SW, C = a.C;
-    const Taps1D tx = cv_taps_at(ws.x0 + ((double)x + 0.5) * ws.xstep, a.w, a.xscale);
-    const Taps1D ty = cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale);
-    const size_t hw = (size_t)a.h * a.w;
-    const SrcCoord c = remap_src_coord(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
+    auto taps_x = [&](int e) { return WINDOW ? cv_taps_at(ws.x0 + ((double)(x + e) + 0.5) * ws.xstep, a.w, a.xscale) : cv_taps(x + e, a.w, a.xscale); };
+    const Taps1D ty = WINDOW ? cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale) : cv_taps(y, a.h, a.yscale);
     const size_t pix = ((size_t)n * OH + y) * OW + x;
-    if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
-    const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
-    const int fx = c.qx & 31, fy = c.qy & 31;
-    int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-    if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
-    const unsigned char* im = src + (size_t)n * a.frame_stride;
-    const bool x0 = ix >= 0 && ix < SW, x1 = ix + 1 >= 0 && ix + 1 < SW, y0 = iy >= 0 && iy < SH, y1 = iy + 1 >= 0 && iy + 1 < SH;
-    for (int ch = 0; ch < C; ++ch) {
-        const int v00 = (x0 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)ix * C + ch] : 0;
-        const int v01 = (x1 && y0) ? (int)im[(size_t)iy * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
-        const int v10 = (x0 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)ix * C + ch] : 0;
-        const int v11 = (x1 && y1) ? (int)im[(size_t)(iy + 1) * a.row_stride + (size_t)(ix + 1) * C + ch] : 0;
-        const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-        out[pix * C + ch] = (unsigned char)min(max(acc, 0), 255);
-    }
-    if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix] += 1;
+    if constexpr (PX == 4) remap_pixel4<true>(src, a, small_maps, n, taps_x, ty, pix, out, black_count, px_out, py_out);
+    else remap_pixel<true>(src, a, small_maps, n, taps_x(0), ty, pix, out, black_count, px_out, py_out);
 }
 
-// grid (cdiv(OW / 4, blockDim.x), OH, N): four consecutive OUTPUT pixels per thread, C == 3, OW % 4 == 0, out 4-byte aligned (px_out /
-// py_out 16-byte).  The source may have any width, stride and alignment: its taps come through remap_src_load6.
-__device__ __forceinline__ void remap_win4_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
-                                                const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
-    if (x0 >= OW) return;
-    const int SH = a.SH, SW = a.SW;
-    const Taps1D ty = cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale);
-    const size_t hw = (size_t)a.h * a.w;
-    const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
-    const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
-    const unsigned char* im = src + (size_t)n * a.frame_stride;
-    const unsigned char* end = im + (size_t)(SH - 1) * a.row_stride + (size_t)SW * 3;
-    const size_t pix = ((size_t)n * OH + y) * OW + x0;
-    unsigned ob[3] = {0u, 0u, 0u};                           // the 12 output bytes
-    float pxs[4], pys[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const Taps1D tx = cv_taps_at(ws.x0 + ((double)(x0 + e) + 0.5) * ws.xstep, a.w, a.xscale);
-        const SrcCoord c = remap_src_coord(mx, my, a, tx, ty);
-        pxs[e] = c.px; pys[e] = c.py;
-        const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
-        const int fx = c.qx & 31, fy = c.qy & 31;
-        int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
-        if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
-        const bool vx0 = ix >= 0 && ix < SW, vx1 = ix + 1 >= 0 && ix + 1 < SW, vy0 = iy >= 0 && iy < SH, vy1 = iy + 1 >= 0 && iy + 1 < SH;
-        // rows iy and iy + 1: 6 bytes from pixel max(ix, 0) on (ix == -1: the first three bytes are tap 1)
-        unsigned long long r0 = 0ull, r1 = 0ull;
-        const int cx = max(ix, 0);
-        if ((vx0 || vx1) && vy0) r0 = remap_src_load6(im + (size_t)iy * a.row_stride + (size_t)cx * 3, im, end);
-        if ((vx0 || vx1) && vy1) r1 = remap_src_load6(im + (size_t)(iy + 1) * a.row_stride + (size_t)cx * 3, im, end);
-        if (ix < 0) { r0 <<= 24; r1 <<= 24; }                  // tap 0 out of frame on the left: what was loaded is tap 1
-        const unsigned long long m0 = vx0 ? 0xffffffull : 0ull, m1 = vx1 ? 0xffffff000000ull : 0ull;
-        r0 &= (vy0 ? (m0 | m1) : 0ull);
-        r1 &= (vy1 ? (m0 | m1) : 0ull);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const int v00 = (int)((r0 >> (8 * ch)) & 0xff), v01 = (int)((r0 >> (24 + 8 * ch)) & 0xff);
-            const int v10 = (int)((r1 >> (8 * ch)) & 0xff), v11 = (int)((r1 >> (24 + 8 * ch)) & 0xff);
-            const int acc = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-            const unsigned o = (unsigned)min(max(acc, 0), 255);
-            const int byte = e * 3 + ch;
-            ob[byte >> 2] |= o << (8 * (byte & 3));
-        }
-        if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix + e] += 1;
-    }
-    unsigned* op = reinterpret_cast<unsigned*>(out + pix * 3);
-    op[0] = ob[0]; op[1] = ob[1]; op[2] = ob[2];
-    if (px_out != nullptr) {
-        *reinterpret_cast<float4*>(px_out + pix) = make_float4(pxs[0], pxs[1], pxs[2], pxs[3]);
-        *reinterpret_cast<float4*>(py_out + pix) = make_float4(pys[0], pys[1], pys[2], pys[3]);
-    }
+__global__ __launch_bounds__(256) void remap_src_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    remap_row_body<1, false>(src, a, a.SH, a.SW, WinSteps{}, small_maps, out, black_count, px_out, py_out);
 }
 
-__global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
-                                                        const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                        int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const WinSteps ws = {wa.x0, wa.y0, wa.xstep, wa.ystep};
-    remap_win_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+__global__ __launch_bounds__(256) void remap_src4_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    remap_row_body<4, false>(src, a, a.SH, a.SW, WinSteps{}, small_maps, out, black_count, px_out, py_out);
 }
 
-__global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
-                                                         const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
-    const WinSteps ws = {wa.x0, wa.y0, wa.xstep, wa.ystep};
-    remap_win4_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+__global__ __launch_bounds__(256) void remap_win_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    remap_row_body<1, true>(src, wa.a, wa.OH, wa.OW, wa.ws, small_maps, out, black_count, px_out, py_out);
+}
+
+__global__ __launch_bounds__(256) void remap_win4_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+    remap_row_body<4, true>(src, wa.a, wa.OH, wa.OW, wa.ws, small_maps, out, black_count, px_out, py_out);
 }
 
 // ---- the window in DEVICE memory: window[n] = {y0, x0, wh, ww}, four doubles per stream, written by an earlier launch on the stream
@@ -429,19 +276,19 @@ __device__ __forceinline__ WinSteps remap_win_load(const double* __restrict__ wi
     return ws;
 }
 
-// grids and preconditions as remap_win_kernel / remap_win4_kernel; wa.x0, wa.y0, wa.xstep, wa.ystep are not read
+// grids and preconditions as remap_win_kernel / remap_win4_kernel; wa.ws is not read
 __global__ __launch_bounds__(256) void remap_win_dev_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const double* __restrict__ window,
-                                                            const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                            int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+        const float* __restrict__ small_maps, unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out,
+        float* __restrict__ py_out) {
     const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
-    remap_win_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+    remap_row_body<1, true>(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
 }
 
-__global__ __launch_bounds__(256) void remap_win4_dev_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const double* __restrict__ window,
-                                                             const float* __restrict__ small_maps, unsigned char* __restrict__ out,
-                                                             int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
+__global__ __launch_bounds__(256) void remap_win4_dev_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa,
+        const double* __restrict__ window, const float* __restrict__ small_maps, unsigned char* __restrict__ out, int* __restrict__ black_count,
+        float* __restrict__ px_out, float* __restrict__ py_out) {
     const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
-    remap_win4_body(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+    remap_row_body<4, true>(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
 }
 
 // ---- adaptive borderless output: the largest centred window of one frame that is provably free of uncovered pixels ----
@@ -538,6 +385,89 @@ static void src_remap_args(SrcRemapArgs& a, int SH, int SW, int C, int H, int W,
     a.row_stride = row_stride_bytes; a.frame_stride = (size_t)SH * row_stride_bytes;
 }
 
+// the four-pixel kernels take BGR rows of a multiple of 4 pixels whose 12 output bytes (and 4 coordinates) land aligned
+static bool remap_vec4(int C, int width, const void* out, const float* px_out, const float* py_out) {
+    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
+    return remap_vec4_enabled() && C == 3 && width % 4 == 0 && aligned;
+}
+
+static int remap_shrink(const float* x_map, const float* y_map, int N, int H, int W, int h, int w, float* workspace, hipStream_t st, Prof* prof) {
+    const bool rec = prof && prof->begin(st);
+    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
+    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
+    SN_LAUNCH_CHECK("map_shrink_kernel");
+    return STABNET_OK;
+}
+
+// stabnet_warp_rev_bundle2_src, _win and _win_dev are one entry: the same checks in the same order, the shrink, then the kind's pair of
+// kernels over row segments of the output.  _src is the whole frame at its own size (window not read, OH, OW == SH, SW).
+enum RemapKind { REMAP_SRC, REMAP_WIN, REMAP_WIN_DEV };
+
+static int remap_src_entry(RemapKind kind, const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
+                           const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
+                           float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
+#define REMAP_NAMES(n) {n, n ": src", n ": out", n ": workspace", n ": window"}
+    static const struct { const char *who, *src, *out, *workspace, *window; } names[3] = {
+        REMAP_NAMES("warp_rev_bundle2_src"), REMAP_NAMES("warp_rev_bundle2_win"), REMAP_NAMES("warp_rev_bundle2_win_dev")};
+#undef REMAP_NAMES
+    const char* who = names[kind].who;
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "%s: null pointer", who);
+    SN_REQUIRE(kind == REMAP_SRC || window != nullptr, "%s: null window", who);
+    SN_REQUIRE(C == 1 || C == 3, "%s: C must be 1 (grey) or 3 (BGR), got %d", who, C);
+    SN_REQUIRE(N >= 1 && N <= 65535, "%s: batch %d outside 1..65535", who, N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767, "%s: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", who, SH, SW);
+    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "%s: output %dx%d outside 1..32767", who, OH, OW);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "%s: maps %dx%d leave nothing at rate %d", who, H, W, rate);
+    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "%s: row stride %zu < %d * %d bytes", who, row_stride_bytes, SW, C);
+    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "%s: px_out and py_out go together", who);
+    double y0 = 0.0, x0 = 0.0, wh = (double)SH, ww = (double)SW;         // what _src gathers, and at most what _win_dev does
+    if (kind == REMAP_WIN) {                                             // the window in host memory: read and checked during the call
+        y0 = window[0]; x0 = window[1]; wh = window[2]; ww = window[3];
+        SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
+                   "%s: window (%g, %g, %g, %g) is not finite", who, y0, x0, wh, ww);
+        SN_REQUIRE(wh > 0.0 && ww > 0.0, "%s: window %g x %g is empty", who, wh, ww);
+        // (a centred ratio window may overshoot by a rounding error; the taps clamp at the border anyway)
+        SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
+                   "%s: window (%g, %g, %g, %g) leaves the %dx%d frame", who, y0, x0, wh, ww, SH, SW);
+    }
+    hipStream_t st = (hipStream_t)stream; Prof* prof = static_cast<Prof*>(profp);
+    int rc = sn_check_device(src, names[kind].src, st);
+    if (rc == 0) rc = sn_check_device(out, names[kind].out, st);
+    if (rc == 0) rc = sn_check_device(workspace, names[kind].workspace, st);
+    if (rc == 0 && kind == REMAP_WIN_DEV) rc = sn_check_device(window, names[kind].window, st);
+    if (rc) return rc;
+    const int h = H / rate, w = W / rate;
+    rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, prof);
+    if (rc) return rc;
+    WinRemapArgs wa;
+    src_remap_args(wa.a, SH, SW, C, H, W, h, w, row_stride_bytes);
+    wa.OH = OH; wa.OW = OW; wa.ws = {x0, y0, ww / (double)OW, wh / (double)OH};      // (_win_dev: not read, its kernels load the window)
+    // algorithmic bytes: the window of the frame gathered once (_win_dev: not known here, at most the whole frame), the output written
+    // once, the two small maps
+    const double bytes = (double)N * ((wh * ww + (double)OH * OW) * C + 8.0 * h * w);
+    const bool v4 = remap_vec4(C, OW, out, px_out, py_out);
+    const int items = v4 ? OW / 4 : OW, threads = items >= 256 ? 256 : ((items + 63) & ~63);      // whole waves, a row segment each
+    const dim3 grid(cdiv(items, threads), OH, N);
+    static const struct { int id; const char* name; } kernels[3][2] = {
+        {{PK_KERNEL_REMAP_SRC, "remap_src_kernel"}, {PK_KERNEL_REMAP_SRC4, "remap_src4_kernel"}},
+        {{PK_KERNEL_REMAP_WIN, "remap_win_kernel"}, {PK_KERNEL_REMAP_WIN4, "remap_win4_kernel"}},
+        {{PK_KERNEL_REMAP_WIN_DEV, "remap_win_dev_kernel"}, {PK_KERNEL_REMAP_WIN4_DEV, "remap_win4_dev_kernel"}}};
+    const bool rec = prof && prof->begin(st);
+    if (kind == REMAP_SRC) {
+        if (v4) remap_src4_kernel<<<grid, threads, 0, st>>>(src, wa.a, workspace, out, black_count, px_out, py_out);
+        else remap_src_kernel<<<grid, threads, 0, st>>>(src, wa.a, workspace, out, black_count, px_out, py_out);
+    } else if (kind == REMAP_WIN) {
+        if (v4) remap_win4_kernel<<<grid, threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
+        else remap_win_kernel<<<grid, threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
+    } else {
+        if (v4) remap_win4_dev_kernel<<<grid, threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
+        else remap_win_dev_kernel<<<grid, threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
+    }
+    if (rec) prof->end(st, kernels[kind][v4].id, 0.0, bytes);
+    SN_LAUNCH_CHECK(kernels[kind][v4].name);
+    return STABNET_OK;
+}
+
 extern "C" {
 
 /* warpRevBundle2(img, x_map, y_map) (deploy_bundle.py:136-146): img uint8 [N,H,W,C] (BGR, C = 3), x_map, y_map [N,H,W]
@@ -550,16 +480,17 @@ int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const
     SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2: px_out and py_out go together");
     const int h = H / rate, w = W / rate;
     hipStream_t st = (hipStream_t)stream;
-    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
-    SN_LAUNCH_CHECK("map_shrink_kernel");
-    const int v4 = remap_vec4_enabled();
-    const bool aligned = (((size_t)img | (size_t)out) & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
-    if (v4 && C == 3 && W % 4 == 0 && (long)H * W * 3 >= 8 && aligned) {
-        remap_color4_kernel<<<dim3(cdiv((long)H * W / 4, 256), N), 256, 0, st>>>(img, workspace, H, W, h, w, out, px_out, py_out);
+    const int rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, nullptr);
+    if (rc) return rc;
+    SrcRemapArgs a;                                          // the source is the network-size frame itself, dense
+    src_remap_args(a, H, W, C, H, W, h, w, (size_t)W * C);
+    // (W % 4 == 0 makes the frame at least 12 bytes: the loader's first tap is always inside it)
+    if (remap_vec4(C, W, out, px_out, py_out) && ((size_t)img & 3) == 0) {
+        remap_color4_kernel<<<dim3(cdiv((long)H * W / 4, 256), N), 256, 0, st>>>(img, a, workspace, out, px_out, py_out);
         SN_LAUNCH_CHECK("remap_color4_kernel");
         return STABNET_OK;
     }
-    remap_color_kernel<<<dim3(cdiv((long)H * W, 256), N), 256, 0, st>>>(img, workspace, H, W, C, h, w, out, px_out, py_out);
+    remap_color_kernel<<<dim3(cdiv((long)H * W, 256), N), 256, 0, st>>>(img, a, workspace, out, px_out, py_out);
     SN_LAUNCH_CHECK("remap_color_kernel");
     return STABNET_OK;
 }
@@ -567,162 +498,31 @@ int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const
 /* warpRevBundle2 at SOURCE resolution: src uint8 [N,SH,SW,C] (rows row_stride_bytes apart) remapped by the network-size maps
  * x_map, y_map [N,H,W] -> out uint8 [N,SH,SW,C] dense.  black_count (optional, int32 [N,SH,SW]): += 1 on pixels whose rounded
  * coordinate lies outside the frame.  px_out/py_out (optional, [N,SH,SW]): the source-pixel coordinates cv2.remap would receive. */
-int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
-                                 const float* x_map, const float* y_map, int H, int W, int rate,
-                                 unsigned char* out, int* black_count, float* workspace,
-                                 float* px_out, float* py_out, void* stream, void* profp) {
-    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_src: null pointer");
-    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_src: C must be 1 (grey) or 3 (BGR), got %d", C);
-    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_src: batch %d outside 1..65535", N);
-    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
-               "warp_rev_bundle2_src: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
-    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_src: maps %dx%d leave nothing at rate %d", H, W, rate);
-    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_src: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
-    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_src: px_out and py_out go together");
-    const int h = H / rate, w = W / rate;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = sn_check_device(src, "warp_rev_bundle2_src: src", st);
-    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_src: out", st);
-    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_src: workspace", st);
-    if (rc) return rc;
-    Prof* prof = static_cast<Prof*>(profp);
-
-    bool rec = prof && prof->begin(st);
-    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
-    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
-    SN_LAUNCH_CHECK("map_shrink_kernel");
-
-    SrcRemapArgs a;
-    src_remap_args(a, SH, SW, C, H, W, h, w, row_stride_bytes);
-    // algorithmic bytes: the frame gathered once, written once, the two small maps
-    const double bytes = (double)N * (2.0 * SH * SW * C + 8.0 * h * w);
-    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
-    rec = prof && prof->begin(st);
-    if (remap_vec4_enabled() && C == 3 && SW % 4 == 0 && aligned) {
-        const int items = SW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
-        remap_src4_kernel<<<dim3(cdiv(items, threads), SH, N), threads, 0, st>>>(src, a, workspace, out, black_count, px_out, py_out);
-        if (rec) prof->end(st, PK_KERNEL_REMAP_SRC4, 0.0, bytes);
-        SN_LAUNCH_CHECK("remap_src4_kernel");
-        return STABNET_OK;
-    }
-    const int threads = SW >= 256 ? 256 : ((SW + 63) & ~63);
-    remap_src_kernel<<<dim3(cdiv(SW, threads), SH, N), threads, 0, st>>>(src, a, workspace, out, black_count, px_out, py_out);
-    if (rec) prof->end(st, PK_KERNEL_REMAP_SRC, 0.0, bytes);
-    SN_LAUNCH_CHECK("remap_src_kernel");
-    return STABNET_OK;
+int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, unsigned char* out, int* black_count, float* workspace, float* px_out, float* py_out,
+        void* stream, void* profp) {
+    return remap_src_entry(REMAP_SRC, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, nullptr, SH, SW, out, black_count, workspace,
+                           px_out, py_out, stream, profp);
 }
 
 /* stabnet_warp_rev_bundle2_src through a window of the stabilised frame: out uint8 [N,OH,OW,C] dense, output pixel (i, j) = the
  * stabilised frame at SH x SW sampled at the fractional position inside window = {y0, x0, wh, ww} (host memory, pixel-edge units,
  * read during the call).  black_count, px_out/py_out: [N,OH,OW], at the OUTPUT pixel. */
-int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
-                                 const float* x_map, const float* y_map, int H, int W, int rate,
-                                 const double* window, int OH, int OW,
-                                 unsigned char* out, int* black_count, float* workspace,
-                                 float* px_out, float* py_out, void* stream, void* profp) {
-    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_win: null pointer");
-    SN_REQUIRE(window != nullptr, "warp_rev_bundle2_win: null window");
-    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_win: C must be 1 (grey) or 3 (BGR), got %d", C);
-    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_win: batch %d outside 1..65535", N);
-    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
-               "warp_rev_bundle2_win: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
-    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "warp_rev_bundle2_win: output %dx%d outside 1..32767", OH, OW);
-    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_win: maps %dx%d leave nothing at rate %d", H, W, rate);
-    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_win: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
-    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_win: px_out and py_out go together");
-    const double y0 = window[0], x0 = window[1], wh = window[2], ww = window[3];
-    SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
-               "warp_rev_bundle2_win: window (%g, %g, %g, %g) is not finite", y0, x0, wh, ww);
-    SN_REQUIRE(wh > 0.0 && ww > 0.0, "warp_rev_bundle2_win: window %g x %g is empty", wh, ww);
-    // (a centred ratio window may overshoot by a rounding error; the taps clamp at the border anyway)
-    SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
-               "warp_rev_bundle2_win: window (%g, %g, %g, %g) leaves the %dx%d frame", y0, x0, wh, ww, SH, SW);
-    const int h = H / rate, w = W / rate;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = sn_check_device(src, "warp_rev_bundle2_win: src", st);
-    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_win: out", st);
-    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_win: workspace", st);
-    if (rc) return rc;
-    Prof* prof = static_cast<Prof*>(profp);
-
-    bool rec = prof && prof->begin(st);
-    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
-    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
-    SN_LAUNCH_CHECK("map_shrink_kernel");
-
-    WinRemapArgs wa;
-    SrcRemapArgs& a = wa.a;
-    src_remap_args(a, SH, SW, C, H, W, h, w, row_stride_bytes);
-    wa.OH = OH; wa.OW = OW; wa.x0 = x0; wa.y0 = y0; wa.xstep = ww / (double)OW; wa.ystep = wh / (double)OH;
-    // algorithmic bytes: the window of the frame gathered once, the output written once, the two small maps
-    const double bytes = (double)N * ((wh * ww + (double)OH * OW) * C + 8.0 * h * w);
-    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
-    rec = prof && prof->begin(st);
-    if (remap_vec4_enabled() && C == 3 && OW % 4 == 0 && aligned) {
-        const int items = OW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
-        remap_win4_kernel<<<dim3(cdiv(items, threads), OH, N), threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
-        if (rec) prof->end(st, PK_KERNEL_REMAP_WIN4, 0.0, bytes);
-        SN_LAUNCH_CHECK("remap_win4_kernel");
-        return STABNET_OK;
-    }
-    const int threads = OW >= 256 ? 256 : ((OW + 63) & ~63);
-    remap_win_kernel<<<dim3(cdiv(OW, threads), OH, N), threads, 0, st>>>(src, wa, workspace, out, black_count, px_out, py_out);
-    if (rec) prof->end(st, PK_KERNEL_REMAP_WIN, 0.0, bytes);
-    SN_LAUNCH_CHECK("remap_win_kernel");
-    return STABNET_OK;
+int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
+        float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
+    return remap_src_entry(REMAP_WIN, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
+                           px_out, py_out, stream, profp);
 }
 
 /* stabnet_warp_rev_bundle2_win with the window in DEVICE memory: window double [N,4] = {y0, x0, wh, ww} per stream, read by the
  * kernels when they run -- what an earlier launch on the stream (stabnet_fill_window_update) wrote is what they see, also when the
  * launches are replayed from a captured graph.  A window whose values _win would refuse gives the whole frame. */
-int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
-                                     const float* x_map, const float* y_map, int H, int W, int rate,
-                                     const double* window, int OH, int OW,
-                                     unsigned char* out, int* black_count, float* workspace,
-                                     float* px_out, float* py_out, void* stream, void* profp) {
-    SN_REQUIRE(src && x_map && y_map && out && workspace, "warp_rev_bundle2_win_dev: null pointer");
-    SN_REQUIRE(window != nullptr, "warp_rev_bundle2_win_dev: null window");
-    SN_REQUIRE(C == 1 || C == 3, "warp_rev_bundle2_win_dev: C must be 1 (grey) or 3 (BGR), got %d", C);
-    SN_REQUIRE(N >= 1 && N <= 65535, "warp_rev_bundle2_win_dev: batch %d outside 1..65535", N);
-    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767,
-               "warp_rev_bundle2_win_dev: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", SH, SW);
-    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "warp_rev_bundle2_win_dev: output %dx%d outside 1..32767", OH, OW);
-    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "warp_rev_bundle2_win_dev: maps %dx%d leave nothing at rate %d", H, W, rate);
-    SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "warp_rev_bundle2_win_dev: row stride %zu < %d * %d bytes", row_stride_bytes, SW, C);
-    SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "warp_rev_bundle2_win_dev: px_out and py_out go together");
-    const int h = H / rate, w = W / rate;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = sn_check_device(src, "warp_rev_bundle2_win_dev: src", st);
-    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_win_dev: out", st);
-    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_win_dev: workspace", st);
-    if (rc == 0) rc = sn_check_device(window, "warp_rev_bundle2_win_dev: window", st);
-    if (rc) return rc;
-    Prof* prof = static_cast<Prof*>(profp);
-
-    bool rec = prof && prof->begin(st);
-    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
-    if (rec) prof->end(st, PK_KERNEL_MAP_SHRINK, 0.0, (double)N * 8.0 * ((double)H * W + (double)h * w));
-    SN_LAUNCH_CHECK("map_shrink_kernel");
-
-    WinRemapArgs wa;
-    src_remap_args(wa.a, SH, SW, C, H, W, h, w, row_stride_bytes);
-    wa.OH = OH; wa.OW = OW; wa.x0 = 0.0; wa.y0 = 0.0; wa.xstep = 0.0; wa.ystep = 0.0;    // not read: the kernels load the window
-    // algorithmic bytes: at most the whole frame gathered once (the window is not known here), the output written once, the small maps
-    const double bytes = (double)N * (((double)SH * SW + (double)OH * OW) * C + 8.0 * h * w);
-    const bool aligned = ((size_t)out & 3) == 0 && (px_out == nullptr || (((size_t)px_out | (size_t)py_out) & 15) == 0);
-    rec = prof && prof->begin(st);
-    if (remap_vec4_enabled() && C == 3 && OW % 4 == 0 && aligned) {
-        const int items = OW / 4, threads = items >= 256 ? 256 : ((items + 63) & ~63);
-        remap_win4_dev_kernel<<<dim3(cdiv(items, threads), OH, N), threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
-        if (rec) prof->end(st, PK_KERNEL_REMAP_WIN4_DEV, 0.0, bytes);
-        SN_LAUNCH_CHECK("remap_win4_dev_kernel");
-        return STABNET_OK;
-    }
-    const int threads = OW >= 256 ? 256 : ((OW + 63) & ~63);
-    remap_win_dev_kernel<<<dim3(cdiv(OW, threads), OH, N), threads, 0, st>>>(src, wa, window, workspace, out, black_count, px_out, py_out);
-    if (rec) prof->end(st, PK_KERNEL_REMAP_WIN_DEV, 0.0, bytes);
-    SN_LAUNCH_CHECK("remap_win_dev_kernel");
-    return STABNET_OK;
+int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
+        float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
+    return remap_src_entry(REMAP_WIN_DEV, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
+                           px_out, py_out, stream, profp);
 }
 
 /* The adaptive window of one frame per stream (fill_window_kernel above): x_map, y_map [N,H,W] as the remap receives them; state
@@ -747,8 +547,8 @@ int stabnet_fill_window_update(const float* x_map, const float* y_map, int N, in
     if (rc == 0) rc = sn_check_device(stats, "fill_window_update: stats", st);
     if (rc == 0) rc = sn_check_device(workspace, "fill_window_update: workspace", st);
     if (rc) return rc;
-    map_shrink_kernel<<<dim3(cdiv(h * w, 256), N), 256, 0, st>>>(x_map, y_map, H, W, h, w, workspace);
-    SN_LAUNCH_CHECK("map_shrink_kernel");
+    rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, nullptr);
+    if (rc) return rc;
     FillArgs fa;
     src_remap_args(fa.a, SH, SW, 1, H, W, h, w, (size_t)SW);
     fa.margin_q = margin_q; fa.r_min = r_min; fa.up = up;

@@ -165,6 +165,18 @@ def _check_maps(x_map, y_map, N, dev, rate, what):
     return xm, ym, H, W
 
 
+def _check_out_and_count(out, black_count, N, OH, OW, C, dev, what):
+    """The optional `out` (uint8, N*OH*OW*C elements; allocated when None) and `black_count` (int32, N*OH*OW) of a remap on `dev` -> out."""
+    if out is None:
+        out = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * OH * OW * C or not out.is_contiguous():
+        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, OH, OW, C], dev))
+    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
+                                    or black_count.numel() != N * OH * OW or not black_count.is_contiguous()):
+        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, OH, OW], dev))
+    return out
+
+
 def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, black_count: torch.Tensor = None,
                        out: torch.Tensor = None, return_maps: bool = False, prof=None):
     """warpRevBundle2 at SOURCE resolution (csrc/remap.hip, stabnet_warp_rev_bundle2_src): the frame as read -- uint8 [N,SH,SW,C] /
@@ -177,13 +189,7 @@ def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     N, SH, SW, C = u8.shape
     dev = u8.device
     xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
-    if out is None:
-        out = torch.empty((N, SH, SW, C), dtype=torch.uint8, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * SH * SW * C or not out.is_contiguous():
-        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, SH, SW, C], dev))
-    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
-                                    or black_count.numel() != N * SH * SW or not black_count.is_contiguous()):
-        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, SH, SW], dev))
+    out = _check_out_and_count(out, black_count, N, SH, SW, C, dev, what)
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
     px = empty((N, SH, SW), xm) if return_maps else None
     py = empty((N, SH, SW), xm) if return_maps else None
@@ -252,13 +258,7 @@ def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
     if OH < 1 or OW < 1:
         raise _lib.StabnetError("%s: out_size %dx%d is empty" % (what, OH, OW))
-    if out is None:
-        out = torch.empty((N, OH, OW, C), dtype=torch.uint8, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * OH * OW * C or not out.is_contiguous():
-        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, OH, OW, C], dev))
-    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
-                                    or black_count.numel() != N * OH * OW or not black_count.is_contiguous()):
-        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, OH, OW], dev))
+    out = _check_out_and_count(out, black_count, N, OH, OW, C, dev, what)
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
     px = empty((N, OH, OW), xm) if return_maps else None
     py = empty((N, OH, OW), xm) if return_maps else None
