@@ -46,6 +46,22 @@ __device__ __forceinline__ AugTaps aug_taps(int H, int W, int yb, int xb, float 
     return t;
 }
 
+// one sample's draw as the kernels use it.  para is a device array the entry cannot inspect: the crop offsets are clamped to the legal
+// range [0, h - H] x [0, w - W] (tf.slice would raise outside it; here it would be a read outside the source), flip is para != 0.
+// The same value for a whole block; a legal draw passes through unchanged.
+struct AugPara {
+    int ph, pw;
+    bool flip;
+};
+
+__device__ __forceinline__ AugPara aug_para(const int* __restrict__ para, int n, const AugGeom& g) {
+    AugPara p;
+    p.ph = min(max(para[3 * n], 0), g.h - g.H);
+    p.pw = min(max(para[3 * n + 1], 0), g.w - g.W);
+    p.flip = para[3 * n + 2] != 0;
+    return p;
+}
+
 __device__ __forceinline__ float aug_lerp(float tl, float tr, float bl, float br, float lx, float ly) {
     const float top = tl + (tr - tl) * lx;
     const float bot = bl + (br - bl) * lx;
@@ -67,7 +83,9 @@ __global__ __launch_bounds__(256) void aug_resize_crop_kernel(const float* __res
     const int plane = g.H * g.W;
     const int q = blockIdx.x * AUG_PIX_PER_BLOCK + threadIdx.x;
     const bool live = q < plane;
-    const int ph = para[3 * n], pw = para[3 * n + 1], flip = para[3 * n + 2];
+    const AugPara pr = aug_para(para, n, g);
+    const int ph = pr.ph, pw = pr.pw;
+    const bool flip = pr.flip;
     AugTaps t = {0, 0, 0, 0, 0.f, 0.f};
     if (live) {
         const int y = q / g.W, x = q - y * g.W;
@@ -187,7 +205,9 @@ __global__ __launch_bounds__(256) void aug_flow_kernel(const float* __restrict__
     const int n = blockIdx.y;
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= g.H * g.W) return;
-    const int ph = para[3 * n], pw = para[3 * n + 1], flip = para[3 * n + 2];
+    const AugPara pr = aug_para(para, n, g);
+    const int ph = pr.ph, pw = pr.pw;
+    const bool flip = pr.flip;
     const int y = q / g.W, x = q - y * g.W;
     const int xs = flip ? g.W - 1 - x : x;
     const float* src = flow + (size_t)n * g.H * g.W * 2;
@@ -209,7 +229,9 @@ __global__ __launch_bounds__(256) void aug_points_kernel(const float* __restrict
     const int n = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
-    const int ph = para[3 * n], pw = para[3 * n + 1], flip = para[3 * n + 2];
+    const AugPara pr = aug_para(para, n, g);
+    const int ph = pr.ph, pw = pr.pw;
+    const bool flip = pr.flip;
     const float ox = 1.0f - ((float)pw / (float)g.w) * 2.0f;
     const float oy = 1.0f - ((float)ph / (float)g.h) * 2.0f;
     const float* p = pts + ((size_t)n * M + i) * 4;
@@ -231,11 +253,14 @@ __global__ __launch_bounds__(256) void aug_points_kernel(const float* __restrict
     mask[(size_t)n * M + i] = ok ? 1.0f : 0.0f;
 }
 
-static int aug_geom(AugGeom& g, int N, int H, int W, int bc, float rate) {
-    SN_REQUIRE(N > 0 && H > 1 && W > 1 && bc >= 1 && bc <= 14 && rate > 0.f && rate <= 1.f, "augment: bad geometry");
+// rate is the caller's float64 (Python's float): int(H / rate) has to be the number the host drew the crop offsets for, and a rate
+// rounded to float32 first gives another one (288 / 0.8 = 360, 288 / 0.8f = 359.99...)
+static int aug_geom(AugGeom& g, int N, int H, int W, int bc, double rate) {
+    SN_REQUIRE(N > 0 && H > 1 && W > 1 && bc >= 1 && bc <= 14 && rate > 0.0 && rate <= 1.0, "augment: bad geometry");
+    SN_REQUIRE((double)H / rate < 2147483647.0 && (double)W / rate < 2147483647.0, "augment: bad geometry (resized size overflows)");
     g.N = N; g.H = H; g.W = W; g.bc = bc;
-    g.h = (int)((double)H / (double)rate);      // int(height / random_crop_rate), get_data_mini_after.py:8-9
-    g.w = (int)((double)W / (double)rate);
+    g.h = (int)((double)H / rate);              // int(height / random_crop_rate), get_data_mini_after.py:8-9
+    g.w = (int)((double)W / rate);
     g.hs = (float)H / (float)g.h;
     g.ws = (float)W / (float)g.w;
     SN_REQUIRE((long)N * H * W * 16 < (1L << 31), "augment: batch too large");
@@ -253,7 +278,7 @@ size_t stabnet_augment_workspace_bytes(int N, int H, int W, int before_ch) {
 
 int stabnet_augment_pairs(const float* stable, const float* unstable, const float* flow_in, const float* matches1,
                           const int* n1, const float* matches2, const int* n2, const int* para, const float* jitter,
-                          const float* Hs, int N, int H, int W, int before_ch, int max_matches, float random_crop_rate,
+                          const float* Hs, int N, int H, int W, int before_ch, int max_matches, double random_crop_rate,
                           float* x1, float* y1, float* x2, float* y2, float* flow_out, float* fm1, float* mk1, float* fm2,
                           float* mk2, void* workspace, size_t workspace_bytes, void* stream) {
     SN_REQUIRE(stable && unstable && para && jitter && Hs && x1 && y1 && x2 && y2 && workspace, "augment_pairs: null pointer");
@@ -266,6 +291,9 @@ int stabnet_augment_pairs(const float* stable, const float* unstable, const floa
         return STABNET_ERR_WORKSPACE;
     }
     SN_REQUIRE(((uintptr_t)stable & 7) == 0 && ((uintptr_t)unstable & 7) == 0, "augment_pairs: stable / unstable must be 8-byte aligned");
+    SN_REQUIRE(flow_in == nullptr || flow_out != nullptr, "augment_pairs: flow_out missing");
+    SN_REQUIRE(matches1 == nullptr || (n1 && matches2 && n2 && fm1 && mk1 && fm2 && mk2 && max_matches > 0),
+               "augment_pairs: match arguments missing");
     hipStream_t st = (hipStream_t)stream;
     const int C = 2 * (before_ch + 1) + 2;
     const int nblk = cdiv((long)H * W, AUG_PIX_PER_BLOCK);
@@ -284,12 +312,10 @@ int stabnet_augment_pairs(const float* stable, const float* unstable, const floa
     const float div_x = (float)((double)H / (double)g.h), div_y = (float)((double)W / (double)g.w);
     const float inv_w = (float)(1.0 / (double)W);
     if (flow_in != nullptr) {
-        SN_REQUIRE(flow_out != nullptr, "augment_pairs: flow_out missing");
         aug_flow_kernel<<<dim3(cdiv((long)H * W, 256), N), 256, 0, st>>>(flow_in, para, g, div_x, div_y, inv_w, flow_out);
         SN_LAUNCH_CHECK("aug_flow_kernel");
     }
     if (matches1 != nullptr) {
-        SN_REQUIRE(n1 && matches2 && n2 && fm1 && mk1 && fm2 && mk2 && max_matches > 0, "augment_pairs: match arguments missing");
         aug_points_kernel<<<dim3(cdiv(max_matches, 256), N), 256, 0, st>>>(matches1, n1, para, g, max_matches, div_x, div_y, inv_w, fm1, mk1);
         SN_LAUNCH_CHECK("aug_points_kernel");
         aug_points_kernel<<<dim3(cdiv(max_matches, 256), N), 256, 0, st>>>(matches2, n2, para, g, max_matches, div_x, div_y, inv_w, fm2, mk2);

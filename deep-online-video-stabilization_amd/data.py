@@ -71,7 +71,8 @@ def draw(rng: np.random.Generator, cfg: Config, N: int, H: int, W: int):
 def augment_pairs(stable, unstable, flow, matches1, n1, matches2, n2, para, jitter, Hs, cfg: Config):
     """read_and_decode's output tuple (x1, y1, x2, y2, flow, feature_matches1, mask1, feature_matches2, mask2) for a batch,
     every tensor on the device.  stable [N,H,W,2*(before_ch+1)], unstable [N,H,W,2], flow [N,H,W,2], matches [N,M,4],
-    n [N] int32 valid counts; para/jitter/Hs as returned by `draw` (host arrays or device tensors)."""
+    n [N] int32 valid counts; para/jitter/Hs as returned by `draw` (host arrays or device tensors).  The crop rate goes to the
+    library as the float64 it is here, so its int(H / rate) is `resized_hw`'s."""
     stable = dev_f32(stable, "stable")
     dev = stable.device
     N, H, W, C = stable.shape

@@ -633,11 +633,17 @@ int stabnet_crop_search(const int* all_black, int H, int W, int step, int* ans5,
  * contrast factor, brightness delta; Hs [N][2][before_ch][9] mask homographies (tower, channel).
  * stable [N,H,W,2*(before_ch+1)] (label, history x before_ch, per tower), unstable [N,H,W,2], flow [N,H,W,2] (or NULL),
  * matches [N,max_matches,4] + n [N] valid counts (or NULL).  Outputs NHWC: x1,x2 [N,H,W,2*before_ch+1] (masks, masked
- * history, current), y1,y2 [N,H,W,1], flow_out, fm [N,max_matches,4], mk [N,max_matches] (0/1 floats). */
+ * history, current), y1,y2 [N,H,W,1], flow_out, fm [N,max_matches,4], mk [N,max_matches] (0/1 floats).
+ * random_crop_rate is a double, in (0, 1]: the resized size is (int)(H / rate), (int)(W / rate) in float64, the number Python's
+ * int(height / random_crop_rate) gives and the host draws its crop offsets for (a rate rounded to float32 first gives another
+ * size: 288 / 0.8 = 360, 288 / 0.8f = 359).  para lives on the device where the entry cannot inspect it, so the kernels clamp
+ * the crop row to [0, (int)(H / rate) - H] and the crop column to [0, (int)(W / rate) - W] (a legal draw is unchanged; an illegal
+ * one gives the result of the nearest legal one instead of a read outside the inputs), and flip means para[n][2] != 0.
+ * stable and unstable must be 8-byte aligned; every argument is checked before the first launch. */
 size_t stabnet_augment_workspace_bytes(int N, int H, int W, int before_ch);
 int stabnet_augment_pairs(const float* stable, const float* unstable, const float* flow_in, const float* matches1,
                           const int* n1, const float* matches2, const int* n2, const int* para, const float* jitter,
-                          const float* Hs, int N, int H, int W, int before_ch, int max_matches, float random_crop_rate,
+                          const float* Hs, int N, int H, int W, int before_ch, int max_matches, double random_crop_rate,
                           float* x1, float* y1, float* x2, float* y2, float* flow_out, float* fm1, float* mk1, float* fm2,
                           float* mk2, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -61,6 +61,7 @@ class Config:
     bn_eps: float = 1e-5                 # [external] slim resnet_arg_scope default
     bn_decay: float = 0.997              # [external]
     indices: tuple = (0, 1, 2, 4, 8, 16, 32)
+    random_crop_rate: float = 0.9        # configs/v2_93.py:23
 
     @property
     def in_ch(self):
@@ -859,16 +860,17 @@ def aug_resized_hw(H, W, rate=RANDOM_CROP_RATE):
     return int(H / rate), int(W / rate)         # get_data_mini_after.py:8-9
 
 
-def warp_img(image, para, contrast, brightness, rate=RANDOM_CROP_RATE):
+def warp_img(image, para, contrast, brightness, rate=RANDOM_CROP_RATE, mean_of=None):
     """get_data_mini_after.py:14-31 for one [H,W] channel: resize up, crop at (para h, w), flip, tf.image contrast
-    ((x - mean)*factor + mean, per-channel mean over H,W) and brightness (x + delta), clip to [-0.5, 0.5]."""
+    ((x - mean)*factor + mean, per-channel mean over H,W) and brightness (x + delta), clip to [-0.5, 0.5].
+    mean_of: [H,W] float32 -> float32 mean; None = the float64 mean (a caller that models one summation order passes its own)."""
     H, W = image.shape
     h, w = aug_resized_hw(H, W, rate)
     big = tf_resize_bilinear(image, h, w)
     img = big[para["h"]:para["h"] + H, para["w"]:para["w"] + W]
     if para["flip"]:
         img = img[:, ::-1]
-    mean = F(np.asarray(img, np.float64).mean())
+    mean = F(np.asarray(img, np.float64).mean()) if mean_of is None else F(mean_of(np.ascontiguousarray(img, F)))
     img = (((img - mean).astype(F) * F(contrast)).astype(F) + mean).astype(F)
     img = (img + F(brightness)).astype(F)
     return np.clip(img, F(-0.5), F(0.5)).astype(F)
@@ -927,18 +929,22 @@ def add_mask(pics, Hs, input_mask=True):
     return np.concatenate([masks, ans], axis=2) if input_mask else ans
 
 
-def assemble_pair(stable, unstable, flow, matches1, n1, matches2, n2, para, contrast, brightness, Hs1, Hs2, cfg: Config):
-    """get_data_mini_after.py:229-253.  stable [H,W,2*(before_ch+1)] (y1, 6 history, y2, 6 history), unstable [H,W,2]."""
+def assemble_pair(stable, unstable, flow, matches1, n1, matches2, n2, para, contrast, brightness, Hs1, Hs2, cfg: Config, mean_of=None):
+    """get_data_mini_after.py:229-253.  stable [H,W,2*(before_ch+1)] (y1, 6 history, y2, 6 history), unstable [H,W,2].
+    The crop rate is cfg.random_crop_rate; mean_of as in warp_img.  flow / matches1 None: that output is None."""
     bc = cfg.before_ch
+    rate = cfg.random_crop_rate
     H, W = stable.shape[:2]
-    st = np.stack([warp_img(stable[..., i], para, contrast, brightness) for i in range(stable.shape[2])], axis=2)
-    un = np.stack([warp_img(unstable[..., i], para, contrast, brightness) for i in range(unstable.shape[2])], axis=2)
+    st = np.stack([warp_img(stable[..., i], para, contrast, brightness, rate, mean_of) for i in range(stable.shape[2])], axis=2)
+    un = np.stack([warp_img(unstable[..., i], para, contrast, brightness, rate, mean_of) for i in range(unstable.shape[2])], axis=2)
     x1 = np.concatenate([add_mask(st[..., 1:1 + bc], Hs1, cfg.input_mask), un[..., 0:1]], axis=2)
     y1 = st[..., 0:1]
     x2 = np.concatenate([add_mask(st[..., bc + 2:2 * bc + 2], Hs2, cfg.input_mask), un[..., 1:2]], axis=2)
     y2 = st[..., bc + 1:bc + 2]
-    m1 = np.arange(cfg.max_matches) < n1
-    m2 = np.arange(cfg.max_matches) < n2
-    fm1, mk1 = warp_point(matches1, m1, para, H, W)
-    fm2, mk2 = warp_point(matches2, m2, para, H, W)
-    return x1, y1, x2, y2, warp_flow(flow, para), fm1, mk1, fm2, mk2
+    fm1 = mk1 = fm2 = mk2 = None
+    if matches1 is not None:
+        m1 = np.arange(cfg.max_matches) < n1
+        m2 = np.arange(cfg.max_matches) < n2
+        fm1, mk1 = warp_point(matches1, m1, para, H, W, rate)
+        fm2, mk2 = warp_point(matches2, m2, para, H, W, rate)
+    return x1, y1, x2, y2, (warp_flow(flow, para, rate) if flow is not None else None), fm1, mk1, fm2, mk2
