@@ -732,6 +732,13 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_REMAP_WIN_DEV: return "remap_win_dev_kernel";
         case PK_KERNEL_REMAP_WIN4_DEV: return "remap_win4_dev_kernel";
         case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
+        case PK_KERNEL_TVL1_STEP: return "tvl1_step_kernel";
+        case PK_KERNEL_TVL1_FUSED: return "tvl1_fused_kernel";
+        case PK_KERNEL_TVL1_DOWN: return "tvl1_down_kernel";
+        case PK_KERNEL_TVL1_GRAD: return "tvl1_grad_kernel";
+        case PK_KERNEL_TVL1_WARP: return "tvl1_warp_kernel";
+        case PK_KERNEL_TVL1_UP: return "tvl1_up_kernel";
+        case PK_KERNEL_TVL1_MAP: return "tvl1_map_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

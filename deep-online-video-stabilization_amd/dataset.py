@@ -68,10 +68,13 @@ class PairDataset:
     """next_batch() -> {'stable' [N,H,W,2*len(indices)], 'unstable' [N,H,W,2], 'flow' [N,H,W,2], 'matches1' / 'matches2'
     [N,max_matches,4]: float32 device tensors; 'n1' / 'n2': int32 arrays}, for ever (num_epochs=None).  Rank `rank` of `world`
     reads records rank, rank + world, ...; the sequence of samples is a function of (seed, rank, world) alone.
-    prefetch=1: the host work of the next batch runs on worker threads while the caller trains on this one; prefetch=0: inline."""
+    prefetch=1: the host work of the next batch runs on worker threads while the caller trains on this one; prefetch=0: inline.
+    flow="record": a record's flow as it stands, zeros when it is empty.  flow="tvl1": records whose flow is empty get the TV-L1
+    flow (stabnet_amd.flow, csrc/tvl1.hip) from stable frame pos - 1 to stable frame pos, as the map interpolate() reads, computed
+    on the device from the `stable` tensor the batch has just produced; records that carry a flow keep it."""
 
     def __init__(self, data_dir, split, cfg: Config, H: int, W: int, batch: int, device="cuda:0", rank: int = 0, world: int = 1,
-                 seed: int = 0, shuffle: bool = True, prefetch: int = 1, workers: int = 8):
+                 seed: int = 0, shuffle: bool = True, prefetch: int = 1, workers: int = 8, flow: str = "record"):
         self.data_dir, self.split, self.cfg = str(data_dir), str(split), cfg
         self.H, self.W, self.batch = int(H), int(W), int(batch)
         self.device_spec = device
@@ -81,6 +84,11 @@ class PairDataset:
         if prefetch not in (0, 1):
             raise StabnetError("PairDataset: prefetch must be 0 (inline) or 1 (one batch ahead), got %r" % (prefetch,))
         self.prefetch = int(prefetch)
+        if flow not in ("record", "tvl1"):
+            raise StabnetError("PairDataset: flow must be 'record' (as stored; zeros when empty) or 'tvl1' (empty flows are computed "
+                               "on the device), got %r" % (flow,))
+        self.flow_mode = flow
+        self._flow_ws = None
         self.workers = max(1, min(int(workers), 16))            # never sized from the machine's CPU count
         if any(i < 0 for i in cfg.indices):
             raise StabnetError("PairDataset: negative entries of cfg.indices (future frames) are not supported")
@@ -189,12 +197,14 @@ class PairDataset:
             ex = tfrecord.parse_example(tfrecord.read_record_at(f, rec.file, rec.number, check=False))   # the index checked the CRCs
         M = self.cfg.max_matches
         flow = np.asarray(ex.get("flow", ()), np.float32)
-        if flow.size == 0:
-            self._note("flow", "PairDataset: records with an empty flow get zeros (the published data has its flow zeroed)")
+        empty = flow.size == 0
+        if empty:
+            if self.flow_mode == "record":
+                self._note("flow", "PairDataset: records with an empty flow get zeros (the published data has its flow zeroed)")
             flow = np.zeros((self.H, self.W, 2), np.float32)
         else:
             flow = np.ascontiguousarray(flow.reshape(self.H, self.W, -1)[:, :, :2])       # get_data_mini_after.py:210
-        out = {"flow": flow}
+        out = {"flow": flow, "flow_empty": empty}
         for k in ("1", "2"):
             m = np.asarray(ex.get("feature_matches" + k, ()), np.float32).reshape(-1, 4)         # :212-213
             p = np.zeros((M, 4), np.float32)                                              # :221-222
@@ -404,7 +414,25 @@ class PairDataset:
                      "matches2": up(np.stack([x["matches2"] for x in p.samples])),
                      "n1": np.array([x["n1"] for x in p.samples], np.int32),
                      "n2": np.array([x["n2"] for x in p.samples], np.int32)}
+            empty = [n for n, x in enumerate(p.samples) if x["flow_empty"]]
+            if self.flow_mode == "tvl1" and empty:
+                batch["flow"] = self._tvl1(stable, batch["flow"], empty)
         return batch, checks
+
+    def _tvl1(self, stable, flow, empty):
+        """The TV-L1 map of every pair of the batch from stable frame pos - 1 (channel 0: what training sees as y1) to stable
+        frame pos (channel len(indices): y2), read in place on get_img's scale; the pairs listed in `empty` take it."""
+        from . import flow as tvl1
+        N = stable.shape[0]
+        need = tvl1.workspace_bytes(N, self.H, self.W)
+        if self._flow_ws is None or self._flow_ws.numel() < need:
+            self._flow_ws = self._torch.empty(need, dtype=self._torch.uint8, device=self._dev)
+        m = tvl1.tvl1_flow(stable[..., 0], stable[..., self.C // 2], out="map", workspace=self._flow_ws, offset=0.5, scale=255.0)
+        if len(empty) == N:
+            return m
+        idx = self._torch.tensor(empty, dtype=self._torch.int64, device=self._dev)
+        flow[idx] = m[idx]
+        return flow
 
     def _free_set(self, s):
         if s["event"] is not None:

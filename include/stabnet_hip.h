@@ -762,6 +762,47 @@ int stabnet_ingest_colour(const unsigned char* img, int N, int sh, int sw, int C
 int stabnet_tf_get_img(const unsigned char* frames_u8, size_t frames_bytes, const int64_t* table_dev, int n_entries, float* dst, int N,
                        int H, int W, int C, void* stream, void* prof);
 
+/* ---- beside the dataset: TV-L1 optical flow, to fill the records' flow (csrc/tvl1.hip; tests/tvl1_model.py is the yardstick) ----
+ * Zach / Pock / Bischof TV-L1 in the IPOL formulation [external: restated from the paper, nothing linked], cut down to deterministic
+ * float32 stencils: a FIXED number of inner iterations (no epsilon stop), no median filter, bilinear warps, pyramid factor 2.
+ * i0, i1: float32 [B,H,W] on the 0..255 scale, pixels pixel_stride floats apart, rows W*pixel_stride, images H*W*pixel_stride (a
+ * channel of an NHWC tensor is read in place).  stabnet_tvl1_flow reads (v + in_offset) * in_scale, two rounded operations (0, 1: v
+ * itself; 0.5, 255: a get_img channel to the 0..255 scale), the stage entry points v itself.  The flow u = (u1, u2) in pixels satisfies i1(x + u1, y + u2) ~ i0(x, y).
+ * Levels: one more while there are fewer than `scales` and min(h, w) / 2 >= min_side; one level down = [1,4,6,4,1]/16 along x,
+ * then along y, replicated borders, then the pixels at even (y, x).  Per level, coarse to fine: u = 2 * upsample(u) (half-pixel
+ * centred bilinear, source (i + 0.5)*0.5 - 0.5, clamped) or 0; the duals p11, p12, p21, p22 = 0; I1x, I1y = 0.5*(next - prev) on
+ * replicated borders.  Per warp: Ix, Iy, Iw = I1x, I1y, I1 sampled bilinearly at (x + u1, y + u2), coordinates clamped to
+ * [0, n-1], upper neighbour clamped to n-1; g = Ix*Ix + Iy*Iy; rc = ((Iw - Ix*u1) - Iy*u2) - I0.  Per iteration, with
+ * lt = lambda*theta and taut = tau/theta (float32): rho = (rc + Ix*u1) + Iy*u2; f = lt if rho < -lt*g, -lt if rho > lt*g, -rho/g if
+ * g > 1e-10f, else 0; u = (u + f*(Ix, Iy)) + theta*div(p), div = backward differences (first column / row: p itself, last: -p[x-1]);
+ * p = (p + taut*grad u) / (1 + taut*sqrt(ux*ux + uy*uy)) per component, grad = forward differences (zero in the last column / row).
+ * Every operation is one float32 operation, rounded once, in this order.  Non-finite pixel values are the caller's error: nothing
+ * is read or written out of bounds for them, but the flow they give is unspecified.
+ * Planes: u [2][B][H][W] = u1, u2; state [6][B][H][W] = u1, u2, p11, p12, p21, p22; consts [4][B][H][W] = Ix, Iy, rc, g.
+ * stabnet_tvl1_iterate runs n iterations on `state` in place (`scratch` is a second buffer of the same size: a sweep cannot run in
+ * place); fused = 0: one launch per iteration; fused = 1: up to K iterations per launch by temporal blocking in LDS and registers
+ * (stabnet_tvl1_fused_geometry gives K and the tile).  Both write the same bits.
+ * stabnet_tvl1_flow is the whole solve: uv_out [B,H,W,2] in pixels and / or map_out [B,H,W,2] in the convention interpolate() reads
+ * (xp = (x + 1)*W/2): map[..., 0] = 2*(j + u1)/W - 1, map[..., 1] = 2*(i + u2)/H - 1; either may be NULL.  It takes the fused
+ * iteration unless the environment holds STABNET_TVL1_FUSED=0.  workspace: stabnet_tvl1_workspace_bytes, 16-byte aligned.  Nothing
+ * allocates, synchronises, reads back or copies from the host; no atomics; every launch goes to `stream`: capturable in a hipGraph.
+ * Bad arguments (-1, before anything touches the GPU): null pointers, B < 1, H or W < 8 (stage entry points: < 2), a workspace too
+ * small, tau / lambda / theta not positive, scales / warps / iters < 1, min_side < 2, more than 2^31 - 1 floats per tensor. */
+int stabnet_tvl1_levels(int H, int W, int scales, int min_side, int* hw);     /* host; the number of levels, hw [levels][2] (or NULL); -1 */
+void stabnet_tvl1_fused_geometry(int* k_tx_ty);                              /* host; K, tile width, tile height of the fused kernel */
+size_t stabnet_tvl1_workspace_bytes(int B, int H, int W, int scales, int min_side);                /* host; 0 = bad arguments */
+int stabnet_tvl1_pyramid_down(const float* in, int pixel_stride, int B, int H, int W, float* out, void* stream, void* prof);
+int stabnet_tvl1_gradient(const float* in, int pixel_stride, int B, int H, int W, float* gx, float* gy, void* stream, void* prof);
+int stabnet_tvl1_warp(const float* i0, const float* i1, int pixel_stride, const float* gx, const float* gy, const float* u, float* consts,
+                      int B, int H, int W, void* stream, void* prof);
+int stabnet_tvl1_upsample(const float* u_coarse, int B, int h, int w, float* u_fine, int H, int W, void* stream, void* prof);
+int stabnet_tvl1_flow_to_map(const float* u, int B, int H, int W, float* uv_out, float* map_out, void* stream, void* prof);
+int stabnet_tvl1_iterate(float* state, float* scratch, const float* consts, int B, int H, int W, float tau, float lambda, float theta, int n,
+                         int fused, void* stream, void* prof);
+int stabnet_tvl1_flow(const float* i0, const float* i1, int pixel_stride, float in_offset, float in_scale, int B, int H, int W, float tau, float lambda, float theta,
+                      int scales, int warps, int iters, int min_side, void* workspace, size_t workspace_bytes, float* uv_out,
+                      float* map_out, void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif
