@@ -63,8 +63,10 @@ enum ConvFamily {
     CONV_RING_PRO,     // ... fragment prologue, <0, operand, 1, 1>
     CONV_PACKED,       // packed split kernel on the pre-split weight image, <mode, 4, 1, pro>
     CONV_PACKED_KG2,   // ... two K groups inside the workgroup, <mode, 4, 2, pro>
-    CONV_ASTAT         // A-stationary packed kernel (conv_astat_kernel.h), conv_astat_f32_kernel<astat_bm>: the wide 1x1 launches over
+    CONV_ASTAT,        // A-stationary packed kernel (conv_astat_kernel.h), conv_astat_f32_kernel<astat_bm>: the wide 1x1 launches over
                        // K <= 256 that CONV_PACKED would take without a K split -- the same arithmetic, bit for bit
+    CONV_PATCH         // patch-stationary packed kernel (conv_patch_kernel.h), conv_patch_f32_kernel<8, 8, WR, 3>: the 3x3 / pad 1 / stride 1
+                       // launches over large maps that CONV_PACKED would take without a K split -- the same arithmetic, bit for bit
 };
 struct ConvRoute {
     int family;        // ConvFamily
@@ -75,6 +77,8 @@ struct ConvRoute {
     int reduce;        // 1: a split-K reduce launch follows
     int prof_kind;     // PK_KERNEL_CONV_* (prof.h)
     int astat_bm;      // CONV_ASTAT: rows of M per workgroup (the kernel's BM: 32 is the one instantiation built)
+    int patch_cfg;     // CONV_PATCH: the kernel's form, 1 = <8, 8, 1, 3> (8 x 8 pixels, a wave per 32 x 32 tile), 2 = <8, 8, 2, 3> (a wave
+                       // multiplies both 32-row blocks of the patch with one B fragment)
 };
 // operand_mode: conv_launch's bf16_operands; has_image: the launch comes with a pre-split weight image (mode 4 without one is mode 0).
 // bound = true, the launcher's view: the pointers of `a` are the launch's.  bound = false, the plan-time view: the prologue is

@@ -25,6 +25,7 @@
 #include "conv_kernel.h"
 #include "conv_ring_kernel.h"
 #include "conv_astat_kernel.h"
+#include "conv_patch_kernel.h"
 #include "conv_b2b_kernel.h"
 
 // Sums the split-K partial slabs in a fixed order and applies the epilogue.  One thread per 4 channels.
@@ -112,6 +113,10 @@ struct ConvSwitches {
     // Cout (tests lower both to reach the kernel with small shapes)
     int astat = env_int("STABNET_CONV_ASTAT", 1), astat_min_m = env_int("STABNET_CONV_ASTAT_MIN_M", 0);
     int astat_min_cout = env_int("STABNET_CONV_ASTAT_MIN_COUT", 256);
+    // patch-stationary packed kernel (3x3 / pad 1 / stride 1): on / off; the smallest M it takes (0: the rule in conv_route(), tests
+    // lower it to reach the kernel with small shapes); its form (0: the rule in patch_cfg(), 1 / 2: ConvRoute::patch_cfg where it fits)
+    int patch = env_int("STABNET_CONV_PATCH", 1), patch_min_m = env_int("STABNET_CONV_PATCH_MIN_M", 0);
+    int patch_cfg = env_int("STABNET_CONV_PATCH_CFG", 0);
     int b2b = env_int("STABNET_CONV_B2B", 1), b2b_wgs_per_cu = env_int("STABNET_CONV_B2B_WGS_PER_CU", 2);   // 80 KB of LDS each
 };
 static const ConvSwitches& sw() {
@@ -255,6 +260,23 @@ static int conv_kgroups(const ConvArgs& a, int operand, bool ring, bool has_prol
     return 1;
 }
 
+// The patch-stationary kernel's forms (ConvRoute::patch_cfg - 1): patch PH x PW, row blocks per wave WR, register sets of B planes NS.
+struct PatchForm { int ph, pw, wr, ns; };
+// Two ship, both 8 x 8 pixels: with two column blocks (Cout <= 64) only WR = 1 keeps four waves busy, one 32 x 32 tile each; from four
+// column blocks on WR = 2 gives every wave one B fragment for two row blocks.  Measured and dropped:
+// 4 x 8 pixels, 16 x 16 pixels with WR = 4, five register sets.
+static const PatchForm g_patch_forms[] = {{8, 8, 1, 3}, {8, 8, 2, 3}};
+constexpr int SN_PATCH_FORMS = 2;
+constexpr size_t SN_PATCH_LDS_MAX = 160 * 1024;
+// The form for a launch, 0: its planes do not fit the LDS of a CU (256 channels and more).
+static int patch_cfg(const ConvArgs& a) {
+    auto fits = [&](int cfg) { return sn_patch_lds_bytes(g_patch_forms[cfg - 1].ph, g_patch_forms[cfg - 1].pw, a.Cin) <= SN_PATCH_LDS_MAX; };
+    const int forced = sw().patch_cfg;
+    if (forced >= 1 && forced <= SN_PATCH_FORMS) return fits(forced) ? forced : 0;
+    const int cfg = a.Cout <= 64 ? 1 : 2;
+    return fits(cfg) ? cfg : 0;
+}
+
 // The Profiler kind of a route -- the ONE place that numbers the kernels (prof.h); conv_prof_kind_name() is its inverse by construction.
 static int route_prof_kind(const ConvRoute& r) {
     switch (r.family) {
@@ -263,6 +285,7 @@ static int route_prof_kind(const ConvRoute& r) {
         case CONV_PACKED: return PK_KERNEL_CONV_PACKED + (r.pro ? 3 : r.mode);
         case CONV_PACKED_KG2: return PK_KERNEL_CONV_PACKED + (r.pro ? 6 : 4 + r.mode);
         case CONV_ASTAT: return PK_KERNEL_CONV_ASTAT;
+        case CONV_PATCH: return PK_KERNEL_CONV_PATCH + r.patch_cfg - 1;
         default: break;
     }
     // the read-time split modes (2 / 3) have kinds of their own (PK_KERNEL_CONV_SPLIT): their ring, K-group and PRO launches
@@ -309,6 +332,17 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
     const bool astat = packed && !packed_pro && !packed_kg2 && kg == 1 && a.splitk == 1 && s.astat && !lowk_ring && !a.rowrun &&
                        a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.up == 1 && a.K <= 256 && a.Cout >= s.astat_min_cout &&
                        a.M >= astat_min_m;
+    // Patch-stationary packed kernel: packed 3x3 / pad 1 / stride 1 launches without a prologue and without slabs (no K split, or
+    // the two equal K halves the ring kernel runs inside the workgroup: the kernel keeps that arithmetic; the stride-2 layers keep
+    // the ring kernel) whose halo patch fits LDS; the training step's
+    // dgrad (lowk_ring) keeps its kernels.  Smallest M: REASONED, not measured -- 12288 rows are 192 patches of 8 x 8
+    // pixels, three workgroups per four CUs; below that the ring kernel's 64 x 64 tiles, cut in N as well, fill the chip better.  The
+    // recorded small-shape routes (M <= 1224) and the 288 x 512 frame (M = 9216), whose launches tests count by kernel name, stay
+    // what they are; the 360 x 640 frame's block 1 (M = 14400) moves
+    const int patch_form = patch_cfg(a);
+    const bool patch = packed && !packed_pro && ((kg == 1 && a.splitk == 1) || packed_kg2) && s.patch && !lowk_ring && !a.rowrun &&
+                       a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.up == 1 && a.Cin % 32 == 0 && patch_form != 0 &&
+                       a.M >= (s.patch_min_m > 0 ? s.patch_min_m : 12288);
 
     ConvRoute r{};
     r.tile = t;
@@ -321,6 +355,10 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
         r.family = CONV_ASTAT;
         r.operand = 4;
         r.astat_bm = 32;                                     // (64 rows measured level at K = 128 and do not fit at K = 256: not built)
+    } else if (patch) {
+        r.family = CONV_PATCH;
+        r.operand = 4;
+        r.patch_cfg = patch_form;
     } else if (packed) {
         r.family = packed_kg2 ? CONV_PACKED_KG2 : CONV_PACKED;
         r.operand = 4;
@@ -371,6 +409,13 @@ const char* conv_prof_kind_name(int kind) {
             ConvRoute r{};
             r.family = CONV_ASTAT; r.astat_bm = 32;
             snprintf(buf, sizeof(buf), "conv_astat_f32_kernel<%d>", r.astat_bm);
+            v[route_prof_kind(r)] = buf;
+        }
+        for (int cfg = 1; cfg <= SN_PATCH_FORMS; ++cfg) {
+            ConvRoute r{};
+            r.family = CONV_PATCH; r.patch_cfg = cfg;
+            const PatchForm& f = g_patch_forms[cfg - 1];
+            snprintf(buf, sizeof(buf), "conv_patch_f32_kernel<%d, %d, %d, %d>", f.ph, f.pw, f.wr, f.ns);
             v[route_prof_kind(r)] = buf;
         }
         for (int i = 0; i < 144; ++i) {                      // <BM, BN, BK, WM, WN, MODE, NBUF, BF16>
@@ -527,6 +572,44 @@ static int launch_astat(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
     return STABNET_OK;
 }
 
+// The patch-stationary packed kernel: grid = (patches, N groups).  A group is a multiple of the CS column blocks the workgroup's waves
+// work on side by side; N is cut into groups only as far as it takes to fill the resident slots: every further group loads and splits
+// the patch once more.
+template <int PH, int PW, int WR, int NS>
+static int launch_patch_one(const ConvArgs& a, int cus, hipStream_t st) {
+    const size_t lds = sn_patch_lds_bytes(PH, PW, a.Cin);
+    auto kern = conv_patch_f32_kernel<PH, PW, WR, NS>;
+    static size_t configured = 64 * 1024;                    // the largest dynamic LDS size this instantiation is set up for
+    if (lds > configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SN_PATCH_LDS_MAX);
+        if (e != hipSuccess) {
+            stabnet_set_error("conv: hipFuncSetAttribute(%zu B LDS) failed: %s", SN_PATCH_LDS_MAX, hipGetErrorString(e));
+            return STABNET_ERR_LAUNCH;
+        }
+        configured = SN_PATCH_LDS_MAX;
+    }
+    constexpr int cs = 4 / ((PH / 4) * (PW / 8) / WR);
+    const int mtiles = a.N * cdiv(a.Ho, PH) * cdiv(a.Wo, PW), nblk = 2 * cdiv(a.Cout, 64);
+    const long slots = (long)std::min<size_t>(WR >= 4 ? 1 : 2, SN_PATCH_LDS_MAX / lds) * usable_cus(cus);
+    int groups = (int)std::min<long>(cdiv(nblk, cs), std::max<long>(1, slots / mtiles));
+    groups = cdiv(nblk, cs * cdiv(cdiv(nblk, groups), cs));          // as the kernel derives the group size from it: no empty group
+    const dim3 grid(mtiles, groups);
+    kern<<<grid, 256, lds, st>>>(a);
+    SN_LAUNCH_CHECK("conv_patch_f32_kernel");
+    return STABNET_OK;
+}
+static int launch_patch(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
+    int cus = 0;
+    if (const int rc = device_cus(cus)) return rc;
+    SN_REQUIRE(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.up == 1 && a.Cin % 32 == 0 &&
+                   (a.splitk == 1 || (a.splitk == 2 && a.steps_per_split * 2 == conv_total_steps(a))) && a.Ho == a.H && a.Wo == a.W && r.patch_cfg >= 1 &&
+                   r.patch_cfg <= SN_PATCH_FORMS &&
+                   sn_patch_lds_bytes(g_patch_forms[r.patch_cfg - 1].ph, g_patch_forms[r.patch_cfg - 1].pw, a.Cin) <= SN_PATCH_LDS_MAX,
+               "conv: the patch-stationary kernel takes 3x3 / pad 1 / stride 1 over Cin %d (a multiple of 32) without a K split or with two equal K halves only if the planes fit %zu bytes",
+               a.Cin, SN_PATCH_LDS_MAX);
+    return r.patch_cfg == 1 ? launch_patch_one<8, 8, 1, 3>(a, cus, st) : launch_patch_one<8, 8, 2, 3>(a, cus, st);
+}
+
 // ---- pre-split weight image (conv.h) -----------------------------------------------------------------------------------
 size_t conv_weight_image_floats(int Cout, int K) { return (size_t)cdiv(Cout, 64) * (size_t)(K / 32) * 3072; }
 
@@ -635,6 +718,12 @@ int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands
             ConvArgs b = a;
             b.w = w_img;
             rc = launch_astat(r, b, st);
+            break;
+        }
+        case CONV_PATCH: {
+            ConvArgs b = a;
+            b.w = w_img;
+            rc = launch_patch(r, b, st);
             break;
         }
         default: rc = launch_ring_route(r, a, st); break;
@@ -867,6 +956,11 @@ int stabnet_conv2d_fwd_ex(const float* x, const float* w_ohwi, const float* bias
 }
 
 /* stabnet_conv2d_fwd_ex through the packed split kernels (include/stabnet_hip.h) */
+int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
+                                 const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,
+                                 const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
+                                 int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 size_t stabnet_conv_weight_image_floats(int Cout, int KH, int KW, int Cin) {
     const int K = KH * KW * Cin;
     return (Cout > 0 && K > 0 && K % 32 == 0) ? conv_weight_image_floats(Cout, K) : 0;
@@ -906,12 +1000,24 @@ int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* 
                               const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
                               int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
                               size_t workspace_bytes, void* stream) {
+    return stabnet_conv2d_fwd_packed_ld(x, 0, w_ohwi, w_img, bias, in_scale, in_shift, residual, res_H, res_W, res_stride, out_scale, out_shift,
+                                        y, N, H, W, Cin, Cout, KH, KW, stride, pad, relu_out, splitk, workspace, workspace_bytes, stream);
+}
+
+/* stabnet_conv2d_fwd_packed on an input whose pixels lie x_ld floats apart (0 = Cin): Cin columns of a wider buffer */
+int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
+                                 const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,
+                                 const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
+                                 int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
     SN_REQUIRE(x && w_ohwi && w_img && y, "conv2d_fwd_packed: null pointer");
     SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv2d_fwd_packed: out_scale and out_shift go together");
+    SN_REQUIRE(x_ld == 0 || (x_ld >= Cin && x_ld % 4 == 0), "conv2d_fwd_packed: x_ld=%d must be 0 or a multiple of 4 >= Cin=%d", x_ld, Cin);
     ConvArgs a;
     int rc = fill_args(a, x, w_ohwi, bias, in_scale, in_shift, residual, res_H, res_W, res_stride, y, N, H, W, Cin, Cout,
                        KH, KW, stride, pad, relu_out);
     if (rc) return rc;
+    a.x_ld = x_ld;
     const size_t need = plan_packed(a, splitk);
     if (need > workspace_bytes || (need > 0 && workspace == nullptr)) {
         stabnet_set_error("conv2d_fwd_packed: workspace %zu B < %zu B needed", workspace_bytes, need);

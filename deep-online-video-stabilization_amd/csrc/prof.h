@@ -18,6 +18,7 @@ enum {
     PK_KERNEL_CONV_PAIR = 80 /* + 2*MODE + (BK==32): conv_igemm_f32_pair_kernel<64, 64, BK, 32, 32, MODE> */, PK_KERNEL_CONV_KG = 84 /* + mode: conv_ring_f32_kernel<MODE, 0, 3, 0>; + 2: conv_ring_f32_kernel<0, 0, 1, 1> (fragment prologue); + 3: <0, 0, 2, 1> */, PK_KERNEL_CONV_RING = 90 /* + mode; + 3 for the bf16-operand variants */,
     PK_KERNEL_CONV_PACKED = 70 /* + mode: conv_ring_f32_kernel<MODE, 4, 1, 0> (pre-split weight image); + 3: <0, 4, 1, 1>; + 4 + mode: <MODE, 4, 2, 0>; + 6: <0, 4, 2, 1> */,
     PK_KERNEL_CONV_ASTAT = 77 /* conv_astat_f32_kernel<32> */,
+    PK_KERNEL_CONV_PATCH = 24 /* + 0: conv_patch_f32_kernel<8, 8, 1, 3>; + 1: <8, 8, 2, 3> (ConvRoute::patch_cfg - 1) */,
     PK_KERNEL_CONV_B2B = 96 /* conv_b2b_f32_kernel<2>; + 1: <4> */,
     PK_KERNEL_CONV_SPLIT = 40 /* + 8 * (BF16 - 2) + slot, the read-time split modes 2 / 3: conv_ring_f32_kernel<MODE, BF16, KG, PRO>, slot 0..2 = <MODE, B, 1, 0>,
                                  3 / 4 = <0 / 1, B, 3, 0>, 5 = <0, B, 1, 1>, 6 = <0, B, 2, 1> */,

@@ -107,6 +107,14 @@ int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* 
                               const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
                               int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* stabnet_conv2d_fwd_packed on an input whose pixels lie x_ld floats apart (0 = Cin; else a multiple of 4 >= Cin): Cin columns of a
+ * wider buffer, as the inference plan's conv2 layers read conv1's columns of the merged shortcut | conv1 buffer.  Geometries the ring
+ * and packed kernels do not take (the register-staged path) need x_ld == Cin. */
+int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
+                                 const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,
+                                 const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
+                                 int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 /* The Profiler kind (see stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry, with
  * (prologue != 0) or without in_scale / in_shift: which kernel the call runs.  Host only, no GPU needed; < 0 on a bad geometry. */
 int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int prologue, int splitk);
