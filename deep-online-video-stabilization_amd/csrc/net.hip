@@ -739,6 +739,9 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_TVL1_WARP: return "tvl1_warp_kernel";
         case PK_KERNEL_TVL1_UP: return "tvl1_up_kernel";
         case PK_KERNEL_TVL1_MAP: return "tvl1_map_kernel";
+        case PK_KERNEL_KLT_DETECT: return "klt_detect_kernel";
+        case PK_KERNEL_KLT_TRACK: return "klt_track_kernel";
+        case PK_KERNEL_KLT_FINISH: return "klt_finish_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

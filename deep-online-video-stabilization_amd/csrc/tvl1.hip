@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "tvl1_shared.h"
 
 namespace {
 
@@ -74,27 +75,6 @@ __device__ __forceinline__ void tv_p_update(float& pa, float& pb, float u, float
     const float n = __fadd_rn(1.0f, __fmul_rn(taut, sqrtf(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)))));
     pa = __fdiv_rn(__fadd_rn(pa, __fmul_rn(taut, a)), n);
     pb = __fdiv_rn(__fadd_rn(pb, __fmul_rn(taut, b)), n);
-}
-
-// what the solve reads from i0 / i1: (v + off) * scl, two rounded operations (a get_img channel to the 0..255 scale); on = 0: v itself
-struct TvAff { float off, scl; int on; };
-__device__ __forceinline__ float tv_px(float v, TvAff a) { return a.on ? __fmul_rn(__fadd_rn(v, a.off), a.scl) : v; }
-
-// I (rows W * ps floats, pixels ps floats apart) at (y, x): coordinates clamped to [0, n-1], the upper neighbour to n-1
-__device__ __forceinline__ float tv_bilinear(const float* __restrict__ I, int ps, int H, int W, float y, float x, TvAff af) {
-    x = fminf(fmaxf(x, 0.0f), (float)(W - 1));
-    y = fminf(fmaxf(y, 0.0f), (float)(H - 1));
-    const float xf = floorf(x), yf = floorf(y);
-    int x0 = (int)xf, y0 = (int)yf;
-    x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0);                                    // (a NaN coordinate is the caller's error: it still reads inside)
-    y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0);
-    const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
-    const float fx = __fsub_rn(x, xf), fy = __fsub_rn(y, yf);
-    const float* r0 = I + (size_t)y0 * W * ps;
-    const float* r1 = I + (size_t)y1 * W * ps;
-    const float a = tv_px(r0[(size_t)x0 * ps], af), b = tv_px(r0[(size_t)x1 * ps], af), c = tv_px(r1[(size_t)x0 * ps], af), d = tv_px(r1[(size_t)x1 * ps], af);
-    const float top = __fadd_rn(a, __fmul_rn(fx, __fsub_rn(b, a))), bot = __fadd_rn(c, __fmul_rn(fx, __fsub_rn(d, c)));
-    return __fadd_rn(top, __fmul_rn(fy, __fsub_rn(bot, top)));
 }
 
 // ---- stage kernels: grid (cdiv(h * w, kThreads), B), one thread per output pixel, indexed by absolute position ------------------------
@@ -405,6 +385,18 @@ bool tv_fused_default() {
 }
 
 }  // namespace
+
+// ---- what csrc/klt.hip shares (tvl1_shared.h) ------------------------------------------------------------------------------------------
+
+int sn_tv_levels(int H, int W, int scales, int min_side, int* hs, int* ws) { return tv_levels(H, W, scales, min_side, hs, ws); }
+
+int sn_tv_down(const float* in, int ps, float off, float scl, int on, int B, int H, int W, float* out, hipStream_t st, Prof* prof) {
+    return tv_down(in, ps, TvAff{off, scl, on}, B, H, W, out, st, prof);
+}
+
+int sn_tv_grad(const float* in, int ps, float off, float scl, int on, int B, int H, int W, float* gx, float* gy, hipStream_t st, Prof* prof) {
+    return tv_grad(in, ps, TvAff{off, scl, on}, B, H, W, gx, gy, st, prof);
+}
 
 #define TV_TRY(call) do { const int rc__ = (call); if (rc__) return rc__; } while (0)
 

@@ -71,10 +71,16 @@ class PairDataset:
     prefetch=1: the host work of the next batch runs on worker threads while the caller trains on this one; prefetch=0: inline.
     flow="record": a record's flow as it stands, zeros when it is empty.  flow="tvl1": records whose flow is empty get the TV-L1
     flow (stabnet_amd.flow, csrc/tvl1.hip) from stable frame pos - 1 to stable frame pos, as the map interpolate() reads, computed
-    on the device from the `stable` tensor the batch has just produced; records that carry a flow keep it."""
+    on the device from the `stable` tensor the batch has just produced; records that carry a flow keep it.
+    matches="record": a record's feature matches as they stand (none when a list is empty).  matches="klt": a list that is empty
+    in the record is computed on the device behind the get_img launches (stabnet_amd.features, csrc/klt.hip): feature_matches1
+    from stable frame pos - 1 to unstable frame pos - 1 (tower 1), feature_matches2 from stable frame pos to unstable frame pos
+    (tower 2); a list that carries rows keeps them.  In this mode 'n1' / 'n2' are int32 DEVICE tensors (nothing is read back;
+    data.augment_pairs takes either)."""
 
     def __init__(self, data_dir, split, cfg: Config, H: int, W: int, batch: int, device="cuda:0", rank: int = 0, world: int = 1,
-                 seed: int = 0, shuffle: bool = True, prefetch: int = 1, workers: int = 8, flow: str = "record"):
+                 seed: int = 0, shuffle: bool = True, prefetch: int = 1, workers: int = 8, flow: str = "record",
+                 matches: str = "record"):
         self.data_dir, self.split, self.cfg = str(data_dir), str(split), cfg
         self.H, self.W, self.batch = int(H), int(W), int(batch)
         self.device_spec = device
@@ -89,6 +95,11 @@ class PairDataset:
                                "on the device), got %r" % (flow,))
         self.flow_mode = flow
         self._flow_ws = None
+        if matches not in ("record", "klt"):
+            raise StabnetError("PairDataset: matches must be 'record' (as stored; none when empty) or 'klt' (empty lists are computed "
+                               "on the device), got %r" % (matches,))
+        self.matches_mode = matches
+        self._klt_ws = None
         self.workers = max(1, min(int(workers), 16))            # never sized from the machine's CPU count
         if any(i < 0 for i in cfg.indices):
             raise StabnetError("PairDataset: negative entries of cfg.indices (future frames) are not supported")
@@ -417,6 +428,9 @@ class PairDataset:
             empty = [n for n, x in enumerate(p.samples) if x["flow_empty"]]
             if self.flow_mode == "tvl1" and empty:
                 batch["flow"] = self._tvl1(stable, batch["flow"], empty)
+            if self.matches_mode == "klt":
+                for k, cs, cu in (("1", 0, 0), ("2", self.C // 2, 1)):
+                    batch["matches" + k], batch["n" + k] = self._klt(stable[..., cs], unstable[..., cu], batch["matches" + k], batch["n" + k])
         return batch, checks
 
     def _tvl1(self, stable, flow, empty):
@@ -433,6 +447,25 @@ class PairDataset:
         idx = self._torch.tensor(empty, dtype=self._torch.int64, device=self._dev)
         flow[idx] = m[idx]
         return flow
+
+    def _klt(self, stable, unstable, rows, n):
+        """The matches of every pair of the batch from one stable channel to the unstable channel of the same instant, read in
+        place on get_img's scale; the records whose list is empty (n == 0 on the host) take them.  -> rows, n (int32, on the device)."""
+        from . import features
+        torch = self._torch
+        N = stable.shape[0]
+        need = features.workspace_bytes(N, self.H, self.W)
+        if self._klt_ws is None or self._klt_ws.numel() < need:
+            self._klt_ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
+        m, cnt = features.klt_matches(stable, unstable, self.cfg.max_matches, workspace=self._klt_ws, offset=0.5, scale=255.0)
+        empty = np.flatnonzero(n == 0)
+        if len(empty) == N:
+            return m, cnt
+        idx = torch.from_numpy(empty.astype(np.int64)).to(self._dev)
+        n = torch.from_numpy(n).to(self._dev)
+        rows[idx] = m[idx]
+        n[idx] = cnt[idx]
+        return rows, n
 
     def _free_set(self, s):
         if s["event"] is not None:

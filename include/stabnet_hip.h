@@ -811,6 +811,54 @@ int stabnet_tvl1_flow(const float* i0, const float* i1, int pixel_stride, float 
                       int scales, int warps, int iters, int min_side, void* workspace, size_t workspace_bytes, float* uv_out,
                       float* map_out, void* stream, void* prof);
 
+/* ---- beside the dataset: corner tracking, to fill the records' feature_matches1 / 2 (csrc/klt.hip; tests/klt_model.py is the yardstick) ----
+ * Shi-Tomasi corners, one per grid cell, tracked by pyramidal Lucas-Kanade with a FIXED number of iterations (no early stop) and kept
+ * when the track back returns to the start [external: restated from the papers of Shi / Tomasi and Bouguet, nothing linked].
+ * i0 (the stable frame), i1 (the unstable frame of the same instant): float32 [B,H,W], pixels pixel_stride0 / pixel_stride1 floats
+ * apart (rows W*stride, images H*W*stride: a channel of an NHWC tensor is read in place), read as (v + in_offset) * in_scale, two
+ * rounded operations, which must give the 0..255 scale (0, 1: v itself).  Every operation is one float32 operation, rounded once, in
+ * this order; sqrt and / are the correctly rounded ones.
+ * 1 Pyramids of both images: TV-L1's (above), one more level while there are fewer than `levels` and min(h, w) / 2 >= min_side.
+ * 2 Response on level 0 of i0: gx, gy = 0.5*(next - prev); a, b, c = the sums of gx*gx, gx*gy, gy*gy over the (2r+1)^2 box, first
+ *   along x from left to right, then along y from top to bottom; resp = 0.5*((a + c) - sqrt((a - c)*(a - c) + 4*(b*b))); resp = 0
+ *   for pixels closer than `border` to an image edge (border >= r + 1: no box leaves the image).
+ * 3 One candidate per cell x cell pixels (row-major cells; partial cells at the right and bottom edges count): the largest
+ *   response, ties to the smallest (y, x).  detected = resp > 0 and resp >= floor and resp >= quality * (the image's largest resp).
+ * 4 Track p from image A to image B, coarse to fine, d = 0 at the coarsest level; at level l, p_l = p * 2^-l: window sample s in
+ *   [0, (2R+1)^2) has the offset o = (s mod (2R+1) - R, s div (2R+1) - R) and lies at (x, y) = p_l + o; T, Tx, Ty = A's level and its
+ *   gradient planes sampled bilinearly there (coordinates clamped to [0, n-1], the upper neighbour to n-1, a NaN coordinate reads 0).
+ *   A window sum of v[s]: lane j of a 64-lane wave starts from 0 and adds v[j], v[j+64], v[j+128], v[j+192] (those below (2R+1)^2)
+ *   in this order; then six steps with partner distances 32, 16, 8, 4, 2, 1, each v = v + the partner's v.
+ *   a, b, c = the window sums of Tx*Tx, Tx*Ty, Ty*Ty; det = a*c - b*b; lost when 0.5*((a+c) - sqrt((a-c)*(a-c) + 4*(b*b))) / (2R+1)^2
+ *   < min_eig or det == 0.  Exactly `iters` times: e = T - B_l(y + d.y, x + d.x); bx, by = the window sums of e*Tx, e*Ty;
+ *   d.x = d.x + (c*bx - b*by)/det; d.y = d.y + (a*by - b*bx)/det.  Then q_l = p_l + d; lost unless 0 <= q_l.x <= w-1 and
+ *   0 <= q_l.y <= h-1 (a non-finite q_l is lost); d = 2*d for the next finer level.  A lost point stays lost; its arithmetic goes on.
+ * 5 q = the forward track of p from i0 to i1; p' = the track of q from i1 to i0; fb2 = (p'.x - p.x)^2 + (p'.y - p.y)^2.  A match is
+ *   valid when it was detected, neither track lost it and fb2 <= fb*fb.
+ * 6 The row of a valid match: (2*p.x)/W - 1, (2*p.y)/H - 1, (2*q.x)/W - 1, (2*q.y)/H - 1; rows in cell order.  The reference wants the
+ *   count to be smaller than max_matches, so at most max_matches - 1 rows are kept, the first in cell order; every row from n on is 0.
+ * cand [B][cells][4] = x, y, resp, detected (1 / 0); trk [B][N][4] = q.x, q.y, lost (1 / 0), fb2, a lost point's row being 0, 0, 1, 0;
+ * pts [B][N][2] = x, y; matches [B][max_matches][4]; n [B] int32.  stabnet_klt_response / _detect / _track are the stages alone
+ * (_track builds the pyramids into the workspace first); stabnet_klt_matches is the whole solve: detection, one tracking launch (one
+ * wave per cell, both directions) and one finishing launch.  workspace: stabnet_klt_workspace_bytes (for _track that of any cell
+ * size), 16-byte aligned, as are cand, trk and matches.  Nothing allocates, synchronises, reads back or copies from the host; no
+ * atomics; every launch goes to `stream`: capturable in a hipGraph.
+ * Bad arguments (-1, before anything touches the GPU): null pointers, B < 1, H or W < 2*border + 1 (_track: < 3), border < r + 1, r
+ * outside 1..4, cell < 2, max_matches < 2, a workspace too small, floor / quality / fb / iters not positive, levels outside 1..8,
+ * min_side < 2, R outside 1..7 (a lane owns four window samples), min_eig negative, more than 2^31 - 1 floats per tensor. */
+int stabnet_klt_cells(int H, int W, int cell, int* rows_cols);                 /* host; the number of cells, rows_cols [2] (or NULL); -1 */
+size_t stabnet_klt_workspace_bytes(int B, int H, int W, int levels, int min_side, int cell);        /* host; 0 = bad arguments */
+int stabnet_klt_response(const float* i0, int pixel_stride, float in_offset, float in_scale, int B, int H, int W, int r, int border, float* resp,
+                         void* stream, void* prof);
+int stabnet_klt_detect(const float* i0, int pixel_stride, float in_offset, float in_scale, int B, int H, int W, int r, int border, int cell,
+                       float floor, float quality, float* cand, void* stream, void* prof);
+int stabnet_klt_track(const float* i0, const float* i1, int pixel_stride0, int pixel_stride1, float in_offset, float in_scale, int B, int H, int W,
+                      const float* pts, int N, int levels, int min_side, int R, int iters, float min_eig, void* workspace, size_t workspace_bytes,
+                      float* trk, void* stream, void* prof);
+int stabnet_klt_matches(const float* i0, const float* i1, int pixel_stride0, int pixel_stride1, float in_offset, float in_scale, int B, int H, int W,
+                        int levels, int min_side, int r, int border, int cell, float floor, float quality, int R, int iters, float min_eig, float fb,
+                        int max_matches, void* workspace, size_t workspace_bytes, float* matches, int* n, void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif

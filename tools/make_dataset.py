@@ -14,10 +14,14 @@ position t of pair k; without it both lists are empty.  No GPU is used -- unless
 after the frames and records are laid out, every record gets the TV-L1 flow (stabnet_amd/flow.py, csrc/tvl1.hip) from stable frame
 pos - 1 to stable frame pos, computed on the GPU from the WRITTEN JPEG files through get_img's arithmetic at the network's size
 (--height x --width) -- the very values a training step will see as y1 and y2 -- and stored as the map [H,W,2] that interpolate()
-reads.  The default --flow none writes the records with an empty flow, as before.
+reads.  The default --flow none writes the records with an empty flow, as before.  --features klt fills feature_matches1 / 2 in
+the same way (stabnet_amd/features.py, csrc/klt.hip): corners of stable frame pos - 1 tracked into unstable frame pos - 1, and
+those of stable frame pos into unstable frame pos, from the written files at --height x --width; it cannot be combined with
+--matches.  With both --flow tvl1 and --features klt the dataset is read back once.
 
     python tools/make_dataset.py --out data --split train --pair stable0.npy unstable0.npy --pair stable1.avi unstable1.avi
     python tools/make_dataset.py --out data --split train --pair stable0.npy unstable0.npy --flow tvl1 --flow-batch 8
+    python tools/make_dataset.py --out data --split train --pair stable0.npy unstable0.npy --features klt --height 288 --width 512
 """
 import argparse
 import os
@@ -54,21 +58,30 @@ def write_clip(path, folder, quality):
     return n
 
 
-def tvl1_flows(out, split, H, W, batch, count):
-    """The TV-L1 map [H,W,2] of records 0 .. count - 1 of the dataset just written, in order: PairDataset decodes stable frames
-    pos - 1 and pos from the written files and runs get_img, so the flow belongs to exactly what training reads."""
+def read_back(out, split, H, W, batch, count, want_flow, want_features):
+    """-> (maps, matches) of records 0 .. count - 1 of the dataset just written, in order (either None when not wanted): the TV-L1
+    map [H,W,2] and the two match lists ([n,4] each).  PairDataset decodes frames pos - 1 and pos of both clips from the written
+    files and runs get_img, so both belong to exactly what training reads."""
     import dataclasses
-    from stabnet_amd import flow
+    from stabnet_amd import features, flow
     from stabnet_amd.config import Config
     from stabnet_amd.dataset import PairDataset
     cfg = dataclasses.replace(Config(), indices=(0,))            # stable [N,H,W,2] = frames pos - 1, pos: nothing else is decoded
-    maps = []
+    maps, lists = [], []
     with PairDataset(out, split, cfg, H, W, batch, shuffle=False, prefetch=0) as ds:
-        while len(maps) < count:
-            stable = ds.next_batch()["stable"]                  # (the last batch wraps round to the first records: ignored)
-            m = flow.tvl1_flow(stable[..., 0], stable[..., 1], out="map", offset=0.5, scale=255.0)
-            maps.extend(m.cpu().numpy())
-    return maps[:count]
+        for _ in range(0, count, batch):                         # (the last batch wraps round to the first records: ignored)
+            b = ds.next_batch()
+            stable, unstable = b["stable"], b["unstable"]
+            if want_flow:
+                maps.extend(flow.tvl1_flow(stable[..., 0], stable[..., 1], out="map", offset=0.5, scale=255.0).cpu().numpy())
+            if want_features:
+                both = []
+                for c in (0, 1):
+                    m, n = features.klt_matches(stable[..., c], unstable[..., c], cfg.max_matches, offset=0.5, scale=255.0)
+                    m, n = m.cpu().numpy(), n.cpu().numpy()
+                    both.append([m[i, :n[i]] for i in range(len(n))])
+                lists.extend(zip(*both))
+    return (maps[:count] if want_flow else None), (lists[:count] if want_features else None)
 
 
 def main():
@@ -80,14 +93,18 @@ def main():
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--records-per-file", type=int, default=10)
     ap.add_argument("--flow", default="none", choices=["none", "tvl1"], help="none: every record's flow is empty; tvl1: computed on the GPU")
-    ap.add_argument("--flow-batch", type=int, default=8, help="--flow tvl1: pairs per solve")
-    ap.add_argument("--height", type=int, default=None, help="--flow tvl1: the network's input height (default: the configuration's)")
-    ap.add_argument("--width", type=int, default=None, help="--flow tvl1: the network's input width")
+    ap.add_argument("--features", default="none", choices=["none", "klt"],
+                    help="none: the feature matches are those of --matches, or empty; klt: corners tracked on the GPU")
+    ap.add_argument("--flow-batch", type=int, default=8, help="--flow tvl1 / --features klt: records per solve")
+    ap.add_argument("--height", type=int, default=None, help="--flow tvl1 / --features klt: the network's input height (default: the configuration's)")
+    ap.add_argument("--width", type=int, default=None, help="--flow tvl1 / --features klt: the network's input width")
     a = ap.parse_args()
     from stabnet_amd.config import Config
     from stabnet_amd.dataset import write_dataset
     if a.matches is not None and len(a.matches) != len(a.pair):
         raise SystemExit("make_dataset.py: %d --matches for %d --pair" % (len(a.matches), len(a.pair)))
+    if a.features == "klt" and a.matches is not None:
+        raise SystemExit("make_dataset.py: --features klt computes the feature matches; it cannot be combined with --matches")
     first = max(Config().indices) + 1
     samples = []
     for k, (stable, unstable) in enumerate(a.pair):
@@ -107,14 +124,21 @@ def main():
             samples.append(s)
         print("pair %d: %d + %d frames, positions %d..%d" % (k, counts[0], counts[1], first, T - 1))
     names = write_dataset(a.out, a.split, samples, records_per_file=a.records_per_file)
-    if a.flow == "tvl1":
+    if a.flow == "tvl1" or a.features == "klt":
         if a.flow_batch < 1:
             raise SystemExit("make_dataset.py: --flow-batch must be at least 1, got %d" % a.flow_batch)
         H, W = a.height or Config().height, a.width or Config().width
-        for s, m in zip(samples, tvl1_flows(a.out, a.split, H, W, a.flow_batch, len(samples))):
-            s["flow"] = m
+        maps, lists = read_back(a.out, a.split, H, W, a.flow_batch, len(samples), a.flow == "tvl1", a.features == "klt")
+        for i, s in enumerate(samples):
+            if maps is not None:
+                s["flow"] = maps[i]
+            if lists is not None:
+                s["feature_matches1"], s["feature_matches2"] = lists[i]
         names = write_dataset(a.out, a.split, samples, records_per_file=a.records_per_file)
-        print("flow: TV-L1 at %dx%d for %d records" % (W, H, len(samples)))
+        if maps is not None:
+            print("flow: TV-L1 at %dx%d for %d records" % (W, H, len(samples)))
+        if lists is not None:
+            print("features: KLT at %dx%d for %d records, %d matches" % (W, H, len(samples), sum(len(m) for l in lists for m in l)))
     print("%s: %d records in %d file(s)" % (os.path.join(a.out, a.split, "list.txt"), len(samples), len(names)))
 
 

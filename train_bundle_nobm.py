@@ -49,6 +49,9 @@ def build_parser():
     p.add_argument('--flow', default='record', choices=['record', 'tvl1'],
                    help='--data-dir: record = the flow a record carries, zeros when it is empty (the published data); tvl1 = empty flows '
                         'are computed on the GPU, TV-L1 from stable frame pos - 1 to pos (stabnet_amd/flow.py)')
+    p.add_argument('--features', default='record', choices=['record', 'klt'],
+                   help='--data-dir: record = the feature matches a record carries, none when a list is empty; klt = empty lists are '
+                        'computed on the GPU, corners of the stable frame tracked into the unstable one (stabnet_amd/features.py)')
     p.add_argument('--data-workers', type=int, default=8, help='--data-dir: host threads that read and entropy-decode frames (at most 16)')
     p.add_argument('--data-prefetch', type=int, default=1, choices=[0, 1],
                    help='--data-dir: 1 = the host work of the next batch runs beside the training step, 0 = everything inline')
@@ -123,7 +126,8 @@ def main():
             try:
                 datasets[split] = PairDataset(args.data_dir, split, cfg, H, W, N, device=dev, rank=rank, world=world,
                                               seed=1234 if split == 'train' else 987654, shuffle=True,
-                                              prefetch=args.data_prefetch, workers=args.data_workers, flow=args.flow)
+                                              prefetch=args.data_prefetch, workers=args.data_workers, flow=args.flow,
+                                              matches=args.features)
             except StabnetError as e:
                 raise SystemExit('train_bundle_nobm.py: --data-dir %s: %s' % (args.data_dir, e))
             if rank == 0:
