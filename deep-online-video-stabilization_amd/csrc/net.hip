@@ -742,6 +742,7 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_KLT_DETECT: return "klt_detect_kernel";
         case PK_KERNEL_KLT_TRACK: return "klt_track_kernel";
         case PK_KERNEL_KLT_FINISH: return "klt_finish_kernel";
+        case PK_KERNEL_HOMFIT: return "homfit_kernel";
         default: break;
     }
     if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>

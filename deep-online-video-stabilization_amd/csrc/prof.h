@@ -15,6 +15,7 @@ enum {
     PK_KERNEL_TVL1_STEP = 57, PK_KERNEL_TVL1_FUSED = 58 /* tvl1.hip, one record per launch; bytes = ten planes read + six written once, shape[0] = sweeps of the launch */,
     PK_KERNEL_TVL1_DOWN = 65, PK_KERNEL_TVL1_GRAD = 66, PK_KERNEL_TVL1_WARP = 67, PK_KERNEL_TVL1_UP = 68, PK_KERNEL_TVL1_MAP = 69 /* tvl1.hip stages; bytes = every plane read or written, once */,
     PK_KERNEL_KLT_DETECT = 26, PK_KERNEL_KLT_TRACK = 27, PK_KERNEL_KLT_FINISH = 28 /* klt.hip; bytes = detect: the image once; track: 16 per bilinear sample (gathers, mostly from L2), shape[0] = iterations; finish: the cell and row records */,
+    PK_KERNEL_HOMFIT = 29 /* homfit.hip; bytes = the rows once + the mask + the small outputs, shape[0] = hypotheses */,
     PK_KERNEL_WGRAD_SAME = 11 /* + 2*K3 + PRO, + 4 with the bias sums (K3 = 0): conv_wgrad_same_f32_kernel<K3, PRO, BIAS> */,
     PK_KERNEL_CONV_PAIR = 80 /* + 2*MODE + (BK==32): conv_igemm_f32_pair_kernel<64, 64, BK, 32, 32, MODE> */, PK_KERNEL_CONV_KG = 84 /* + mode: conv_ring_f32_kernel<MODE, 0, 3, 0>; + 2: conv_ring_f32_kernel<0, 0, 1, 1> (fragment prologue); + 3: <0, 0, 2, 1> */, PK_KERNEL_CONV_RING = 90 /* + mode; + 3 for the bf16-operand variants */,
     PK_KERNEL_CONV_PACKED = 70 /* + mode: conv_ring_f32_kernel<MODE, 4, 1, 0> (pre-split weight image); + 3: <0, 4, 1, 1>; + 4 + mode: <MODE, 4, 2, 0>; + 6: <0, 4, 2, 1> */,

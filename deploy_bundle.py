@@ -32,6 +32,11 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     parsed description are uploaded in one copy and decoded on the GPU (csrc/mjpeg_decode.hip: bit for bit libjpeg-turbo's pixels)
     into the buffer the ingest reads.  Implies --ingest device.  A clip the decoder does not take (progressive, 4:2:2 ...) is read
     with Pillow as with --decode host, and a note says so.
+  * --score: after a clip, the kept stabilised frames are scored against the input frames, both at the network's size
+    (stabnet_amd/metrics.py: corner tracks and a robust homography per frame pair on the GPU, then the literature's cropping ratio,
+    distortion value and stability score); <name>_score.json is written and the three numbers are printed.  The stabilised frames
+    are the network's grey output, or, with --fill R / adaptive, the window that was written, converted by the ingest stage.  Off by
+    default; no other output changes with it.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -102,6 +107,9 @@ def build_parser():
                         'is cut at this ratio and may show uncovered pixels')
     p.add_argument('--fill-up', type=float, default=None, metavar='D',
                    help='--fill adaptive: how much the ratio may grow back per frame, >= 0 (default 0.002); zooming in is immediate')
+    p.add_argument('--score', action='store_true',
+                   help='after a clip, score the kept stabilised frames against the input frames at the network\'s size: cropping ratio, '
+                        'distortion value, stability score (stabnet_amd.metrics.score_clip); writes <name>_score.json')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     return p
 
@@ -381,6 +389,41 @@ def fill_second_pass(clip, ing, source, xmaps, ymaps, window, out_size, dev, ste
     return per
 
 
+def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem):
+    """--score: frames 1.. of the clip as ingested (the network's grey input on the 0..255 scale) against the kept frames of the same
+    instants: the network's grey output, or (filled) the window that was written, brought to the network's size by the ingest stage."""
+    import json
+    import torch
+    from stabnet_amd import metrics
+    from stabnet_amd.ingest import FrameIngest
+    n = len(frames_out)
+    if n < metrics.MIN_FRAMES:
+        print('note: --score needs %d kept frames or more; this clip has %d and is not scored' % (metrics.MIN_FRAMES, n))
+        return
+    raw = (lambda t: clip.device_frame(t)) if hasattr(clip, 'device_frame') else (lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev))
+    if ing is not None:
+        unstable = torch.cat([ing.grey(raw(t)) for t in range(1, n + 1)])
+    else:
+        unstable = torch.from_numpy(np.stack([grey_train(clip[t], H, W) for t in range(1, n + 1)])).to(dev)
+    unstable = (unstable + 0.5) * 255.0
+    if filled and colour_out:
+        kept = torch.from_numpy(np.stack(colour_out)).to(dev)
+        kh, kw = kept.shape[1], kept.shape[2]
+        stable = (FrameIngest(kh, kw, 3 if kept.dim() == 4 else 1, H, W, gray=ing.weights, batch=n, device=dev).grey(kept) + 0.5) * 255.0
+        what = 'the written window'
+    else:
+        stable = torch.from_numpy(np.stack(frames_out)).to(dev)
+        what = 'the network\'s grey output'
+    res = metrics.score_clip(unstable, stable)
+    res['stable_frames'] = what
+    with open(stem + '_score.json', 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print('score (%s, %d frames at %dx%d): cropping / distortion / stability = %.4f / %.4f / %.4f'
+          % (what, n, W, H, res['cropping'], res['distortion'], res['stability']))
+    print('wrote', stem + '_score.json')
+
+
 def main():
     args = parse_args()
     import torch
@@ -584,6 +627,11 @@ def main():
                             write_fill_json(stem, 'auto', fwin, ans, kept, fill_report(per, kept), None)
                 except Exception:
                     traceback.print_exc()
+                if args.score:
+                    try:
+                        score_outputs(clip, frames_out, colour_out, ing, window is not None or bool(fill_params), H, W, dev, stem)
+                    except Exception:
+                        traceback.print_exc()
 
 
 if __name__ == '__main__':

@@ -859,6 +859,43 @@ int stabnet_klt_matches(const float* i0, const float* i1, int pixel_stride0, int
                         int levels, int min_side, int r, int border, int cell, float floor, float quality, int R, int iters, float min_eig, float fb,
                         int max_matches, void* workspace, size_t workspace_bytes, float* matches, int* n, void* stream, void* prof);
 
+/* ---- beside the matches: a robust homography per pair, for scoring a stabilised clip (csrc/homfit.hip; tests/homfit_model.py is the yardstick) ----
+ * RANSAC with a fixed number of four-point hypotheses, a least-squares refit over the winner's inliers, the final inlier mask
+ * [external: restated from Fischler / Bolles 1981 and Heckbert's projective mapping through the unit square, nothing linked].
+ * matches [B][M][4] float32 and n [B] int32 as stabnet_klt_matches writes them, on the device: a row is (x0, y0, x1, y1) in the frame
+ * 2x/W - 1, 2y/H - 1; only the first n[b] rows of pair b are read (n is clamped to 0..M), staged once in LDS.  One workgroup of 256
+ * threads per pair.  float32 and float64 operations are single operations, rounded once, in this order; / and sqrt are the correctly
+ * rounded ones; uint32 arithmetic wraps.
+ * 1 mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16.  chain = mix(mix(seed + 0x9e3779b9) + b);
+ *   base_k = mix(chain + k); draw d = 0..15 of hypothesis k: j = (uint64(mix(base_k + d)) * n) >> 32, taken unless the sample holds
+ *   j already or is complete.  A hypothesis with fewer than four indices after 16 draws is invalid.  Thread t owns k = t, t + 256, ...
+ * 2 With the sample's rows i = 0..3 in the order drawn, p_i = (x0, y0) and q_i = (x1, y1):  adj(p) = the rows
+ *   (y1-y2, x2-x1, x1*y2 - x2*y1), (y2-y0, x0-x2, x2*y0 - x0*y2), (y0-y1, x1-x0, x0*y1 - x1*y0) of p_0..2; lambda_i = (adj_i0*x3 +
+ *   adj_i1*y3) + adj_i2; mu_i the same from q;  s_0 = mu_0*(lambda_1*lambda_2), s_1 = mu_1*(lambda_0*lambda_2), s_2 = mu_2*(lambda_0*
+ *   lambda_1);  t_0i = q_i.x*s_i, t_1i = q_i.y*s_i, t_2i = s_i;  G_rc = (t_r0*adj(p)_0c + t_r1*adj(p)_1c) + t_r2*adj(p)_2c;
+ *   h_0..7 = G_0..7 / G_8.  Invalid when any of the eight is not finite.
+ * 3 Row i < n is an inlier of h when w = (h6*x0 + h7*y0) + 1 > w_min and ((u/w - x1)*(W/2))^2 + ((v/w - y1)*(H/2))^2 <= thr_px*thr_px,
+ *   u = (h0*x0 + h1*y0) + h2, v = (h3*x0 + h4*y0) + h5.  The best hypothesis is the valid one with the most inliers, ties to the smallest k.
+ *   n < 4, no valid hypothesis, or fewer than max(4, min_inliers) inliers: status 0, Hm and mask all 0, count 0, best -1.
+ * 4 Refit in float64 over the best hypothesis's inliers: the normal equations of the rows (x, y, 1, 0, 0, 0, -u*x, -u*y | u) and
+ *   (0, 0, 0, x, y, 1, -v*x, -v*y | v), (x, y, u, v) = the row.  Their 36 + 8 entries are 23 distinct sums (the others repeat one or are 0):
+ *   S0..5 = x*x, x*y, x, y*y, y, 1;  S6..11 = (u*x)*x, (u*x)*y, u*x, (u*y)*y, u*y, u;  S12..17 = the same with v;  S18..22 = q*(x*x),
+ *   q*(x*y), q*(y*y), q*x, q*y with q = u*u + v*v.  Thread t adds its inlier rows t, t + 256, ... in order from 0; six steps with partner
+ *   distances 32, 16, 8, 4, 2, 1 inside each 64-lane wave, each S = S + the partner's S; then ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   Lower triangle: A00 A10 A11 A20 A21 A22 = S0 S1 S3 S2 S4 S5, again for A33..A55; A6. = -S6 -S7 -S8 -S12 -S13 -S14 S18;
+ *   A7. = -S7 -S9 -S10 -S13 -S15 -S16 S19 S20; b = S8 S10 S11 S14 S16 S17 -S21 -S22.  Cholesky column by column: d = Ajj - sum_k<j
+ *   Ljk*Ljk (k ascending, one subtraction each), Ljj = sqrt(d), Lij = (Aij - sum_k<j Lik*Ljk) / Ljj; then L z = b and L^T h = z the
+ *   same way (k ascending).  A d that is not > 0, or a solution that is not finite after its one rounding to float32, keeps the
+ *   hypothesis: status 2; else status 1.
+ * 5 mask and count: step 3's test under the final Hm (h33 = 1); mask is 0 from row n on.
+ * Hm [B][9] float32, mask [B][M] uint8, count, status, best [B] int32, all on the device.  No workspace, no atomics, no allocation,
+ * nothing synchronises, reads back or copies from the host; one launch on `stream`: capturable in a hipGraph.
+ * Bad arguments (-1, before anything touches the GPU): null pointers, B outside 1..65535, M outside 4..1024 (16 KiB of LDS), H or W
+ * outside 1..2^20, hypotheses outside 1..65536, thr_px not positive and finite, min_inliers < 0, seed < 0, w_min negative or not
+ * finite, matches not 16-byte aligned. */
+int stabnet_homfit(const float* matches, const int* n, int B, int M, int H, int W, int hypotheses, float thr_px, int min_inliers, int seed,
+                   float w_min, float* Hm, unsigned char* mask, int* count, int* status, int* best, void* stream, void* prof);
+
 #ifdef __cplusplus
 }
 #endif
