@@ -28,6 +28,13 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     chosen per frame on the GPU (stabnet_fill_window_update, then stabnet_warp_rev_bundle2_win_dev): the largest centred window that
     provably shows no uncovered pixel, never below --fill-min, growing back by at most --fill-up per frame.  All three write
     <name>_fill_window.json.
+  * --fill history [--fill-age 64] [--fill-feather 8] (with --ingest device, a colour clip, the serial loop): full-frame output.  Nothing
+    is cut: a pixel the stabilised frame does not cover is taken from what earlier stabilised frames showed there, moved by a
+    homography between the two stabilised frames that is fitted on the GPU (stabnet_amd/mosaic.py, csrc/mosaic.hip: corner tracks of
+    the network's grey output, a coverage guard, the robust fit, one composing launch), at most --fill-age frames old, blended over
+    --fill-feather pixels at the frame's edge.  Written beside everything the run writes without the flag: <name>_fill.npy, with
+    --mjpg <name>_fill.avi, and <name>_fill_history.json (parameters, per frame the fresh / blended / history / empty pixel counts,
+    the fit's status and inliers, the totals).
   * --decode device: the frames of a Motion-JPEG .avi are not decoded up front with Pillow; per frame the compressed bytes and their
     parsed description are uploaded in one copy and decoded on the GPU (csrc/mjpeg_decode.hip: bit for bit libjpeg-turbo's pixels)
     into the buffer the ingest reads.  Implies --ingest device.  A clip the decoder does not take (progressive, 4:2:2 ...) is read
@@ -96,17 +103,23 @@ def build_parser():
     p.add_argument('--output-size', default='network', choices=['network', 'source'],
                    help='size of the frames that are written: network = --height x --width, the frame resized and then warped as the '
                         'reference does; source (needs --ingest device) = the frame as read, warped at its own size by the network-size maps')
-    p.add_argument('--fill', default=None, metavar='R|auto|adaptive',
+    p.add_argument('--fill', default=None, metavar='R|auto|adaptive|history',
                    help='borderless output (needs --ingest device): crop-and-zoom the stabilised frame to the kept frame\'s own size in the '
                         'remap\'s one gather (stabnet_warp_rev_bundle2_win).  R in (0, 1]: online, every kept frame is the centred window that '
                         'keeps R of each side; auto: a second pass through the largest window of the output\'s aspect ratio inside the '
                         'clip\'s black-free rectangle, written as <name>_fill.npy / _fill.avi; adaptive: online, the window is chosen per '
-                        'frame on the GPU (stabnet_fill_window_update): the largest centred one that shows no uncovered pixel')
+                        'frame on the GPU (stabnet_fill_window_update): the largest centred one that shows no uncovered pixel; history: '
+                        'nothing is cut, uncovered pixels are filled from earlier stabilised frames (stabnet_amd.mosaic), written as '
+                        '<name>_fill.npy / _fill.avi / _fill_history.json')
     p.add_argument('--fill-min', type=float, default=None, metavar='R',
                    help='--fill adaptive: the smallest ratio the window may shrink to, in (0, 1] (default 0.5); a frame that needs less '
                         'is cut at this ratio and may show uncovered pixels')
     p.add_argument('--fill-up', type=float, default=None, metavar='D',
                    help='--fill adaptive: how much the ratio may grow back per frame, >= 0 (default 0.002); zooming in is immediate')
+    p.add_argument('--fill-age', type=int, default=None, metavar='N',
+                   help='--fill history: the oldest earlier frame a filled pixel may come from, 1..254 frames back (default 64)')
+    p.add_argument('--fill-feather', type=int, default=None, metavar='PX',
+                   help='--fill history: width of the blend band at the stabilised frame\'s edge, a power of two 1..64 pixels (default 8)')
     p.add_argument('--score', action='store_true',
                    help='after a clip, score the kept stabilised frames against the input frames at the network\'s size: cropping ratio, '
                         'distortion value, stability score (stabnet_amd.metrics.score_clip); writes <name>_score.json')
@@ -130,12 +143,23 @@ def parse_args(argv=None):
             p.error('--fill-min needs 0 < R <= 1, got %r' % (args.fill_min,))
         if not 0.0 <= args.fill_up < float('inf'):
             p.error('--fill-up needs a finite D >= 0, got %r' % (args.fill_up,))
+    if args.fill != 'history' and (args.fill_age is not None or args.fill_feather is not None):
+        p.error('--fill-age / --fill-feather belong to --fill history')
+    if args.fill == 'history':
+        args.fill_age = 64 if args.fill_age is None else args.fill_age
+        args.fill_feather = 8 if args.fill_feather is None else args.fill_feather
+        if not 1 <= args.fill_age <= 254:
+            p.error('--fill-age needs 1 <= N <= 254, got %r' % (args.fill_age,))
+        if args.fill_feather not in (1, 2, 4, 8, 16, 32, 64):
+            p.error('--fill-feather needs a power of two in 1..64, got %r' % (args.fill_feather,))
+        if args.pipeline:
+            p.error('--fill history runs in the serial loop only: it is not available with --pipeline')
     if args.fill is not None:
-        if args.fill not in ('auto', 'adaptive'):
+        if args.fill not in ('auto', 'adaptive', 'history'):
             try:
                 args.fill = float(args.fill)
             except ValueError:
-                p.error('--fill takes a ratio in (0, 1] or one of the words auto, adaptive, got %r' % (args.fill,))
+                p.error('--fill takes a ratio in (0, 1] or one of the words auto, adaptive, history, got %r' % (args.fill,))
             if not 0.0 < args.fill <= 1.0:                     # (a NaN fails both comparisons)
                 p.error('--fill R needs 0 < R <= 1, got %r' % (args.fill,))
         if args.ingest != 'device':
@@ -197,13 +221,15 @@ def jpeg_options(args):
 
 
 def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None,
-               window=None, black_win=None, adaptive=None, fill_log=None):
+               window=None, black_win=None, adaptive=None, fill_log=None, mosaic=None, fill_frames=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
     uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
     raw frame is warped at its own size and its coverage counted there.  window, black_win (--fill R): the kept frame is that window of
     the stabilised frame at the kept frame's size, its coverage counted at the output pixels.  adaptive (--fill adaptive; a
-    warp.AdaptiveFill): the window is the one the GPU chooses for the frame; fill_log gets (window, stats) per frame."""
+    warp.AdaptiveFill): the window is the one the GPU chooses for the frame; fill_log gets (window, stats) per frame.  mosaic (--fill
+    history; a mosaic.Mosaic): the kept colour frame is remapped with its coordinates written out, composed over the canvas of the
+    earlier frames, and the canvas goes to fill_frames; every other output is the one of a run without it."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
@@ -211,6 +237,8 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     raw = (lambda t: clip.device_frame(t)) if hasattr(clip, 'device_frame') else (lambda t: torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev))
     if adaptive is not None:
         adaptive.reset()
+    if mosaic is not None:
+        mosaic.reset()
     if ing is not None:
         stream.start_u8(raw(0), ing)
     else:
@@ -230,6 +258,15 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
             colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], win, black_count=black_win).cpu().numpy())
             if adaptive is not None:
                 fill_log.append((adaptive.window[0].cpu().numpy(), adaptive.stats[0].cpu().numpy()))
+        elif mosaic is not None:
+            # the same remap as below with px_out / py_out written (the same output bytes), then the composite over the earlier frames
+            if black_src is not None:
+                kept_frame, px, py = warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src, return_maps=True)
+            else:
+                kept_frame, px, py = warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map'], return_maps=True)
+            colour_out.append(kept_frame.cpu().numpy())
+            canvas = mosaic.update(kept_frame.reshape(1, mosaic.SH, mosaic.SW, 3), px, py, r['output'][..., 0], r['black_pix'])
+            fill_frames.append(canvas[0].cpu().numpy())
         elif black_src is not None:
             # where the reference resizes the colour frame down and warps it (deploy_bundle.py:303): the frame as read, warped as it is
             colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src).cpu().numpy())
@@ -339,6 +376,39 @@ def write_fill_adaptive_json(stem, params, fill_log, nodes, out_size, uncovered,
                    'uncovered': dict(uncovered, pixels_ever_uncovered=pixels_ever)}, f, indent=1)
         f.write('\n')
     print('wrote', stem + '_fill_window.json')
+
+
+def write_fill_history(stem, mosaic, fill_frames, first, enc_options, fps, dev, args):
+    """--fill history: <name>_fill.npy, with --mjpg <name>_fill.avi (as <name>.avi: the first frame as read comes first), and
+    <name>_fill_history.json from the one readback of the per-frame log."""
+    import json
+    import torch
+    from stabnet_amd import mosaic as mosaic_mod
+    filled = np.stack(fill_frames)
+    np.save(stem + '_fill.npy', filled)
+    print('wrote', stem + '_fill.npy')
+    if args.mjpg:
+        from stabnet_amd.avi import AviMjpegWriter
+        from stabnet_amd.mjpeg import MjpegEncoder
+        oh, ow = filled.shape[1:3]
+        enc = MjpegEncoder(oh, ow, 3, device=dev, **enc_options)
+        with AviMjpegWriter(stem + '_fill.avi', ow, oh, fps) as w:
+            w.write(enc.encode_bytes(torch.from_numpy(first).to(dev))[0])
+            for f in filled:
+                w.write(enc.encode_bytes(torch.from_numpy(np.ascontiguousarray(f)).to(dev))[0])
+        print('wrote %s (%d frames %dx%d)' % (stem + '_fill.avi', len(filled) + 1, ow, oh))
+    log = mosaic.log()
+    tot = mosaic_mod.totals(log)
+    with open(stem + '_fill_history.json', 'w') as f:
+        json.dump({'mode': 'history', 'params': dict(mosaic.params_dict(), fill_age=args.fill_age, fill_feather=args.fill_feather),
+                   'output_size': [mosaic.SH, mosaic.SW], 'network_size': [mosaic.H, mosaic.W], 'frames': int(len(filled)),
+                   'per_frame': {k: [int(v) for v in log[k][:, 0]] for k in mosaic_mod.LOG_FIELDS}, 'totals': tot}, f, indent=1)
+        f.write('\n')
+    px = max(tot['fresh'] + tot['blended'] + tot['history'] + tot['empty'], 1)
+    print('fill history: %.3f %% of the pixels came from earlier frames, %.3f %% were blended at the edge, %.3f %% stayed empty; '
+          '%d of %d frames had no motion model' % (100.0 * tot['history'] / px, 100.0 * tot['blended'] / px, 100.0 * tot['empty'] / px,
+                                                   tot['frames_without_model'], len(filled)))
+    print('wrote', stem + '_fill_history.json')
 
 
 def fill_report(per_frame, out_size):
@@ -506,6 +576,7 @@ def main():
         window, black_win, first, source = None, None, None, False      # --fill R: the window, the coverage at its output pixels
         fill, kept = None, (H, W)            # --fill as it applies to this clip; the kept frame's size
         adaptive, fill_params, fill_log = None, None, []     # --fill adaptive: the window's state on the device; (window, stats) per frame
+        mosaic, fill_frames = None, []       # --fill history: the canvas of the earlier frames on the device; the filled frames
         try:
             if args.ingest == 'device':
                 shp = np.shape(clip[0])
@@ -529,6 +600,18 @@ def main():
             kept = (ing.sh, ing.sw) if source else (H, W)
             if args.fill is not None and fill is None:
                 print('note: --fill needs a remapped frame to cut; this clip keeps the network\'s grey output and is written as without it')
+            elif fill == 'history' and ing.C != 3:
+                fill = None
+                print('note: --fill history composes colour frames; this clip is grey and is written as without it')
+            elif fill == 'history':
+                from stabnet_amd.mosaic import Mosaic, MosaicParams
+                mosaic = Mosaic(1, kept[0], kept[1], H, W, MosaicParams(feather_log2=args.fill_feather.bit_length() - 1, max_age=args.fill_age),
+                                device=dev)
+                print('note: --fill history: pixels the stabilised frame does not cover are filled from earlier stabilised frames (at most %d '
+                      'frames old, a %d px blend band), at %dx%d; written as %s_fill.npy beside the usual outputs'
+                      % (args.fill_age, args.fill_feather, kept[1], kept[0], os.path.basename(stem)))
+                if args.score:
+                    print('note: --score scores the online frames (the network\'s grey output) as without --fill history, not the filled ones')
             elif fill == 'adaptive':
                 fill_params = dict(r_min=args.fill_min, up=args.fill_up, margin_q=8)
                 black_win = torch.zeros(kept, dtype=torch.int32, device=dev)
@@ -566,7 +649,7 @@ def main():
                 black_win = pipe_win if (window is not None or fill_params) else None
             else:
                 length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src,
-                                              window, black_win, adaptive, fill_log)
+                                              window, black_win, adaptive, fill_log, mosaic, fill_frames)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -616,6 +699,10 @@ def main():
                                                  int((black_win > 0).sum().item()))
                         if tot_time > 0:
                             print('fps={}'.format(length / tot_time))
+                    elif mosaic is not None and fill_frames:
+                        if first is None:
+                            first = np.ascontiguousarray(fill_frames[0])      # (only used with --mjpg, which sets it)
+                        write_fill_history(stem, mosaic, fill_frames, first, jpeg_options(args), fps, dev, args)
                     elif fill == 'auto' and colour_out:
                         if not ans:
                             print('note: --fill auto: no black-free rectangle in this clip; no _fill files are written')

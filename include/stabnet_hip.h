@@ -896,6 +896,64 @@ int stabnet_klt_matches(const float* i0, const float* i1, int pixel_stride0, int
 int stabnet_homfit(const float* matches, const int* n, int B, int M, int H, int W, int hypotheses, float thr_px, int min_inliers, int seed,
                    float w_min, float* Hm, unsigned char* mask, int* count, int* status, int* best, void* stream, void* prof);
 
+/* ---- full-frame output: uncovered pixels filled from earlier stabilised frames (csrc/mosaic.hip; tests/mosaic_model.py is the yardstick) ----
+ * [external: the mosaicking step of full-frame stabilisation as the literature describes it, Matsushita et al. 2006 among others,
+ * restated with one global homography; nothing linked.]  float32 and float64 operations are single operations, rounded once, in
+ * this order; everything else is integer arithmetic.
+ *
+ * stabnet_mosaic_guard_matches: keep only the matches that lie on content.  matches [B][M][4] float32 and n [B] int32 as
+ * stabnet_klt_matches writes them (only the first n[b] rows are read, n clamped to 0..M); black0, black1 [B][H][W] float32: the
+ * network's `black` of the frame each end of a row lives in ((x0, y0): black0; (x1, y1): black1).  An end (xn, yn) is SAFE when, with
+ * X = ((xn + 1)*W)*0.5 and Y = ((yn + 1)*H)*0.5 in float32, xr = rintf(X), yr = rintf(Y) (half to even), g = guard:
+ * xr - g >= 0, xr + g <= W - 1, yr - g >= 0, yr + g <= H - 1 (float32; all false for a NaN) and black[yr + dy][xr + dx] < 0.5 for
+ * every |dx|, |dy| <= g (a NaN black is not < 0.5).  Row r < n[b] is kept when both ends are safe; the kept rows go to out_matches
+ * [B][M][4] in their order, zeros from row out_n[b] on; out_n [B] int32.  One workgroup of 1024 threads per pair, a row per thread,
+ * positions from wave ballots and sixteen LDS slots: no atomics, no workspace, nothing allocates, synchronises or reads back;
+ * one launch on `stream`, capturable in a hipGraph.
+ * Bad arguments (-1, before anything touches the GPU): null pointers, out_matches == matches, B outside 1..65535, M outside 4..1024,
+ * guard outside 0..16, H or W outside 1..2^20, matches or out_matches not 16-byte aligned.
+ *
+ * stabnet_mosaic_compose: one launch per frame over [N][SH][SW] output pixels, uint8 BGR.  warped [N][SH][SW][3], px, py float32
+ * [N][SH][SW]: out, px_out, py_out of stabnet_warp_rev_bundle2_src for this frame; canvas_prev [N][SH][SW][3] and age_prev uint8
+ * [N][SH][SW]: the previous call's canvas_cur, age_cur (age 255: the pixel holds nothing); Hm [N][9] float32 and status [N] int32 as
+ * stabnet_homfit writes them for matches tracked from frame t (i0) into frame t - 1 (i1), both read WHEN THE KERNEL RUNS: a captured
+ * graph replays with what an earlier launch on the stream wrote.  H, W: the network's size (the frame Hm lives in).
+ * Per pixel (i, j) of stream n, F = 32 << feather_log2:
+ * 1 q(p) of a float32 p: t = fmin(fmax(p*32, -2e9), 2e9), rintf(t) as int32, -2e9 for a NaN (the remap's quantisation to 1/32 px).
+ *   qx = q(px), qy = q(py); d = min(qx, 32*(SW-1) - qx, qy, 32*(SH-1) - qy); covered = d >= 0 (the remap's own coverage rule);
+ *   a = min(max(d, 0), F).
+ * 2 d >= F: out = warped, age = 0, counted fresh; nothing else is read.
+ * 3 Otherwise the history sample; unavailable at once unless status[n] is 1 or 2.  In float64, h = Hm[n] widened:
+ *   ax = 2/SW, cx = (1/SW - 1/W) - 1, ay = 2/SH, cy = (1/SH - 1/H) - 1       (A: x_n = ax*j + cx, cv2's half-pixel convention between
+ *   sx = 0.5*SW, tx = (0.5*SW + (0.5*SW)/W) - 0.5, sy, ty alike with SH, H    SW and W pixels, then 2u/W - 1; B: j = sx*x_n + tx)
+ *   m = h A: m[3r] = h[3r]*ax, m[3r+1] = h[3r+1]*ay, m[3r+2] = (h[3r]*cx + h[3r+1]*cy) + h[3r+2], r = 0..2;
+ *   G = B m: G[c] = sx*m[c] + tx*m[6+c], G[3+c] = sy*m[3+c] + ty*m[6+c], G[6+c] = m[6+c], c = 0..2;
+ *   u = (G0*j + G1*i) + G2, v = (G3*j + G4*i) + G5, w = (G6*j + G7*i) + G8; unavailable unless w > (double)w_min (false for a NaN);
+ *   qx = q64(u/w), qy = q64(v/w), q64 being q in float64 (fmin, fmax, rint, int32).  ix = qx >> 5, fx = qx & 31, iy, fy alike; the
+ *   taps (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1) of canvas_prev have the weights (32-fy)*(32-fx), (32-fy)*fx, fy*(32-fx),
+ *   fy*fx (sum 1024; no table quirk); a tap COUNTS when its weight is not 0.  Available when every counting tap lies inside the
+ *   frame and has age_prev < 255 and hist_age = 1 + (the largest age_prev of the counting taps) <= max_age.
+ *   hist_c = (sum of value*weight + 512) >> 10 per channel (a tap that does not count adds nothing).
+ * 4 covered, available:   out_c = (warped_c*a + hist_c*(F - a) + F/2) >> (5 + feather_log2); age = 0 when 2*a >= F, else hist_age; blended
+ *   uncovered, available: out = hist, age = hist_age; history.     covered, unavailable: out = warped, age = 0; fresh.
+ *   uncovered, unavailable: out = 0, age = 255; empty.
+ * canvas_cur [N][SH][SW][3], age_cur [N][SH][SW]; counts [N][4] int32 += {fresh, blended, history, empty} of the frame (the caller
+ * zeroes it on the stream; integer atomics after a wave / LDS sum, a workgroup covering several rows and adding two counters with
+ * one 64-bit add where counts is 8-byte aligned: any order gives the same sums).
+ * Two kernels with the same results: four pixels per thread (three dwords and two float4 in, three dwords and one age dword out)
+ * when SW % 4 == 0, warped, canvas_cur, age_cur are 4-byte and px, py 16-byte aligned; one pixel per thread otherwise.  History taps
+ * are read as six contiguous bytes per row; nothing outside a stream's own canvas is read.  Nothing allocates, synchronises or reads
+ * back; one launch on `stream`, capturable in a hipGraph.
+ * Bad arguments (-1, before anything touches the GPU): null pointers, N outside 1..65535, SH or SW outside 1..32767, H or W outside
+ * 1..2^20, feather_log2 outside 0..6, max_age outside 1..254, w_min negative or not finite, canvas_cur == canvas_prev or
+ * age_cur == age_prev. */
+int stabnet_mosaic_guard_matches(const float* matches, const int* n, const float* black0, const float* black1, int B, int M, int H, int W,
+                                 int guard, float* out_matches, int* out_n, void* stream);
+int stabnet_mosaic_compose(const unsigned char* warped, const float* px, const float* py, const unsigned char* canvas_prev,
+                           const unsigned char* age_prev, const float* Hm, const int* status, int N, int SH, int SW, int H, int W,
+                           int feather_log2, int max_age, float w_min, unsigned char* canvas_cur, unsigned char* age_cur, int* counts,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
