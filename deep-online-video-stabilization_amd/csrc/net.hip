@@ -731,6 +731,7 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_REMAP_WIN4: return "remap_win4_kernel";
         case PK_KERNEL_REMAP_WIN_DEV: return "remap_win_dev_kernel";
         case PK_KERNEL_REMAP_WIN4_DEV: return "remap_win4_dev_kernel";
+        case PK_KERNEL_REMAP_I420: return "remap_i420_kernel";
         case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
         case PK_KERNEL_TVL1_STEP: return "tvl1_step_kernel";
         case PK_KERNEL_TVL1_FUSED: return "tvl1_fused_kernel";

@@ -11,7 +11,8 @@ enum {
     PK_KERNEL_MAP_SHRINK = 37, PK_KERNEL_REMAP_SRC = 38, PK_KERNEL_REMAP_SRC4 = 39 /* remap.hip, stabnet_warp_rev_bundle2_src; bytes = frame gathered + frame written + small maps */,
     PK_KERNEL_REMAP_WIN = 60, PK_KERNEL_REMAP_WIN4 = 61 /* remap.hip, stabnet_warp_rev_bundle2_win; bytes = window gathered + output written + small maps */,
     PK_KERNEL_REMAP_WIN_DEV = 62, PK_KERNEL_REMAP_WIN4_DEV = 63 /* remap.hip, stabnet_warp_rev_bundle2_win_dev; bytes = whole frame (the window is on the device) + output written + small maps */,
-    PK_KERNEL_TF_GET_IMG = 64 /* tf_image.hip; bytes = 12 tap bytes read + 4 written per destination value, every channel named */,
+    PK_KERNEL_REMAP_I420 = 59 /* remap.hip, stabnet_warp_rev_bundle2_i420; bytes = the window of every plane gathered + the planes written + small maps */,
+    PK_KERNEL_TF_GET_IMG = 64/* tf_image.hip; bytes = 12 tap bytes read + 4 written per destination value, every channel named */,
     PK_KERNEL_TVL1_STEP = 57, PK_KERNEL_TVL1_FUSED = 58 /* tvl1.hip, one record per launch; bytes = ten planes read + six written once, shape[0] = sweeps of the launch */,
     PK_KERNEL_TVL1_DOWN = 65, PK_KERNEL_TVL1_GRAD = 66, PK_KERNEL_TVL1_WARP = 67, PK_KERNEL_TVL1_UP = 68, PK_KERNEL_TVL1_MAP = 69 /* tvl1.hip stages; bytes = every plane read or written, once */,
     PK_KERNEL_KLT_DETECT = 26, PK_KERNEL_KLT_TRACK = 27, PK_KERNEL_KLT_FINISH = 28 /* klt.hip; bytes = detect: the image once; track: 16 per bilinear sample (gathers, mostly from L2), shape[0] = iterations; finish: the cell and row records */,

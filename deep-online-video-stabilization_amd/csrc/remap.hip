@@ -369,6 +369,76 @@ __global__ __launch_bounds__(256) void cvt_train2img_kernel(const float* __restr
     }
 }
 
+// ---- a planar YUV 4:2:0 frame (I420: the Y plane [SH, SW], then U and V [SH/2, SW/2], all dense), every plane in ONE launch ----
+// Each plane is what remap_win_kernel gives it as a C == 1 image of the plane's own size: the Y plane at (SH, SW) -> (OH, OW) through the
+// window, a chroma plane at (SH/2, SW/2) -> (OH/2, OW/2) through the halved window with its own sx, cx, sy, cy (src_remap_args of the
+// plane's size) -- with centred chroma siting that is the luma coordinate of the chroma sample, halved.  One difference: a tap outside
+// the plane reads a BORDER VALUE instead of 0 (cv2.remap's borderValue): (Y, U, V) = (0, 0, 0) is saturated green, so chroma reads 128.
+// Coverage is counted at the luma output pixel.  The window is always given (the whole frame: steps of exactly 1, _src's bits).
+struct I420Geom { SrcRemapArgs a; int OH, OW; WinSteps ws; };        // one plane kind: a.C == 1, a.row_stride == a.SW
+struct I420Args {
+    I420Geom g[2];                           // luma, chroma
+    size_t src_off[3], out_off[3];           // of planes Y, U, V inside a frame, bytes
+    size_t src_frame, out_frame;             // bytes from one frame to the next
+    int px4[3];                              // the plane takes the four-pixel path: its OW % 4 == 0 and its output rows are 4-byte aligned
+    int border[3];
+};
+
+// PX consecutive output pixels of row y of one plane from x on; orow, black_row: the row's first output byte / count (or null)
+template <int PX>
+__device__ __forceinline__ void remap_plane_pixels(const unsigned char* __restrict__ im, const I420Geom& g, const float* __restrict__ mx,
+        const float* __restrict__ my, int x, int y, int border, unsigned char* __restrict__ orow, int* __restrict__ black_row) {
+    const SrcRemapArgs& a = g.a;
+    const Taps1D ty = cv_taps_at(g.ws.y0 + ((double)y + 0.5) * g.ws.ystep, a.h, a.yscale);
+    unsigned ob = 0u;
+#pragma unroll
+    for (int e = 0; e < PX; ++e) {
+        const Taps1D tx = cv_taps_at(g.ws.x0 + ((double)(x + e) + 0.5) * g.ws.xstep, a.w, a.xscale);
+        const SrcCoord c = remap_src_coord<true>(mx, my, a, tx, ty);
+        const RemapTaps t = remap_taps(c);
+        const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
+        const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix] : border;
+        const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix + 1] : border;
+        const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix] : border;
+        const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix + 1] : border;
+        unsigned o = remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
+        if constexpr (PX == 4) {
+            // The byte is finished in a register of its own before it is packed (an empty statement the compiler cannot see through).
+            // Left to itself, hipcc folds the shift and clamp of pixels 0 and 1 into one v_ashr_pk_u8_i32 on the first accumulator's own
+            // register and ORs pixels 2 and 3 into the result as if its bits 31:16 were zero; on the MI355X they still held bits 31:16
+            // of that accumulator, so pixel 2 came out as value | (acc0 >> 16) & 0xff (seen against the one-pixel path and the model).
+            asm volatile("" : "+v"(o));
+            ob |= o << (8 * e);
+        } else {
+            orow[x] = (unsigned char)o;
+        }
+        if (black_row != nullptr && remap_src_black(c, a.SH, a.SW)) black_row[x + e] += 1;
+    }
+    if constexpr (PX == 4) *reinterpret_cast<unsigned*>(orow + x) = ob;
+}
+
+// grid (cdiv(items, blockDim.x), OH [+ 2 * (OH / 2)], N): one workgroup per row segment of ONE plane -- rows 0 .. OH - 1 are the Y plane's,
+// then the U plane's OH / 2, then the V plane's -- so the plane, its path and its vertical taps are workgroup-uniform.  items: the most
+// any plane needs (OW / 4 or OW threads for a Y row, half of that for a chroma row on the same path).
+__global__ __launch_bounds__(256) void remap_i420_kernel(const unsigned char* __restrict__ src, I420Args ia, const float* __restrict__ small_maps,
+        unsigned char* __restrict__ out, int* __restrict__ black_count) {
+    const int n = blockIdx.z, OH = ia.g[0].OH, CH = ia.g[1].OH;
+    int y = blockIdx.y, plane = 0;
+    if (y >= OH) { y -= OH; plane = 1; if (y >= CH) { y -= CH; plane = 2; } }
+    const I420Geom& g = ia.g[plane != 0];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, px4 = ia.px4[plane];
+    const int x = px4 ? t * 4 : t;
+    if (x >= g.OW) return;
+    const size_t hw = (size_t)g.a.h * g.a.w;
+    const float* mx = small_maps + ((size_t)n * 2 + 0) * hw;
+    const float* my = small_maps + ((size_t)n * 2 + 1) * hw;
+    const unsigned char* im = src + (size_t)n * ia.src_frame + ia.src_off[plane];
+    unsigned char* orow = out + (size_t)n * ia.out_frame + ia.out_off[plane] + (size_t)y * g.OW;
+    int* black_row = (plane == 0 && black_count != nullptr) ? black_count + ((size_t)n * OH + y) * g.OW : nullptr;
+    if (px4) remap_plane_pixels<4>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
+    else remap_plane_pixels<1>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
+}
+
 // STABNET_REMAP_VEC4=0: the one-pixel-per-thread kernels everywhere (debug switch; read once)
 static int remap_vec4_enabled() {
     static const int v4 = []() { const char* v = getenv("STABNET_REMAP_VEC4"); return v ? atoi(v) : 1; }();
@@ -523,6 +593,76 @@ int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, in
         float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
     return remap_src_entry(REMAP_WIN_DEV, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
                            px_out, py_out, stream, profp);
+}
+
+/* stabnet_warp_rev_bundle2_win of a planar 4:2:0 frame (remap_i420_kernel above): src N frames frame_stride_bytes apart, each the Y plane
+ * [SH,SW] and, with planes == 3, U and V [SH/2,SW/2] behind it, dense, any base alignment; out the same layout at OH x OW, dense.
+ * window {y0, x0, wh, ww} in HOST memory, in pixel-edge units of the stabilised LUMA frame (null: the whole frame, OH, OW == SH, SW); a
+ * chroma plane goes through the halved window.  Taps outside a plane read border_y (Y) or 128 (U, V).  black_count (optional, int32
+ * [N,OH,OW]): at the luma output pixel.  Two launches: the shrink, then one gather over every plane of every frame. */
+int stabnet_warp_rev_bundle2_i420(const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, int border_y, unsigned char* out, int* black_count,
+        float* workspace, void* stream, void* profp) {
+    const char* who = "warp_rev_bundle2_i420";
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "%s: null pointer", who);
+    SN_REQUIRE(planes == 1 || planes == 3, "%s: planes must be 1 (Y only) or 3 (Y, U, V of a 4:2:0 frame), got %d", who, planes);
+    SN_REQUIRE(N >= 1 && N <= 65535, "%s: batch %d outside 1..65535", who, N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767, "%s: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", who, SH, SW);
+    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "%s: output %dx%d outside 1..32767", who, OH, OW);
+    SN_REQUIRE(planes == 1 || ((SH | SW | OH | OW) & 1) == 0, "%s: a 4:2:0 frame has even sides, got source %dx%d, output %dx%d", who, SH, SW, OH, OW);
+    const size_t src_y = (size_t)SH * SW, src_c = planes == 3 ? (size_t)(SH / 2) * (SW / 2) : 0, src_bytes = src_y + 2 * src_c;
+    SN_REQUIRE(frame_stride_bytes >= src_bytes, "%s: frame stride %zu < the frame's %zu bytes", who, frame_stride_bytes, src_bytes);
+    SN_REQUIRE(border_y >= 0 && border_y <= 255, "%s: border_y %d outside 0..255", who, border_y);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "%s: maps %dx%d leave nothing at rate %d", who, H, W, rate);
+    double y0 = 0.0, x0 = 0.0, wh = (double)SH, ww = (double)SW;
+    if (window == nullptr) {
+        SN_REQUIRE(OH == SH && OW == SW, "%s: a null window is the whole frame at its own size, got output %dx%d of source %dx%d", who, OH, OW, SH, SW);
+    } else {
+        y0 = window[0]; x0 = window[1]; wh = window[2]; ww = window[3];
+        SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
+                   "%s: window (%g, %g, %g, %g) is not finite", who, y0, x0, wh, ww);
+        SN_REQUIRE(wh > 0.0 && ww > 0.0, "%s: window %g x %g is empty", who, wh, ww);
+        SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
+                   "%s: window (%g, %g, %g, %g) leaves the %dx%d frame", who, y0, x0, wh, ww, SH, SW);
+    }
+    hipStream_t st = (hipStream_t)stream; Prof* prof = static_cast<Prof*>(profp);
+    int rc = sn_check_device(src, "warp_rev_bundle2_i420: src", st);
+    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_i420: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_i420: workspace", st);
+    if (rc) return rc;
+    const int h = H / rate, w = W / rate;
+    rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, prof);
+    if (rc) return rc;
+    I420Args ia;
+    const size_t out_y = (size_t)OH * OW, out_c = planes == 3 ? (size_t)(OH / 2) * (OW / 2) : 0;
+    ia.src_frame = frame_stride_bytes; ia.out_frame = out_y + 2 * out_c;
+    ia.src_off[0] = 0; ia.src_off[1] = src_y; ia.src_off[2] = src_y + src_c;
+    ia.out_off[0] = 0; ia.out_off[1] = out_y; ia.out_off[2] = out_y + out_c;
+    ia.border[0] = border_y; ia.border[1] = 128; ia.border[2] = 128;
+    int items = 0;
+    for (int k = 0; k < 2; ++k) {                            // luma; chroma: every length and the window halved (exact)
+        const int d = k + 1;
+        if (k == 1 && planes == 1) { ia.g[1] = ia.g[0]; ia.g[1].OH = 0; break; }
+        I420Geom& g = ia.g[k];
+        src_remap_args(g.a, SH / d, SW / d, 1, H, W, h, w, (size_t)(SW / d));
+        g.OH = OH / d; g.OW = OW / d;
+        g.ws = {x0 / d, y0 / d, (ww / d) / (double)g.OW, (wh / d) / (double)g.OH};
+    }
+    for (int p = 0; p < 3; ++p) {
+        const I420Geom& g = ia.g[p != 0];
+        const bool aligned = (((size_t)out + ia.out_off[p]) & 3) == 0 && (N == 1 || (ia.out_frame & 3) == 0);
+        ia.px4[p] = (p < planes && remap_vec4_enabled() && g.OW % 4 == 0 && aligned) ? 1 : 0;
+        if (p < planes && (ia.px4[p] ? g.OW / 4 : g.OW) > items) items = ia.px4[p] ? g.OW / 4 : g.OW;
+    }
+    const int threads = items >= 256 ? 256 : ((items + 63) & ~63);       // whole waves, a row segment each
+    const dim3 grid(cdiv(items, threads), ia.g[0].OH + (planes == 3 ? 2 * ia.g[1].OH : 0), N);
+    // algorithmic bytes: the window of every plane gathered once, the output written once, the two small maps
+    const double cf = planes == 3 ? 1.5 : 1.0, bytes = (double)N * ((wh * ww + (double)OH * OW) * cf + 8.0 * h * w);
+    const bool rec = prof && prof->begin(st);
+    remap_i420_kernel<<<grid, threads, 0, st>>>(src, ia, workspace, out, black_count);
+    if (rec) prof->end(st, PK_KERNEL_REMAP_I420, 0.0, bytes);
+    SN_LAUNCH_CHECK("remap_i420_kernel");
+    return STABNET_OK;
 }
 
 /* The adaptive window of one frame per stream (fill_window_kernel above): x_map, y_map [N,H,W] as the remap receives them; state

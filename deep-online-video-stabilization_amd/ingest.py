@@ -41,6 +41,12 @@ def lut256() -> np.ndarray:
     return (np.arange(256, dtype=np.float64) * (1. / 255) - 0.5).astype(np.float32)
 
 
+def lut256_limited() -> np.ndarray:
+    """lut256 for a LIMITED-range Y plane (16..235): float32(clip((u - 16) * 255/219, 0, 255) * (1./255) - 0.5), computed in float64."""
+    u = np.arange(256, dtype=np.float64)
+    return (np.clip((u - 16.0) * 255 / 219, 0.0, 255.0) * (1. / 255) - 0.5).astype(np.float32)
+
+
 class FrameIngest:
     """Tables of one geometry on the device: source src_h x src_w x channels (3 = BGR, 1 = grey) -> network H x W.
 
@@ -48,9 +54,11 @@ class FrameIngest:
                             (int(H/crop_rate), int(W/crop_rate)) and the centred H x W window of that (config.py:8-15) --, normalised
     colour(u8, out=None) -> uint8 [N,H,W,3]: cv2.resize(frame, (W, H)), the frame that is warped and written
     u8: uint8 device tensor [N,src_h,src_w,channels] ([src_h,src_w,channels] / [src_h,src_w]: N = 1); rows may be strided
-    (u8.stride(-3) bytes apart), pixels must be dense.  Nothing synchronises: both calls can be captured in a hipGraph."""
+    (u8.stride(-3) bytes apart), pixels must be dense.  Nothing synchronises: both calls can be captured in a hipGraph.
+    lut: float32 [256], the normalisation of the resized grey value (default lut256(); lut256_limited() for a limited-range Y plane)."""
 
-    def __init__(self, src_h: int, src_w: int, channels: int, H: int, W: int, crop_rate=1, gray="cv3", batch: int = 1, device="cuda:0"):
+    def __init__(self, src_h: int, src_w: int, channels: int, H: int, W: int, crop_rate=1, gray="cv3", batch: int = 1, device="cuda:0",
+                 lut=None):
         self.sh, self.sw, self.C, self.H, self.W = int(src_h), int(src_w), int(channels), int(H), int(W)
         if self.C not in (1, 3):
             raise _lib.StabnetError("FrameIngest: channels must be 1 (grey) or 3 (BGR), got %r" % (channels,))
@@ -79,7 +87,10 @@ class FrameIngest:
         if self.rh != self.sh:
             self._yk, b, k = pil_taps(self.sh, self.rh)
             self._yb_dev, self._yk_dev = up(b), up(k)
-        self._lut = torch.from_numpy(lut256()).to(self.device)
+        lut = lut256() if lut is None else np.ascontiguousarray(lut)
+        if lut.dtype != np.float32 or lut.shape != (256,):
+            raise _lib.StabnetError("FrameIngest: lut must be a float32 array of 256 entries, got %s %s" % (lut.dtype, list(lut.shape)))
+        self._lut = torch.from_numpy(lut.copy()).to(self.device)
         self._cv = None
         if self.C == 3:
             (xo, xc), (yo, yc) = cv_taps(self.sw, self.W), cv_taps(self.sh, self.H)

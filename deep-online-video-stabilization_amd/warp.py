@@ -268,6 +268,65 @@ def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     return (res, px, py) if return_maps else res
 
 
+def i420_frame_bytes(SH: int, SW: int, planes: int = 3) -> int:
+    """Bytes of one planar frame: the Y plane, and with planes == 3 the U and V planes of a 4:2:0 frame behind it."""
+    return SH * SW if planes == 1 else SH * SW * 3 // 2
+
+
+def warpRevBundle2_i420(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, size, planes: int = 3, window=None, out_size=None,
+                        border_y: int = 0, rate: int = 4, black_count: torch.Tensor = None, out: torch.Tensor = None,
+                        workspace: torch.Tensor = None, prof=None):
+    """warpRevBundle2_win of planar YUV 4:2:0 frames as a Y4M stream carries them (csrc/remap.hip, stabnet_warp_rev_bundle2_i420): no
+    colour conversion, the Y plane and the two half-size chroma planes are warped as the single-channel images they are, in one gather
+    launch.  src_u8: uint8 on the GPU, [N, B] or [B] with B >= the frame's bytes (i420_frame_bytes(SH, SW, planes)): per frame Y [SH,SW],
+    then U, V [SH/2,SW/2], dense, at any byte alignment; size = (SH, SW); planes = 3, or 1 for Y only (Cmono).  window = (y0, x0, wh, ww)
+    in pixel-edge units of the stabilised LUMA frame (host numbers; None: the whole frame), out_size = (OH, OW), default the source's.
+    A tap outside a plane reads border_y (Y; 16 for a limited-range stream) or 128 (U, V).  black_count: optional int32 [N,OH,OW], += 1
+    where the frame does not cover the luma output pixel.  out: optional contiguous uint8 tensor of N * i420_frame_bytes(OH, OW, planes)
+    elements; workspace: optional float32 tensor of 2*N*(H//rate)*(W//rate) elements.  With both given nothing allocates, and nothing
+    ever synchronises.  -> uint8 [N, bytes] ([bytes] for a 1-D source)."""
+    what = "warpRevBundle2_i420"
+    if not isinstance(src_u8, torch.Tensor) or not src_u8.is_cuda:
+        raise _lib.StabnetError("%s: expected a uint8 tensor on the GPU (there is no CPU fallback)" % what)
+    if src_u8.dtype != torch.uint8:
+        raise _lib.StabnetError("%s: expected uint8, got %s" % (what, src_u8.dtype))
+    try:
+        SH, SW = int(size[0]), int(size[1])
+    except (TypeError, ValueError, IndexError):
+        raise _lib.StabnetError("%s: size must be (SH, SW), got %r" % (what, size))
+    if planes not in (1, 3) or SH < 1 or SW < 1 or (planes == 3 and (SH % 2 or SW % 2)):
+        raise _lib.StabnetError("%s: planes must be 1 or 3 and a 4:2:0 frame has even sides, got planes %r, size %dx%d" % (what, planes, SH, SW))
+    flat = src_u8.dim() == 1
+    u8 = src_u8[None] if flat else src_u8
+    need = i420_frame_bytes(SH, SW, planes)
+    if u8.dim() != 2 or u8.stride(1) != 1 or u8.shape[1] < need or (u8.shape[0] > 1 and u8.stride(0) < need):
+        raise _lib.StabnetError("%s: expected [N, >= %d] or [>= %d] dense bytes per frame, got %s" % (what, need, need, list(src_u8.shape)))
+    N, dev = u8.shape[0], u8.device
+    stride = u8.stride(0) if N > 1 else u8.shape[1]
+    win = None if window is None else _check_window(window, what)
+    OH, OW = (SH, SW) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if OH < 1 or OW < 1 or (planes == 3 and (OH % 2 or OW % 2)):
+        raise _lib.StabnetError("%s: out_size %dx%d is empty or odd" % (what, OH, OW))
+    xm, ym, H, W = _check_maps(x_map, y_map, N, dev, rate, what)
+    obytes = i420_frame_bytes(OH, OW, planes)
+    if out is None:
+        out = torch.empty((N, obytes), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or out.numel() != N * obytes or not out.is_contiguous():
+        raise _lib.StabnetError("%s: out must be a contiguous uint8 tensor of %s on %s" % (what, [N, obytes], dev))
+    if black_count is not None and (not isinstance(black_count, torch.Tensor) or black_count.device != dev or black_count.dtype != torch.int32
+                                    or black_count.numel() != N * OH * OW or not black_count.is_contiguous()):
+        raise _lib.StabnetError("%s: black_count must be a contiguous int32 tensor of %s on %s" % (what, [N, OH, OW], dev))
+    n_ws = 2 * N * (H // rate) * (W // rate)
+    if workspace is None:
+        workspace = torch.empty(n_ws, dtype=torch.float32, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.float32 or workspace.numel() < n_ws \
+            or not workspace.is_contiguous():
+        raise _lib.StabnetError("%s: workspace must be a contiguous float32 tensor of >= %d elements on %s" % (what, n_ws, dev))
+    _lib.call("stabnet_warp_rev_bundle2_i420", ptr(u8), N, SH, SW, int(planes), stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW,
+              int(border_y), ptr(out), ptr(black_count), ptr(workspace), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    return out.view(obytes) if flat else out.view(N, obytes)
+
+
 def check_fill_params(r_min=0.5, up=0.002, margin_q=8, SH=None, SW=None):
     """The ranges stabnet_fill_window_update accepts, checked on the host (ValueError): r_min in (0, 1], up finite and >= 0, margin_q an
     integer in 0 .. 16 * min(SH, SW) (the upper end only when the size is given).  -> (float r_min, float up, int margin_q)."""

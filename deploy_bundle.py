@@ -44,6 +44,14 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     distortion value and stability score); <name>_score.json is written and the three numbers are printed.  The stabilised frames
     are the network's grey output, or, with --fill R / adaptive, the window that was written, converted by the ingest stage.  Off by
     default; no other output changes with it.
+  * --y4m-in PATH|- [--y4m-out PATH|-]: a YUV4MPEG2 stream (8-bit 4:2:0 or mono; stabnet_amd/y4m.py) from a file or stdin, frame by
+    frame in bounded memory, to a stream of the same size, chroma tag, frame rate, aspect and range in a file or on stdout:
+      ffmpeg -i in.mp4 -f yuv4mpegpipe - | deploy_bundle.py --y4m-in - --y4m-out - | ffmpeg -i - out.mp4
+    No colour conversion: the network reads the Y plane (range-expanded by the ingest's table when the stream is limited-range), and
+    the frame's three planes are warped as they are in one gather (csrc/remap.hip, stabnet_warp_rev_bundle2_i420; taps outside the
+    frame read black: Y 0 or 16, U = V = 128).  The test list is not read; --fill R is honoured; every message goes to stderr; at the
+    end frames, fps and the luma pixels ever uncovered are reported, and <out>.json is written beside a --y4m-out file.  Without
+    --y4m-out nothing is written but the report.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -124,12 +132,35 @@ def build_parser():
                    help='after a clip, score the kept stabilised frames against the input frames at the network\'s size: cropping ratio, '
                         'distortion value, stability score (stabnet_amd.metrics.score_clip); writes <name>_score.json')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
+    p.add_argument('--y4m-in', default=None, metavar='PATH|-',
+                   help='stabilise a YUV4MPEG2 stream (8-bit 4:2:0 or mono) from this file, or from stdin with -, frame by frame in bounded '
+                        'memory; the planes are warped as they are (stabnet_warp_rev_bundle2_i420); the test list is not read; implies '
+                        '--ingest device --output-size source; every message goes to stderr')
+    p.add_argument('--y4m-out', default=None, metavar='PATH|-',
+                   help='with --y4m-in: write the stabilised stream (the input\'s size, chroma tag, frame rate, aspect and range) to this '
+                        'file, with <PATH>.json beside it, or to stdout with -; without it only the report is printed')
     return p
 
 
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    if args.y4m_out is not None and args.y4m_in is None:
+        p.error('--y4m-out needs --y4m-in: it is the output of the Y4M loop')
+    if args.y4m_in is not None:
+        if args.pipeline:
+            p.error('--y4m-in runs its own serial loop: it is not available with --pipeline')
+        if args.mjpg:
+            p.error('--y4m-in writes a Y4M stream (--y4m-out): it is not available with --mjpg')
+        if args.score:
+            p.error('--y4m-in keeps no frames to score: it is not available with --score')
+        if args.decode == 'device':
+            p.error('--y4m-in reads raw planes, there is nothing to decode: it is not available with --decode device')
+        if args.synthetic:
+            p.error('--y4m-in names the input: it is not available with --synthetic')
+        if args.fill in ('auto', 'adaptive', 'history'):
+            p.error('--y4m-in honours --fill R only: --fill %s is not available in the Y4M loop' % args.fill)
+        args.ingest, args.output_size = 'device', 'source'
     if args.decode == 'device':
         args.ingest = 'device'                                 # the decoded frame lies on the GPU: that is where it is converted
     if args.output_size == 'source' and args.ingest != 'device':
@@ -494,10 +525,110 @@ def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem):
     print('wrote', stem + '_score.json')
 
 
-def main():
-    args = parse_args()
+def run_y4m(args, rd, stream, H, W, dev, out_file):
+    """--y4m-in: the online loop over a Y4M stream of unknown length, in bounded memory -- one pinned and one device buffer per
+    direction, no per-frame list; only the coverage image accumulates.  Per frame: read_into the pinned buffer, one upload, the frame's
+    graph on the Y plane's view of the uploaded buffer (ingest, then the network: stream.step_u8), the planar warp of the uploaded
+    buffer by the frame's maps into the fixed output buffer, one download, Y4mWriter.write.  Frame 0 seeds the ring and is written as
+    read.  rd: the opened y4m.Y4mReader; out_file: '-' given as the process's real stdout, a path, or None (a dry run).  Everything
+    printed goes to stderr.  -> the report that <out>.json holds."""
     import torch
-    from stabnet_amd import synthetic, warp
+    from stabnet_amd import warp, y4m
+    from stabnet_amd.ingest import FrameIngest, lut256_limited
+    say = lambda *a: print(*a, file=sys.stderr)
+    SH, SW = rd.height, rd.width
+    planes = 1 if rd.chroma == 'mono' else 3
+    limited = rd.colour_range == 'limited'
+    border_y = 16 if limited else 0
+    window = warp.ratio_window(SH, SW, args.fill) if args.fill is not None else None
+    say('note: --y4m-in: %dx%d C%s frames at %d:%d fps, %s range; the Y plane feeds the %dx%d network, the planes are warped as they are '
+        '(taps outside the frame read Y = %d, U = V = 128)' % (SW, SH, rd.chroma, rd.fps[0], rd.fps[1], rd.colour_range, W, H, border_y))
+    if window is not None:
+        say('note: --fill %g: every written frame is the window (y0, x0, wh, ww) = %s of the stabilised frame, at %dx%d' % (args.fill, list(window), SW, SH))
+    ing = FrameIngest(SH, SW, 1, H, W, gray=args.gray_weights, device=dev, lut=lut256_limited() if limited else None)
+    pin_in, pin_out = (torch.empty(rd.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(2))
+    dev_in, dev_out = (torch.empty(rd.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(2))
+    host_in, host_out = pin_in.numpy(), pin_out.numpy()
+    y_view = dev_in[:SH * SW].view(SH, SW)
+    ws = torch.empty(2 * (H // 4) * (W // 4), dtype=torch.float32, device=dev)
+    black = torch.zeros((SH, SW), dtype=torch.int32, device=dev)
+    wr = None
+    if out_file is not None:
+        wr = y4m.Y4mWriter(out_file, SW, SH, rd.fps, rd.chroma, aspect=rd.aspect, colour_range=rd.colour_range if rd.range_given else None)
+    length, tot_time = 0, 0.0
+    try:
+        if not rd.read_into(host_in):
+            raise y4m.Y4mError('Y4M: the stream holds no frame')
+        dev_in.copy_(pin_in)
+        stream.start_u8(y_view, ing)                                               # ring = 32 x the first frame
+        torch.cuda.synchronize()
+        alive = wr is None or wr.write(host_in)                                    # the first frame as read (deploy_bundle.py:215)
+        while alive and rd.read_into(host_in):
+            dev_in.copy_(pin_in)
+            torch.cuda.synchronize()
+            start = time.time()
+            r = stream.step_u8(y_view, ing)
+            warp.warpRevBundle2_i420(dev_in, r['x_map'], r['y_map'], (SH, SW), planes, window=window, border_y=border_y, black_count=black,
+                                     out=dev_out, workspace=ws)
+            torch.cuda.synchronize()
+            tot_time += time.time() - start
+            pin_out.copy_(dev_out)
+            torch.cuda.synchronize()
+            alive = wr is None or wr.write(host_out)
+            length += 1
+            if length % 10 == 0:
+                say('length: ' + str(length))
+                say('fps={}'.format(length / tot_time))
+    finally:
+        say('total length={}'.format(length + 2))
+        if wr is not None:
+            wr.close()
+    if wr is not None and wr.broken:
+        say('note: the consumer of --y4m-out closed the stream after %d frames' % wr.frames_written)
+    report = {'input': rd.header_fields(), 'network_size': [H, W], 'colour_range': rd.colour_range, 'border_y': border_y,
+              'window': [float(v) for v in window] if window is not None else None, 'frames': length + 1,
+              'pixels_ever_uncovered': int((black > 0).sum().item()), 'max_uncovered_count': int(black.max().item())}
+    say('y4m: %d frames (the first as read, %d stabilised), fps=%s (the step and the warp), %d of %d luma pixels were uncovered in some frame'
+        % (length + 1, length, length / tot_time if tot_time > 0 else 'n/a', report['pixels_ever_uncovered'], SH * SW))
+    if wr is not None and isinstance(out_file, str):
+        import json
+        with open(out_file + '.json', 'w') as f:
+            json.dump(report, f, indent=1)
+            f.write('\n')
+        say('wrote %s (%d frames) and %s' % (out_file, wr.frames_written, out_file + '.json'))
+    return report
+
+
+def main_y4m(args):
+    """--y4m-in: stdout may be the video, so everything the driver prints goes to stderr; a stream that is refused (y4m.Y4mError) ends
+    the run with its sentence and a non-zero status, before anything touches the GPU when the header is what is refused."""
+    import contextlib
+    from stabnet_amd import y4m
+    real_stdout = sys.stdout.buffer
+    with contextlib.redirect_stdout(sys.stderr):
+        try:
+            rd = y4m.Y4mReader(args.y4m_in)
+        except (y4m.Y4mError, OSError) as e:
+            sys.exit('deploy_bundle.py: --y4m-in %s: %s' % (args.y4m_in, e))
+        import torch
+        stream, H, W, dev = setup_stream(args)
+        try:
+            run_y4m(args, rd, stream, H, W, dev, real_stdout if args.y4m_out == '-' else args.y4m_out)
+        except (y4m.Y4mError, OSError) as e:
+            sys.exit('deploy_bundle.py: --y4m-in %s: %s' % (args.y4m_in, e))
+        finally:
+            rd.close()
+            torch.cuda.synchronize()
+    if args.y4m_out == '-':
+        try:
+            real_stdout.flush()
+        except BrokenPipeError:
+            os.dup2(os.open(os.devnull, os.O_WRONLY), sys.stdout.fileno())          # nothing more to say to a closed pipe, at exit either
+
+
+def setup_stream(args):
+    """The network of a run from the flags: the size, the weights, the stream with its frame graph.  -> (stream, H, W, device)"""
+    import torch
     from stabnet_amd.config import Config
     from stabnet_amd.deploy import StabNetStream
 
@@ -524,6 +655,16 @@ def main():
     stream = StabNetStream(params, H, W, cfg, streams=1, device=dev, refine=args.refine, before_ch=args.before_ch,
                            use_graph=True, operand_mode=args.operand_mode)   # one frame = fixed-argument launches: captured once, replayed per frame
     stream.track_black()            # all_black += round(black) inside every refine pass (deploy_bundle.py:234,291), on the device
+    return stream, H, W, dev
+
+
+def main():
+    args = parse_args()
+    if args.y4m_in is not None:
+        return main_y4m(args)
+    import torch
+    from stabnet_amd import synthetic, warp
+    stream, H, W, dev = setup_stream(args)
 
     clips, fps_of = [], {}
     if args.synthetic > 0:

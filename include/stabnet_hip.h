@@ -604,6 +604,29 @@ int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, in
                                      unsigned char* out, int* black_count, float* workspace,
                                      float* px_out, float* py_out, void* stream, void* prof);
 
+/* stabnet_warp_rev_bundle2_win of a planar YUV 4:2:0 frame as a Y4M stream carries it (remap_i420_kernel): no colour conversion, every
+ * plane warped as the single-channel image it is, all planes of all frames in one gather launch after the shrink.
+ * src: N frames frame_stride_bytes apart; each the Y plane [SH,SW] and, with planes == 3, U [SH/2,SW/2] and V [SH/2,SW/2] behind it,
+ * all dense (planes == 1: Y only).  Any base alignment; nothing outside a frame's own SH*SW*3/2 (SH*SW) bytes is read.  out: the same
+ * layout at OH x OW, dense.  window: {y0, x0, wh, ww} in HOST memory, pixel-edge units of the stabilised LUMA frame, as _win takes it,
+ * or NULL: the whole frame, and then OH, OW must equal SH, SW.
+ * Each plane is what _win gives that plane as a C == 1 image of its own size: Y at (SH,SW) -> (OH,OW) through `window`, a chroma plane
+ * at (SH/2,SW/2) -> (OH/2,OW/2) through {y0/2, x0/2, wh/2, ww/2}, with the plane's own constants sx = float32((SW/2)/W),
+ * cx = float32(0.5*(SW/2)/W - 0.5) (centred chroma siting: the luma coordinate of the chroma sample, halved).  One difference: a tap
+ * outside the plane reads a border value instead of 0 (cv2.remap's borderValue): border_y (0..255) for Y, 128 for U and V.  The 1/32-px
+ * rounding, the 15-bit weights with the (0, 0) repair and (sum + 16384) >> 15 are unchanged.  black_count (optional, int32 [N,OH,OW]):
+ * += 1 at the LUMA output pixel under _src's rule.  workspace: 2*N*(H/rate)*(W/rate) floats.
+ * One workgroup per output row segment of one plane; a plane whose output width is a multiple of 4 and whose output rows are 4-byte
+ * aligned takes four pixels per thread and one dword store, any other one pixel per thread with byte traffic (STABNET_REMAP_VEC4=0:
+ * every plane); the bits are the same.  Nothing allocates, synchronises or copies: the call can be captured in a hipGraph.
+ * Refused before any launch: null src, out, maps or workspace; planes not 1 or 3; odd SH, SW, OH or OW with planes == 3; sizes outside
+ * 1..32767; frame_stride_bytes below the frame's size; border_y outside 0..255; rate < 1 or H/rate or W/rate == 0; a null window with
+ * OH, OW != SH, SW; a window _win would refuse. */
+int stabnet_warp_rev_bundle2_i420(const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes,
+                                  const float* x_map, const float* y_map, int H, int W, int rate,
+                                  const double* window, int OH, int OW, int border_y,
+                                  unsigned char* out, int* black_count, float* workspace, void* stream, void* prof);
+
 /* Adaptive borderless output: per stream, the largest centred window of the stabilised frame that is provably free of uncovered
  * pixels, rate-limited on the way back out (fill_window_kernel).  x_map, y_map [N,H,W] as the remap receives them; h = H / rate,
  * w = W / rate.  Node (a, b) of the h x w small maps is BAD when its own coordinate (the remap's arithmetic with all the weight on the
