@@ -39,10 +39,12 @@ def get_4_pts(theta, cfg):
     """s_net_bundle_nobm.py:29-71 -> pts1 [N,gh,gw,8], pts2 [N,gh+1,gw+1,2]."""
     N = theta.shape[0]
     gh, gw = cfg.grid_h, cfg.grid_w
-    lim = 1.0 / float(np.float32(cfg.do_crop_rate))
+    # the limit is a float32 value of the reference's graph (1 / 0.8 rounds to 1.25 there), and tf.clip_by_value passes the whole
+    # gradient to a vertex that sits exactly on it: torch.clamp does the same, torch.minimum / maximum would halve it at the tie
+    lim = float(np.float32(1.0) / np.float32(cfg.do_crop_rate))
     base = torch.tensor([[[j * (2.0 / gw) - 1, i * (2.0 / gh) - 1] for j in range(gw + 1)] for i in range(gh + 1)], dtype=DT)
     pts2 = base[None] + theta.reshape(N, gh + 1, gw + 1, 2)
-    pts2 = torch.minimum(torch.maximum(pts2, torch.tensor(-lim, dtype=DT)), torch.tensor(lim, dtype=DT))
+    pts2 = torch.clamp(pts2, -lim, lim)
     tl, tr, bl, br = pts2[:, :-1, :-1], pts2[:, :-1, 1:], pts2[:, 1:, :-1], pts2[:, 1:, 1:]
     pts1 = torch.stack([tl, tr, bl, br], dim=-1).reshape(N, gh, gw, 8)
     return pts1, pts2
@@ -71,7 +73,10 @@ def get_Hs(pts2, cfg):
             A6v, A7v = -sx[None] * v, -sy[None] * v
             A = torch.cat([A[:, :, :6], torch.cat([A6u, A6v], dim=1)[:, :, None], torch.cat([A7u, A7v], dim=1)[:, :, None]], dim=2)
             b = torch.cat([u, v], dim=1)[:, :, None]
-            hvec = torch.linalg.solve(A + ridge[None], b)[:, :, 0]
+            # the reference inverts, then multiplies (tf.matrix_inverse, tf.matmul: spatial_transformer3.py:145,173; get_H of
+            # stabnet_oracle.py).  In float64 that equals a solve to 1e-13; evaluated in float32 (DT switched by a test that wants
+            # the float32 rounding of this graph) it is NOT backward stable as a solve is, and the adjoint amplifies the difference
+            hvec = (torch.linalg.inv(A + ridge[None]) @ b)[:, :, 0]
             out.append(torch.cat([hvec, torch.ones(N, 1, dtype=DT)], dim=1))
     return torch.stack(out, dim=1).reshape(N, gh, gw, 9)
 
@@ -130,8 +135,8 @@ def transformer(U, pts2, cfg, corners=None, black=None, record=None):
     N, H, W, C = U.shape
     gh, gw = cfg.grid_h, cfg.grid_w
     Hs = get_Hs(pts2, cfg)
-    xs = torch.tensor(O.linspace_tf(-1.0, 1.0, W).astype(np.float64))
-    ys = torch.tensor(O.linspace_tf(-1.0, 1.0, H).astype(np.float64))
+    xs = torch.tensor(O.linspace_tf(-1.0, 1.0, W), dtype=DT)
+    ys = torch.tensor(O.linspace_tf(-1.0, 1.0, H), dtype=DT)
     rows, cols = O.cell_bounds(H, W, gh, gw)
     xrows = []
     yrows = []
@@ -173,7 +178,7 @@ def interpolate(im, x, y, corners=None):
 
 # ---- losses ------------------------------------------------------------------------------------------------
 def get_black_pos(pts1, cfg):
-    lim = 1.0 / float(np.float32(cfg.do_crop_rate))
+    lim = float(np.float32(1.0) / np.float32(cfg.do_crop_rate))       # the float32 limit of get_4_pts
     z = torch.zeros((), dtype=DT)
     e = torch.where(pts1 > lim, pts1 - lim, z) + torch.where(-lim > pts1, -lim - pts1, z)
     return e.reshape(pts1.shape[0], -1)
