@@ -24,7 +24,7 @@ class StabnetError(RuntimeError):
 
 _CTYPE = {
     "int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "long": ctypes.c_long,
-    "int64_t": ctypes.c_int64, "double": ctypes.c_double,
+    "int64_t": ctypes.c_int64, "double": ctypes.c_double, "unsigned": ctypes.c_uint,
 }
 
 

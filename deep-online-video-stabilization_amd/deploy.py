@@ -131,6 +131,7 @@ class StabNetStream:
         self._graph_u8 = None                             # step_u8's frame graph: ingest launches + the frame
         self.cur_u8 = None                                # fixed-address uint8 staging buffer of the raw frame (step_u8)
         self._ingest = None
+        self.scene = None                                 # optional scene.SceneCut: detect cuts and re-seed the ring inside the frame
         self.started = False
 
     @property
@@ -145,6 +146,9 @@ class StabNetStream:
         self.head_dev.zero_()
         if self.all_black is not None:
             self.all_black.zero_()
+        if self.scene is not None:
+            self.scene.reset()
+            self.scene.update(first)                      # seen == 0: no flag; the next frame is compared with this one
         self.started = True
 
     def track_black(self, enable: bool = True):
@@ -153,10 +157,35 @@ class StabNetStream:
         self._graph = self._graph_u8 = None
         return self.all_black
 
+    def enable_scene_cut(self, threshold: float = 0.35, min_gap: int = 8):
+        """Detect scene cuts on the device and re-seed the ring inside the frame (scene.SceneCut, csrc/scene.hip): in front of every
+        frame, stabnet_scene_update compares the incoming frame's tile histograms with the previous frame's, and
+        stabnet_ring_reseed_if turns the ring of a flagged stream into 32 x that frame with zero masks; the frame is then stabilised
+        like any other, so the run from a cut on equals a fresh run that starts there with its first frame doubled.  step() then also
+        returns "scene_cut" (int32 [S]) and "scene_dist" (uint32 [S], D; d = D / (2*H*W)), device tensors.  all_black is not zeroed
+        at a cut.  threshold in (0, 1], min_gap >= 0 frames since the last cut (or the start); reset by start()."""
+        from .scene import SceneCut
+        self.scene = SceneCut(self.S, self.H, self.W, threshold, min_gap, device=self.reg.device)
+        self._graph = self._graph_u8 = None
+        return self.scene
+
+    def _outputs(self):
+        out = {"output": self.out_img, "black_pix": self.black, "Hs": self.Hs, "x_map": self.x_map,
+               "y_map": self.y_map, "theta": self.theta, "frame": self.frame_fb}
+        if self.scene is not None:
+            out["scene_cut"], out["scene_dist"] = self.scene.flag, self.scene.dist
+        return out
+
     def _enqueue(self, prof=None, cur=None):
         """One frame on the current stream.  cur: the frame to read instead of the fixed staging buffer self.cur (ClipPipeline hands
         its upload slot over directly)."""
         r = self.reg
+        if self.scene is not None:
+            # the cut decision and the predicated reseed read the frame stabnet_deploy_frame is about to read
+            frame = ptr(self.cur if cur is None else cur)
+            self.scene.enqueue(frame)
+            _lib.call("stabnet_ring_reseed_if", ptr(self.frames_ring), ptr(self.masks_ring), frame, self.S, self.depth, self.H, self.W,
+                      ptr(self.scene.flag), stream_ptr(r.device), device=r.device)
         _lib.call("stabnet_deploy_frame", r.plan.handle, ptr(r.params), ptr(r.fold), ptr(self.frames_ring),
                   ptr(self.masks_ring), self.depth, ptr(self.head_dev), self._lags_c, len(self.lags), ptr(self.cur if cur is None else cur),
                   self.refine, self.cfg.grid_h, self.cfg.grid_w, self.cfg.do_crop_rate, ptr(self.theta), ptr(self.out_img),
@@ -187,8 +216,7 @@ class StabNetStream:
                 self._graph.replay()
         else:
             self._enqueue(prof)
-        return {"output": self.out_img, "black_pix": self.black, "Hs": self.Hs, "x_map": self.x_map,
-                "y_map": self.y_map, "theta": self.theta, "frame": self.frame_fb}
+        return self._outputs()
 
     def _bind_ingest(self, ingest):
         if (ingest.H, ingest.W) != (self.H, self.W) or ingest.device != self.reg.device:
@@ -242,8 +270,7 @@ class StabNetStream:
                 self._graph_u8.replay()
         else:
             self._enqueue_u8(prof)
-        return {"output": self.out_img, "black_pix": self.black, "Hs": self.Hs, "x_map": self.x_map,
-                "y_map": self.y_map, "theta": self.theta, "frame": self.frame_fb}
+        return self._outputs()
 
 
 class ClipPipeline:
@@ -296,7 +323,11 @@ class ClipPipeline:
     decoder=mjpeg.MjpegDecoder (needs ingest): the clip is a Motion-JPEG one -- run(clip, ...) with clip.jpeg(t) the compressed frame
     (mjpeg.DeviceClip).  A slot then uploads the compressed bytes and their parsed description in one copy on the upload stream, and
     the slot's frame graph starts with the decode launches (csrc/mjpeg_decode.hip) into the buffer the ingest reads.  The frame's
-    status word comes down with its outputs; a frame that does not decode raises StabnetError naming it."""
+    status word comes down with its outputs; a frame that does not decode raises StabnetError naming it.
+
+    A stream with enable_scene_cut(): the detector's launches and the predicated reseed come with stream._enqueue inside every slot's
+    graph, its state advancing in frame order on the run stream; the frame's 8 bytes {flag, D} are copied into the slot inside the
+    graph and downloaded with the slot's other outputs: the result carries "scene_cut" (0 / 1) and "scene_dist" (D; d = D / (2*H*W))."""
 
     def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
                  output: str = "network", window=None, fill=None, decoder=None):
@@ -402,6 +433,7 @@ class ClipPipeline:
             self.h_jpeg = [pin((mb,), torch.uint8) for _ in range(slots)]
             self.h_jlen = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(slots)]
         self.h_maps = None
+        self.h_scene = None                                   # per slot {flag, D} of a stream with enable_scene_cut(): made by run()
         self.use_graph = True
         self._graphs = {}
         self.s_in, self.s_run, self.s_out = (torch.cuda.Stream(device=dev) for _ in range(3))
@@ -423,6 +455,8 @@ class ClipPipeline:
             st._enqueue()
         else:
             st._enqueue(cur=self.d_grey[k])                  # the frame reads the upload slot itself: no staging copy
+        if st.scene is not None:
+            self.d_scene[k].copy_(st.scene.out)              # this frame's {flag, D}: the next frame overwrites the detector's own
         # cvt_train2img (deploy_bundle.py:75)
         _lib.call("stabnet_cvt_train2img", ptr(st.out_img), ptr(self.d_out[k]), H * W, stream_ptr(self.dev), device=self.dev)
         if self.windowed:
@@ -491,6 +525,8 @@ class ClipPipeline:
         if self.adaptive:
             r["window"] = self.h_fill[slot][:32].view(torch.float64).numpy()
             r["fill_stats"] = self.h_fill[slot][32:].view(torch.int32).numpy()
+        if self.st.scene is not None:
+            r["scene_cut"], r["scene_dist"] = int(self.h_scene[slot][0]), int(self.h_scene[slot][1]) & 0xffffffff
         return r
 
     def run(self, grey, bgr=None, sink=None, maps: bool = False, raw: bool = True):
@@ -505,6 +541,9 @@ class ClipPipeline:
                                 for dt in (torch.float32, torch.float32, torch.uint8))
             self.d_maps = tuple([torch.empty((H, W), dtype=dt, device=self.dev) for _ in range(K)]
                                 for dt in (torch.float32, torch.float32, torch.uint8))
+        if st.scene is not None and self.h_scene is None:
+            self.h_scene = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(K)]
+            self.d_scene = [torch.zeros(2, dtype=torch.int32, device=self.dev) for _ in range(K)]
         results = []
         emit = sink if sink is not None else (lambda r: results.append({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in r.items()}))
         n = len(grey)
@@ -555,7 +594,7 @@ class ClipPipeline:
                 self.ev_up[k].record(self.s_in)
             with torch.cuda.stream(self.s_run):
                 self.s_run.wait_event(self.ev_up[k])
-                key = (k, maps, ptr(st.all_black))
+                key = (k, maps, ptr(st.all_black)) if st.scene is None else (k, maps, ptr(st.all_black), ptr(st.scene.out))
                 g = self._graphs.get(key)
                 if g is not None:
                     g.replay()
@@ -582,6 +621,8 @@ class ClipPipeline:
                     self.h_jstat[k].copy_(self.d_jstat[k], non_blocking=True)
                 if self.adaptive:
                     self.h_fill[k].copy_(self.d_fill[k], non_blocking=True)
+                if st.scene is not None:
+                    self.h_scene[k].copy_(self.d_scene[k], non_blocking=True)
                 self.ev_down[k].record(self.s_out)
             pending[k] = t                                    # (the slot's next upload follows the host's wait on ev_down[k])
         order = sorted((p, k) for k, p in enumerate(pending) if p is not None)

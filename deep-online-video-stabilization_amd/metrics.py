@@ -15,6 +15,7 @@ them back once; everything after that is host float64:
                |t| = sqrt(P02^2 + P12^2) and theta = atan2(P10, P00), T values each; p = |fft(series)|^2 [1 : T//2]; the share
                sum(p[:5]) / sum(p) (1 when sum(p) is 0); the clip's value is the smaller of the two shares.  T >= 14.
   failed pair  a pair without a model (status 0) is left out of cropping and distortion and is the identity in the path.
+  scene cut    with cuts=[c, ...] the stable pair (c - 1, c) joins two scenes: it is the identity in the path like a failed pair.
 
 Grey of a uint8 BGR frame: (0.114*B + 0.587*G) + 0.299*R in float32 (torch arithmetic: plumbing); a uint8 grey frame is its values."""
 from __future__ import annotations
@@ -139,10 +140,25 @@ def spectrum_share(series) -> float:
     return 1.0 if tot == 0.0 else float(p[:5].sum()) / tot
 
 
-def host_metrics(H_us, status_us, H_ss, status_ss, H: int, W: int, per_frame: bool = False) -> dict:
-    """The three numbers from the homographies unstable -> stable [T,9] and stable t -> t + 1 [T-1,9] with their statuses."""
+def cut_pairs(cuts, T: int):
+    """The stable pairs (c - 1, c) that the scene cuts `cuts` (frame indices of the scored clip) break, as sorted pair indices c - 1.  A cut
+    at frame 0 has no pair in front of it; one outside 0..T-1 is an error."""
+    pairs = set()
+    for c in cuts:
+        if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < T:
+            raise StabnetError("metrics: scene cut %r is no frame of a clip of %d frames" % (c, T))
+        if int(c) >= 1:
+            pairs.add(int(c) - 1)
+    return sorted(pairs)
+
+
+def host_metrics(H_us, status_us, H_ss, status_ss, H: int, W: int, per_frame: bool = False, cuts=None) -> dict:
+    """The three numbers from the homographies unstable -> stable [T,9] and stable t -> t + 1 [T-1,9] with their statuses.
+    cuts (optional): frames of the clip at which a new scene starts; the stable pair (c - 1, c) of each joins two scenes and is treated
+    as a failed pair -- the identity in the path -- and counted under "scene_cuts" (present only when cuts is given)."""
     H_us, H_ss = np.asarray(H_us, np.float64).reshape(-1, 9), np.asarray(H_ss, np.float64).reshape(-1, 9)
     T = len(H_us)
+    broken = cut_pairs(cuts, T) if cuts is not None else []
     if T < MIN_FRAMES:
         raise StabnetError("metrics.score_clip: a clip of %d frames is too short to score: the stability spectrum needs %d or more" % (T, MIN_FRAMES))
     if len(H_ss) != T - 1 or len(status_us) != T or len(status_ss) != T - 1:
@@ -156,8 +172,8 @@ def host_metrics(H_us, status_us, H_ss, status_ss, H: int, W: int, per_frame: bo
             dist.append(frame_distortion(P))
     path = np.eye(3)
     tr, th = [0.0], [0.0]
-    for h, s in zip(H_ss, status_ss):
-        if int(s) != 0:
+    for i, (h, s) in enumerate(zip(H_ss, status_ss)):
+        if int(s) != 0 and i not in broken:
             path = path @ pixel_homography(h, H, W)
         path = path / path[2, 2]
         tr.append(math.hypot(path[0, 2], path[1, 2]))
@@ -167,18 +183,21 @@ def host_metrics(H_us, status_us, H_ss, status_ss, H: int, W: int, per_frame: bo
            "stability": min(s_t, s_r), "stability_translation": s_t, "stability_rotation": s_r, "frames": T,
            "failed_pairs_unstable_stable": int(sum(1 for s in status_us if int(s) == 0)),
            "failed_pairs_stable_stable": int(sum(1 for s in status_ss if int(s) == 0))}
+    if cuts is not None:
+        out["scene_cuts"] = len(broken)
     if per_frame:
         out.update(cropping_per_frame=crop, distortion_per_frame=dist, path_translation=tr, path_rotation=th)
     return out
 
 
 def score_clip(unstable, stable, klt: features.KltParams = None, fit: HomfitParams = None, chunk: int = 64, per_frame: bool = False,
-               homographies: bool = False, prof=None) -> dict:
+               homographies: bool = False, prof=None, cuts=None) -> dict:
     """unstable, stable: device tensors of the same T x H x W -- float32 [T,H,W] on the 0..255 scale, uint8 [T,H,W], or uint8 BGR
     [T,H,W,3] (see grey()).  Two batched solves (unstable t -> stable t for every t; stable t -> stable t + 1), one readback of the
     homographies, their statuses and inlier counts, then host float64.  -> a dict: cropping, distortion, stability (each in (0, 1]
     for a sane clip), stability_translation, stability_rotation, frames, failed_pairs_*, mean_inliers, the parameters; the per-frame
-    lists with per_frame=True; the homographies read back (H_us, status_us, H_ss, status_ss as lists) with homographies=True."""
+    lists with per_frame=True; the homographies read back (H_us, status_us, H_ss, status_ss as lists) with homographies=True.
+    cuts: see host_metrics (frames of THESE clips at which a new scene starts; "scene_cuts" in the result)."""
     klt, fit = klt or features.KltParams(), fit or HomfitParams()
     u, s = grey(unstable), grey(stable)
     if u.shape != s.shape or u.device != s.device:
@@ -194,7 +213,7 @@ def score_clip(unstable, stable, klt: features.KltParams = None, fit: HomfitPara
     H_us, H_ss = back[:a].reshape(T, 9), back[a:b].reshape(T - 1, 9)
     st_us, st_ss = back[b:b + T].astype(np.int32), back[b + T:b + 2 * T - 1].astype(np.int32)
     inl = back[b + 2 * T - 1:]
-    out = host_metrics(H_us, st_us, H_ss, st_ss, H, W, per_frame)
+    out = host_metrics(H_us, st_us, H_ss, st_ss, H, W, per_frame, cuts=cuts)
     out["mean_inliers"] = float(inl.mean())
     out["size"] = [H, W]
     out["params"] = {"klt": dataclasses.asdict(klt), "fit": dataclasses.asdict(fit)}

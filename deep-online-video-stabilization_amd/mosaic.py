@@ -126,13 +126,14 @@ class Mosaic:
         self.cur = 0                                            # canvas[cur], age[cur]: the last frame's
         self.reset()
 
-    def reset(self):
-        """Empty canvases (every age 255); the next frame has no model (status 0) and is not tracked."""
+    def reset(self, keep_log: bool = False):
+        """Empty canvases (every age 255); the next frame has no model (status 0) and is not tracked.  keep_log (a scene cut inside a
+        clip): the per-frame log goes on where it is."""
         for a in self.age:
             a.fill_(255)
         for c in self.canvas:
             c.zero_()
-        self.frames, self._have_prev = 0, False
+        self.frames, self._have_prev = (self.frames if keep_log else 0), False
 
     def _check(self, t, dtype, shape, what):
         if not isinstance(t, torch.Tensor) or t.device != self.dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():

@@ -52,6 +52,13 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     frame read black: Y 0 or 16, U = V = 128).  The test list is not read; --fill R is honoured; every message goes to stderr; at the
     end frames, fps and the luma pixels ever uncovered are reported, and <out>.json is written beside a --y4m-out file.  Without
     --y4m-out nothing is written but the report.
+  * --scene-cut [T] [--scene-gap 8]: scene cuts.  The loop is recurrent -- every frame is regressed against 32 earlier stabilised frames
+    -- so after a cut the network would warp the new scene against the old one.  With the flag, the frame's graph starts with a cut
+    decision on the GPU (csrc/scene.hip: the distance d between the 4 x 4 x 32 tile histograms of consecutive grey frames, a cut when
+    d > T, default 0.35, and at least --scene-gap frames after the last one) and a ring reseed predicated on it: the run from a cut on
+    equals a fresh run that starts there.  Works in the serial loop, with --pipeline and with --y4m-in; <name>_scenes.json holds the
+    cuts and d per frame, the Y4M report scene_cuts; --fill history empties its canvas at a cut and --score leaves the pair across a
+    cut out of the stability path.  Off by default; without it nothing differs.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -131,6 +138,12 @@ def build_parser():
     p.add_argument('--score', action='store_true',
                    help='after a clip, score the kept stabilised frames against the input frames at the network\'s size: cropping ratio, '
                         'distortion value, stability score (stabnet_amd.metrics.score_clip); writes <name>_score.json')
+    p.add_argument('--scene-cut', nargs='?', type=float, const=0.35, default=None, metavar='T',
+                   help='detect scene cuts on the GPU inside the frame (stabnet_scene_update: the distance d in [0, 1] between the tile '
+                        'histograms of consecutive grey frames; a cut is d > T, default 0.35, T in (0, 1]) and re-seed the history ring '
+                        'with the first frame of the new scene (stabnet_ring_reseed_if); writes <name>_scenes.json')
+    p.add_argument('--scene-gap', type=int, default=None, metavar='N',
+                   help='--scene-cut: no cut is flagged within N frames of the last one or of the start, N >= 0 (default 8)')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     p.add_argument('--y4m-in', default=None, metavar='PATH|-',
                    help='stabilise a YUV4MPEG2 stream (8-bit 4:2:0 or mono) from this file, or from stdin with -, frame by frame in bounded '
@@ -161,6 +174,14 @@ def parse_args(argv=None):
         if args.fill in ('auto', 'adaptive', 'history'):
             p.error('--y4m-in honours --fill R only: --fill %s is not available in the Y4M loop' % args.fill)
         args.ingest, args.output_size = 'device', 'source'
+    if args.scene_cut is None and args.scene_gap is not None:
+        p.error('--scene-gap belongs to --scene-cut')
+    if args.scene_cut is not None:
+        args.scene_gap = 8 if args.scene_gap is None else args.scene_gap
+        if not 0.0 < args.scene_cut <= 1.0:                    # (a NaN fails both comparisons)
+            p.error('--scene-cut needs 0 < T <= 1, got %r' % (args.scene_cut,))
+        if args.scene_gap < 0:
+            p.error('--scene-gap needs N >= 0, got %r' % (args.scene_gap,))
     if args.decode == 'device':
         args.ingest = 'device'                                 # the decoded frame lies on the GPU: that is where it is converted
     if args.output_size == 'source' and args.ingest != 'device':
@@ -251,8 +272,28 @@ def jpeg_options(args):
     return dict(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
 
 
+def scene_note(scene_log, t, cut, D, H, W, say=print):
+    """--scene-cut: frame t's flag and D (host ints) into scene_log as (t, cut, d = D / (2*H*W)); a cut is said.  -> cut"""
+    d = int(D) / (2.0 * H * W)
+    scene_log.append((int(t), int(cut), d))
+    if cut:
+        say('scene cut at frame %d (d = %.2f)' % (t, d))
+    return bool(cut)
+
+
+def write_scenes_json(path, args, scene_log, say=print):
+    """<name>_scenes.json: the threshold, the gap, the frames of the clip at which a new scene starts and d of every frame (0 for the
+    first, which has nothing to differ from)."""
+    import json
+    with open(path, 'w') as f:
+        json.dump({'threshold': args.scene_cut, 'gap': args.scene_gap, 'cuts': [t for t, cut, _ in scene_log if cut],
+                   'd': [0.0] + [d for _, _, d in scene_log]}, f, indent=1)
+        f.write('\n')
+    say('wrote', path)
+
+
 def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None,
-               window=None, black_win=None, adaptive=None, fill_log=None, mosaic=None, fill_frames=None):
+               window=None, black_win=None, adaptive=None, fill_log=None, mosaic=None, fill_frames=None, scene_log=None):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
     uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
@@ -260,7 +301,9 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     the stabilised frame at the kept frame's size, its coverage counted at the output pixels.  adaptive (--fill adaptive; a
     warp.AdaptiveFill): the window is the one the GPU chooses for the frame; fill_log gets (window, stats) per frame.  mosaic (--fill
     history; a mosaic.Mosaic): the kept colour frame is remapped with its coordinates written out, composed over the canvas of the
-    earlier frames, and the canvas goes to fill_frames; every other output is the one of a run without it."""
+    earlier frames, and the canvas goes to fill_frames; every other output is the one of a run without it.  scene_log (--scene-cut; the
+    stream has enable_scene_cut()): gets (frame, cut, d) per frame from the step's device flag, read outside the timed part; at a cut the
+    mosaic's canvas is emptied before the frame is composed."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
@@ -282,6 +325,9 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
         r = stream.step_u8(cur, ing) if ing is not None else stream.step(cur)     # one sess.run-equivalent
         torch.cuda.synchronize()
         tot_time += time.time() - start
+        if scene_log is not None:
+            if scene_note(scene_log, t, int(r['scene_cut'][0]), int(r['scene_dist'].cpu().numpy()[0]), H, W) and mosaic is not None:
+                mosaic.reset(keep_log=True)                                       # the earlier frames show another scene
         if window is not None or adaptive is not None:
             # the window of the stabilised frame in the one gather: of the frame as read, or of the cv2-resized colour frame
             frame = cur if black_src is not None else ing.colour(cur)[0]
@@ -323,10 +369,11 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
 
 
 def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False,
-                  window=None, fill=None, fill_log=None):
+                  window=None, fill=None, fill_log=None, scene_log=None):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included.
     window='adaptive' with fill=dict(r_min, up, margin_q): the per-frame window of --fill adaptive; fill_log gets (window, stats).
+    scene_log (--scene-cut): gets (frame, cut, d) per frame.
     -> (frames, seconds, coverage at source size or None, coverage at the output pixels of the window or None)."""
     from stabnet_amd.deploy import ClipPipeline
     colour = ing.C == 3 if ing is not None else is_colour(clip[0], H, W)
@@ -347,6 +394,8 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
         xmaps.append(r['x_map'].copy()); ymaps.append(r['y_map'].copy()); blacks.append(r['black'].copy())
         if 'window' in r:
             fill_log.append((r['window'].copy(), r['fill_stats'].copy()))
+        if 'scene_cut' in r:                                                  # --scene-cut: downloaded with the slot's other outputs
+            scene_note(scene_log, r['t'], r['scene_cut'], r['scene_dist'], H, W)
         if len(frames_out) % 10 == 0:
             print('length: ' + str(len(frames_out)))
 
@@ -490,9 +539,10 @@ def fill_second_pass(clip, ing, source, xmaps, ymaps, window, out_size, dev, ste
     return per
 
 
-def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem):
+def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem, cuts=None):
     """--score: frames 1.. of the clip as ingested (the network's grey input on the 0..255 scale) against the kept frames of the same
-    instants: the network's grey output, or (filled) the window that was written, brought to the network's size by the ingest stage."""
+    instants: the network's grey output, or (filled) the window that was written, brought to the network's size by the ingest stage.
+    cuts (--scene-cut): the frames of the CLIP at which a new scene starts; kept frame k is the clip's frame k + 1."""
     import json
     import torch
     from stabnet_amd import metrics
@@ -515,7 +565,7 @@ def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem):
     else:
         stable = torch.from_numpy(np.stack(frames_out)).to(dev)
         what = 'the network\'s grey output'
-    res = metrics.score_clip(unstable, stable)
+    res = metrics.score_clip(unstable, stable, cuts=None if cuts is None else [c - 1 for c in cuts if c - 1 < n])
     res['stable_frames'] = what
     with open(stem + '_score.json', 'w') as f:
         json.dump(res, f, indent=1)
@@ -556,6 +606,7 @@ def run_y4m(args, rd, stream, H, W, dev, out_file):
     if out_file is not None:
         wr = y4m.Y4mWriter(out_file, SW, SH, rd.fps, rd.chroma, aspect=rd.aspect, colour_range=rd.colour_range if rd.range_given else None)
     length, tot_time = 0, 0.0
+    scene_cuts = [] if args.scene_cut is not None else None                        # --scene-cut: the flagged frames (no per-frame list here)
     try:
         if not rd.read_into(host_in):
             raise y4m.Y4mError('Y4M: the stream holds no frame')
@@ -572,6 +623,8 @@ def run_y4m(args, rd, stream, H, W, dev, out_file):
                                      out=dev_out, workspace=ws)
             torch.cuda.synchronize()
             tot_time += time.time() - start
+            if scene_cuts is not None and int(r['scene_cut'][0]):
+                scene_note(scene_cuts, length + 1, 1, int(r['scene_dist'].cpu().numpy()[0]), H, W, say)
             pin_out.copy_(dev_out)
             torch.cuda.synchronize()
             alive = wr is None or wr.write(host_out)
@@ -588,6 +641,8 @@ def run_y4m(args, rd, stream, H, W, dev, out_file):
     report = {'input': rd.header_fields(), 'network_size': [H, W], 'colour_range': rd.colour_range, 'border_y': border_y,
               'window': [float(v) for v in window] if window is not None else None, 'frames': length + 1,
               'pixels_ever_uncovered': int((black > 0).sum().item()), 'max_uncovered_count': int(black.max().item())}
+    if scene_cuts is not None:
+        report.update(scene_cuts=[t for t, _, _ in scene_cuts], scene_threshold=args.scene_cut)
     say('y4m: %d frames (the first as read, %d stabilised), fps=%s (the step and the warp), %d of %d luma pixels were uncovered in some frame'
         % (length + 1, length, length / tot_time if tot_time > 0 else 'n/a', report['pixels_ever_uncovered'], SH * SW))
     if wr is not None and isinstance(out_file, str):
@@ -655,6 +710,10 @@ def setup_stream(args):
     stream = StabNetStream(params, H, W, cfg, streams=1, device=dev, refine=args.refine, before_ch=args.before_ch,
                            use_graph=True, operand_mode=args.operand_mode)   # one frame = fixed-argument launches: captured once, replayed per frame
     stream.track_black()            # all_black += round(black) inside every refine pass (deploy_bundle.py:234,291), on the device
+    if args.scene_cut is not None:
+        stream.enable_scene_cut(args.scene_cut, args.scene_gap)
+        print('note: --scene-cut %g: a frame whose tile histograms differ from the previous frame\'s by d > %g, %d frames or more after the '
+              'last cut, starts a new scene: the history ring is re-seeded with it on the GPU' % (args.scene_cut, args.scene_cut, args.scene_gap))
     return stream, H, W, dev
 
 
@@ -718,6 +777,7 @@ def main():
         fill, kept = None, (H, W)            # --fill as it applies to this clip; the kept frame's size
         adaptive, fill_params, fill_log = None, None, []     # --fill adaptive: the window's state on the device; (window, stats) per frame
         mosaic, fill_frames = None, []       # --fill history: the canvas of the earlier frames on the device; the filled frames
+        scene_log = [] if args.scene_cut is not None else None      # --scene-cut: (frame, cut, d) per frame
         try:
             if args.ingest == 'device':
                 shp = np.shape(clip[0])
@@ -785,12 +845,12 @@ def main():
             if args.pipeline:
                 length, tot_time, pipe_black, pipe_win = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
                                                                        jpeg_options(args) if args.mjpg else None, ing, source,
-                                                                       'adaptive' if fill_params else window, fill_params, fill_log)
+                                                                       'adaptive' if fill_params else window, fill_params, fill_log, scene_log)
                 black_src = pipe_black if source else None
                 black_win = pipe_win if (window is not None or fill_params) else None
             else:
                 length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src,
-                                              window, black_win, adaptive, fill_log, mosaic, fill_frames)
+                                              window, black_win, adaptive, fill_log, mosaic, fill_frames, scene_log)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -805,6 +865,8 @@ def main():
                     np.save(stem + '_stable_bgr.npy', np.stack(colour_out))
                 np.savez_compressed(stem + '_maps.npz', x_map=np.stack(xmaps), y_map=np.stack(ymaps), black=np.stack(blacks))
                 print('wrote', stem + '_stable.npy')
+                if scene_log is not None:
+                    write_scenes_json(stem + '_scenes.json', args, scene_log)
                 # max-inscribed black-free rectangle over the whole clip (deploy_bundle.py:344-371), searched on the device
                 # (--output-size source: over the coverage counted at source size, and the frames are cut there)
                 # (--fill R: over the coverage counted at the window's output pixels)
@@ -857,7 +919,8 @@ def main():
                     traceback.print_exc()
                 if args.score:
                     try:
-                        score_outputs(clip, frames_out, colour_out, ing, window is not None or bool(fill_params), H, W, dev, stem)
+                        score_outputs(clip, frames_out, colour_out, ing, window is not None or bool(fill_params), H, W, dev, stem,
+                                      None if scene_log is None else [t for t, cut, _ in scene_log if cut])
                     except Exception:
                         traceback.print_exc()
 

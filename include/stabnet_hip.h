@@ -977,6 +977,52 @@ int stabnet_mosaic_compose(const unsigned char* warped, const float* px, const f
                            int feather_log2, int max_age, float w_min, unsigned char* canvas_cur, unsigned char* age_cur, int* counts,
                            void* stream);
 
+/* ---- scene cuts (csrc/scene.hip) --------------------------------------------------------------------------
+ * The online loop is recurrent: every frame is regressed against a ring of earlier STABILISED frames.  After a cut those hold
+ * another scene.  These entries decide on the device, inside the frame's graph, whether the incoming grey frame starts a new scene,
+ * and re-seed the ring when it does -- no host round trip, fixed arguments, capturable in a hipGraph.
+ *
+ * The statistic is all integers, so any grid shape and any order of the atomics gives the same bits.  For a train-normalised grey
+ * frame g [N][H][W], float32 in [-0.5, 0.5]:
+ *   t = floorf((g + 0.5f) * 255.0f + 0.5f), each operation one float32 rounding (no FMA contraction);
+ *   t = fminf(fmaxf(t, 0.f), 255.f): a NaN lands in 0, -inf in 0, +inf in 255;
+ *   q = (int)t, bin = q >> 3 (32 bins);  tile = (4*y / H) * 4 + (4*x / W), integer division: a 4 x 4 grid, ragged when H or W is
+ *   no multiple of 4;  hist[n][tile][bin] = uint32 count;  D[n] = sum over tiles and bins of |hist_cur - hist_prev| (<= 2*H*W);
+ *   the distance is d = D / (2*H*W), in [0, 1].
+ *
+ * stabnet_scene_state_words() = 1026.  The per-stream state is uint32 [N][1026] = {seen, since, prev[16][32], cur[16][32]} in device
+ * memory; all zeros is a fresh stream.  Between calls cur is zero: the call's second kernel moves it to prev and zeroes it, so that
+ * the next call's histogram kernel adds into zeros without a memset the graph cannot see.  After a call, prev is the histogram of
+ * the frame the call was given.
+ *
+ * stabnet_scene_update: two launches on `stream`.  (1) the histogram of grey into cur: a workgroup takes up to 2048 consecutive
+ * pixels of one tile row, counts into private LDS histograms (4 tile columns x 32 bins, one copy per wave and group of eight lanes),
+ * then adds its non-zero counters with integer atomicAdd; four pixels per load when W % 4 == 0 and grey is 16-byte aligned, one
+ * otherwise, with the same counts.  (2) one workgroup per stream forms D and evaluates the rule
+ *   seen == 0:  flag = 0, D = 0 (the first frame has nothing to differ from);
+ *   otherwise:  flag = (since >= min_gap) && (D > thr_num);
+ * then since = flag ? 0 : since + 1 and seen = seen + 1 (both saturating at 0xffffffff), prev = cur, cur = 0, flag[n] = flag,
+ * dist[n] = D.  The host computes thr_num = floor(threshold * 2.0 * H * W) in double, threshold in (0, 1].  `since` counts the
+ * frames since the last flag (or since the start), so flashes closer than min_gap frames to the last cut are not flagged.
+ * Nothing allocates, synchronises or copies to the host.
+ * Bad arguments (-1, before any launch): null pointers, N outside 1..65535, H or W outside 4..32767, min_gap < 0, pointers that are
+ * not memory of the current device.
+ *
+ * stabnet_ring_reseed_if: for every stream s with flag[s] != 0 what stabnet_ring_init does for that stream -- all `depth` frame
+ * slots become first_frame[s], all mask slots 0; a stream with flag[s] == 0 is not touched (its workgroups load the flag and
+ * return).  The ring head is left alone: with all slots equal its value does not matter.  flag: DEVICE int32 [S], read when the
+ * kernel runs (what stabnet_scene_update wrote earlier on the stream, also in a replayed graph).  A null flag is refused:
+ * stabnet_ring_init is the unconditional form.
+ *
+ * What a cut means: called as scene_update(cur), ring_reseed_if(ring, cur, flag), deploy_frame(cur), a flagged frame c meets a ring
+ * of 32 x frame c with zero masks and is then stabilised like any other frame -- the run from c on equals a fresh run on the clip
+ * that starts at c with its first frame doubled, bit for bit. */
+int stabnet_scene_state_words(void);
+int stabnet_scene_update(const float* grey, int N, int H, int W, unsigned thr_num, int min_gap, unsigned* state, int* flag,
+                         unsigned* dist, void* stream);
+int stabnet_ring_reseed_if(float* frames_ring, float* masks_ring, const float* first_frame, int S, int depth, int H, int W,
+                           const int* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

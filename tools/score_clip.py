@@ -2,7 +2,7 @@
 """Score a stabilised clip against its unstable source: the literature's cropping ratio, distortion value and stability score
 (stabnet_amd/metrics.py; the corner tracks and the robust homography fit run on the GPU).
 
-    python tools/score_clip.py --unstable A --stable B [--height 288 --width 512] [--thr-px 2] [--per-frame] [--json OUT]
+    python tools/score_clip.py --unstable A --stable B [--height 288 --width 512] [--thr-px 2] [--per-frame] [--json OUT] [--scenes FILE.json]
 
 A and B: uint8 .npy clips ([T,H,W] grey or [T,H,W,3] BGR) or Motion-JPEG .avi files with the same number of frames, read the way
 deploy_bundle.py reads its inputs (--decode device: decoded on the GPU where the stream allows it, else with Pillow).  Frames that
@@ -69,7 +69,16 @@ def main():
     ap.add_argument('--gray-weights', default='cv3', choices=['cv3', 'cv4'])
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--json', default=None, metavar='OUT', help='also write the result to this file')
+    ap.add_argument('--scenes', default=None, metavar='FILE.json',
+                    help='<name>_scenes.json of a deploy_bundle.py --scene-cut run: the stable pair across each cut is left out of the stability '
+                         'path and counted as scene_cuts')
+    ap.add_argument('--scenes-offset', type=int, default=1,
+                    help='frame of the input clip that the first scored frame is (default 1: the driver\'s outputs start at the clip\'s frame 1)')
     a = ap.parse_args()
+    cuts = None
+    if a.scenes:
+        with open(a.scenes) as f:
+            cuts = [int(c) - a.scenes_offset for c in json.load(f)['cuts']]
     import torch
     from stabnet_amd import metrics
     dev = torch.device(a.device)
@@ -80,7 +89,10 @@ def main():
         raise SystemExit('the clips must have the same number of frames: %s has %d, %s has %d' % (a.unstable, nu, a.stable, ns))
     u = to_network(fu, nu, su, a.height, a.width, dev, a.gray_weights)
     s = to_network(fs, ns, ss, a.height, a.width, dev, a.gray_weights)
-    res = metrics.score_clip(u, s, fit=metrics.HomfitParams(hypotheses=a.hypotheses, thr_px=a.thr_px, seed=a.seed), per_frame=a.per_frame)
+    if cuts is not None:
+        cuts = [c for c in cuts if 0 <= c < nu]
+    res = metrics.score_clip(u, s, fit=metrics.HomfitParams(hypotheses=a.hypotheses, thr_px=a.thr_px, seed=a.seed), per_frame=a.per_frame,
+                             cuts=cuts)
     res.update(unstable=a.unstable, stable=a.stable)
     print(json.dumps(res))
     if a.json:
