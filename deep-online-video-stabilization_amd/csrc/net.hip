@@ -732,6 +732,13 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_REMAP_WIN_DEV: return "remap_win_dev_kernel";
         case PK_KERNEL_REMAP_WIN4_DEV: return "remap_win4_dev_kernel";
         case PK_KERNEL_REMAP_I420: return "remap_i420_kernel";
+        case PK_KERNEL_REMAP_CUBIC + 0: return "remap_cubic_kernel<1, 0>";
+        case PK_KERNEL_REMAP_CUBIC + 1: return "remap_cubic_kernel<4, 0>";
+        case PK_KERNEL_REMAP_CUBIC + 2: return "remap_cubic_kernel<1, 1>";
+        case PK_KERNEL_REMAP_CUBIC + 3: return "remap_cubic_kernel<4, 1>";
+        case PK_KERNEL_REMAP_CUBIC + 4: return "remap_cubic_kernel<1, 2>";
+        case PK_KERNEL_REMAP_CUBIC + 5: return "remap_cubic_kernel<4, 2>";
+        case PK_KERNEL_REMAP_I420_CUBIC: return "remap_i420_kernel<true>";
         case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
         case PK_KERNEL_TVL1_STEP: return "tvl1_step_kernel";
         case PK_KERNEL_TVL1_FUSED: return "tvl1_fused_kernel";

@@ -100,8 +100,163 @@ __device__ __forceinline__ unsigned remap_blend(int v00, int v01, int v10, int v
     return (unsigned)min(max(acc, 0), 255);
 }
 
+// ---- the bicubic taps (--interp cubic): cv2.remap(..., INTER_CUBIC), OpenCV's fixed-point path (imgwarp.cpp: initInterTab2D(INTER_CUBIC,
+// fixpt = true) + remapBicubic<FixedPtCast<int, uchar, 15>, short, 32768>; tests/remap_cubic_model.py).  The coordinate and its
+// quantisation are the bilinear path's; the 16 taps sit at rows iy - 1 .. iy + 2, columns ix - 1 .. ix + 2, and their weights are entry
+// (fy, fx) of BicubicTab_i: saturate_cast<short>(rint(float32(cy[k1] * cx[k2]) * 32768)) of the two 1-D rows interpolateCubic(f / 32)
+// (A = -0.75, float32, left to right, not contracted), then the table's repair: an entry whose taps do not sum to 32768 (657 of the
+// 1024) has the difference taken from the smallest (sum too large) or largest (too small) of taps [2..3][2..3].  Signed weights: the
+// blend clamps at both ends.
+// The kernels read the 32 KiB int16 table from global memory, two 16-byte loads per pixel (measured 3-13 % faster per launch than forming
+// the weights in registers: profiles/r20_remap_cubic_weights_ab.txt).  The table is a CONSTANT of the code object, evaluated by the compiler
+// from the functions below (IEEE float32, nothing contracted): no upload, no state per device, nothing to do before a graph is captured.
+// The host builder (stabnet_remap_cubic_table) runs the same functions at run time; the tests hold both to the NumPy model.
+constexpr __host__ __device__ void cubic_coeffs(int i, float* c) {
+    const float A = -0.75f, x = (float)i * (1.f / 32);
+    c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
+    c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
+    c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
+    c[3] = 1.f - c[0] - c[1] - c[2];
+}
+
+// rint of |v| < 2^23, half to even (v - (float)i is exact there); constexpr, unlike rintf
+constexpr __host__ __device__ int cubic_rint(float v) {
+    const int i = (int)v;
+    const float r = v - (float)i;
+    if (r > 0.5f || (r == 0.5f && (i & 1))) return i + 1;
+    if (r < -0.5f || (r == -0.5f && (i & 1))) return i - 1;
+    return i;
+}
+
+// w[k1 * 4 + k2]: the weight of the tap at row iy - 1 + k1, column ix - 1 + k2
+constexpr __host__ __device__ void cubic_weights_calc(int fx, int fy, int* w) {
+    float cx[4] = {}, cy[4] = {};
+    cubic_coeffs(fx, cx); cubic_coeffs(fy, cy);
+    int sum = 0;
+    for (int k1 = 0; k1 < 4; ++k1)
+        for (int k2 = 0; k2 < 4; ++k2) {
+            const float v = cy[k1] * cx[k2];
+            int iv = cubic_rint(v * 32768.0f);
+            iv = iv < -32768 ? -32768 : (iv > 32767 ? 32767 : iv);       // saturate_cast<short>: entry (0, 0)'s 1.0 becomes 32767
+            w[k1 * 4 + k2] = iv; sum += iv;
+        }
+    // the repair loop of initInterTab2D with ksize = 4: k1, k2 in {2, 3} in row order, the minimum with strict <, otherwise the maximum
+    // with strict >, both starting at tap [2][2]; diff == 0 leaves the entry alone
+    const int diff = sum - 32768;
+    int mk = 10, Mk = 10;
+    for (int k = 0; k < 4; ++k) {
+        const int t = 10 + (k & 1) + 4 * (k >> 1);
+        if (w[t] < w[mk]) mk = t;
+        else if (w[t] > w[Mk]) Mk = t;
+    }
+    w[diff < 0 ? Mk : mk] -= diff;
+}
+
+struct alignas(16) CubicTab { short w[1024 * 16]; };         // entry fy * 32 + fx, tap k1 * 4 + k2
+constexpr CubicTab cubic_make_tab() {
+    CubicTab t = {};
+    for (int e = 0; e < 1024; ++e) {
+        int w[16] = {};
+        cubic_weights_calc(e & 31, e >> 5, w);
+        for (int k = 0; k < 16; ++k) t.w[e * 16 + k] = (short)w[k];
+    }
+    return t;
+}
+__device__ const CubicTab g_cubic_tab = cubic_make_tab();
+
+__device__ __forceinline__ void cubic_weights(int fx, int fy, int* w) {
+    const int4* p = reinterpret_cast<const int4*>(g_cubic_tab.w + ((fy * 32 + fx) << 4));
+    const int4 a = p[0], b = p[1];
+    const int v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { w[2 * k] = (v[k] << 16) >> 16; w[2 * k + 1] = v[k] >> 16; }
+}
+
+__device__ __forceinline__ unsigned remap_cubic_round(int acc) { return (unsigned)min(max((acc + (1 << 14)) >> 15, 0), 255); }
+
+// One channel of one pixel by byte loads: im the frame (or plane), pixels C bytes apart; a tap outside reads `border`.
+__device__ __forceinline__ unsigned remap_cubic_px(const unsigned char* __restrict__ im, size_t row_stride, int C, int ch, int SH, int SW, int ix,
+        int iy, const int* w, int border) {
+    int acc = 0;
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) {
+        const int yy = iy - 1 + k1;
+        const bool oky = yy >= 0 && yy < SH;
+#pragma unroll
+        for (int k2 = 0; k2 < 4; ++k2) {
+            const int xx = ix - 1 + k2;
+            const int v = (oky && xx >= 0 && xx < SW) ? (int)im[(size_t)yy * row_stride + (size_t)xx * C + ch] : border;
+            acc += v * w[k1 * 4 + k2];
+        }
+    }
+    return remap_cubic_round(acc);
+}
+
+// The four BGR taps of row yy from pixel x0 on: 12 contiguous bytes in three dwords, border 0.  All four inside the row: the four
+// aligned dwords that cover them where they lie inside [lo, hi) (the frame's own bytes), funnel-shifted; bytes otherwise, and tap by
+// tap where the row's end cuts the taps.  Nothing outside [lo, hi) is read.
+struct Bytes12 { unsigned d[3]; };
+__device__ __forceinline__ Bytes12 remap_cubic_row12(const unsigned char* __restrict__ im, size_t row_stride, int yy, int x0, int SH, int SW,
+        const unsigned char* lo, const unsigned char* hi) {
+    Bytes12 b; b.d[0] = 0u; b.d[1] = 0u; b.d[2] = 0u;
+    if (yy < 0 || yy >= SH || x0 + 3 < 0 || x0 >= SW) return b;
+    const unsigned char* row = im + (size_t)yy * row_stride;
+    if (x0 >= 0 && x0 + 3 < SW) {
+        const unsigned char* p = row + (size_t)x0 * 3;
+        const uintptr_t al = (uintptr_t)p & ~(uintptr_t)3;
+        const int sh = 8 * (int)((uintptr_t)p & 3);
+        if (al >= (uintptr_t)lo && al + 16 <= (uintptr_t)hi) {
+            const unsigned* q = reinterpret_cast<const unsigned*>(al);
+            const unsigned q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+            b.d[0] = (unsigned)(((((unsigned long long)q1) << 32) | q0) >> sh);
+            b.d[1] = (unsigned)(((((unsigned long long)q2) << 32) | q1) >> sh);
+            b.d[2] = (unsigned)(((((unsigned long long)q3) << 32) | q2) >> sh);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) b.d[k >> 2] |= ((unsigned)p[k]) << (8 * (k & 3));
+        }
+        return b;
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < 4; ++k2) {
+        const int xx = x0 + k2;
+        if (xx < 0 || xx >= SW) continue;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) b.d[(k2 * 3 + ch) >> 2] |= ((unsigned)row[(size_t)xx * 3 + ch]) << (8 * ((k2 * 3 + ch) & 3));
+    }
+    return b;
+}
+
+// The same for a dense plane (C == 1, rows SW bytes apart): four bytes in one dword, a tap outside reads `border`.
+__device__ __forceinline__ unsigned remap_cubic_row4(const unsigned char* __restrict__ im, int yy, int x0, int SH, int SW, unsigned border) {
+    if (yy < 0 || yy >= SH || x0 + 3 < 0 || x0 >= SW) return border * 0x01010101u;
+    const unsigned char* row = im + (size_t)yy * SW;
+    const unsigned char* hi = im + (size_t)SH * SW;
+    unsigned r = 0u;
+    if (x0 >= 0 && x0 + 3 < SW) {
+        const unsigned char* p = row + x0;
+        const uintptr_t al = (uintptr_t)p & ~(uintptr_t)3;
+        const int sh = 8 * (int)((uintptr_t)p & 3);
+        if (al >= (uintptr_t)im && al + 8 <= (uintptr_t)hi) {
+            const unsigned* q = reinterpret_cast<const unsigned*>(al);
+            const unsigned q0 = q[0], q1 = q[1];
+            return (unsigned)(((((unsigned long long)q1) << 32) | q0) >> sh);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r |= ((unsigned)p[k]) << (8 * k);
+        return r;
+    }
+#pragma unroll
+    for (int k2 = 0; k2 < 4; ++k2) {
+        const int xx = x0 + k2;
+        r |= ((xx >= 0 && xx < SW) ? (unsigned)row[xx] : border) << (8 * k2);
+    }
+    return r;
+}
+
 // One pixel: output pixel `pix` of stream n, its taps into the small maps given.  Any C, width, stride and alignment; byte loads and stores.
-template <bool AFFINE>
+// CUBIC: the 16 taps above in place of the four bilinear ones; everything else is shared.
+template <bool AFFINE, bool CUBIC = false>
 __device__ __forceinline__ void remap_pixel(const unsigned char* __restrict__ src, const SrcRemapArgs& a,
         const float* __restrict__ small_maps, int n, const Taps1D& tx, const Taps1D& ty, size_t pix, unsigned char* __restrict__ out,
         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
@@ -110,14 +265,21 @@ __device__ __forceinline__ void remap_pixel(const unsigned char* __restrict__ sr
     const SrcCoord c = remap_src_coord<AFFINE>(small_maps + ((size_t)n * 2 + 0) * hw, small_maps + ((size_t)n * 2 + 1) * hw, a, tx, ty);
     if (px_out != nullptr) { px_out[pix] = c.px; py_out[pix] = c.py; }
     const RemapTaps t = remap_taps(c);
-    const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
-    const unsigned char* im = src + (size_t)n * a.frame_stride;
-    for (int ch = 0; ch < C; ++ch) {
-        const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)t.ix * C + ch] : 0;
-        const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
-        const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)t.ix * C + ch] : 0;
-        const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
-        out[pix * C + ch] = (unsigned char)remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
+    if constexpr (CUBIC) {
+        const unsigned char* im = src + (size_t)n * a.frame_stride;
+        int w[16];
+        cubic_weights(c.qx & 31, c.qy & 31, w);
+        for (int ch = 0; ch < C; ++ch) out[pix * C + ch] = (unsigned char)remap_cubic_px(im, a.row_stride, C, ch, a.SH, a.SW, t.ix, t.iy, w, 0);
+    } else {
+        const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
+        const unsigned char* im = src + (size_t)n * a.frame_stride;
+        for (int ch = 0; ch < C; ++ch) {
+            const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)t.ix * C + ch] : 0;
+            const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
+            const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)t.ix * C + ch] : 0;
+            const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.row_stride + (size_t)(t.ix + 1) * C + ch] : 0;
+            out[pix * C + ch] = (unsigned char)remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
+        }
     }
     if (black_count != nullptr && remap_src_black(c, a.SH, a.SW)) black_count[pix] += 1;
 }
@@ -144,8 +306,9 @@ __device__ __forceinline__ unsigned long long remap_src_load6(const unsigned cha
 // frames of the path); taps_x(e) gives the horizontal taps of pixel e.  The byte traffic of remap_pixel -- 12 one-byte gathers and 3
 // one-byte stores per pixel -- becomes 4-byte traffic: the two taps of a row are 6 CONTIGUOUS bytes (BGR BGR), fetched through
 // remap_src_load6 (the source may have any width, stride and alignment); the 12 output bytes of the four pixels leave as three 4-byte
-// stores of one thread.  Same integer arithmetic, same results.
-template <bool AFFINE, class TapsX>
+// stores of one thread.  Same integer arithmetic, same results.  CUBIC: the four taps of a row are 12 contiguous bytes
+// (remap_cubic_row12), four rows per pixel; the stores are the same three.
+template <bool AFFINE, bool CUBIC = false, class TapsX>
 __device__ __forceinline__ void remap_pixel4(const unsigned char* __restrict__ src, const SrcRemapArgs& a,
         const float* __restrict__ small_maps, int n, TapsX taps_x, const Taps1D& ty, size_t pix, unsigned char* __restrict__ out,
         int* __restrict__ black_count, float* __restrict__ px_out, float* __restrict__ py_out) {
@@ -165,6 +328,25 @@ __device__ __forceinline__ void remap_pixel4(const unsigned char* __restrict__ s
         // remap_win4_dev_kernel then measured half a timer tick over the parent's range (profiles/remap_refactor_ab.txt)
         const int ix = min(max(c.qx >> 5, -32768), 32767), iy = min(max(c.qy >> 5, -32768), 32767);
         const int fx = c.qx & 31, fy = c.qy & 31;
+        if constexpr (CUBIC) {
+            int w[16], acc[3] = {0, 0, 0};
+            cubic_weights(fx, fy, w);
+#pragma unroll
+            for (int k1 = 0; k1 < 4; ++k1) {
+                const Bytes12 b = remap_cubic_row12(im, a.row_stride, iy - 1 + k1, ix - 1, SH, SW, im, end);
+#pragma unroll
+                for (int k = 0; k < 12; ++k) acc[k % 3] += (int)((b.d[k >> 2] >> (8 * (k & 3))) & 0xffu) * w[k1 * 4 + k / 3];
+            }
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                unsigned o = remap_cubic_round(acc[ch]);
+                asm volatile("" : "+v"(o));                  // the byte finished in its own register before packing (see remap_plane_pixels)
+                const int byte = e * 3 + ch;
+                ob[byte >> 2] |= o << (8 * (byte & 3));
+            }
+            if (black_count != nullptr && remap_src_black(c, SH, SW)) black_count[pix + e] += 1;
+            continue;
+        }
         int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
         if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
         const bool vx0 = ix >= 0 && ix < SW, vx1 = ix + 1 >= 0 && ix + 1 < SW, vy0 = iy >= 0 && iy < SH, vy1 = iy + 1 >= 0 && iy + 1 < SH;
@@ -228,7 +410,7 @@ struct WinRemapArgs { SrcRemapArgs a; int OH, OW; WinSteps ws; };
 
 // grid (cdiv(OW / PX, blockDim.x), OH, N), one workgroup per row segment: the vertical taps and the two small-map rows are wave-uniform.
 // PX consecutive output pixels per thread: 1, or 4 under remap_pixel4's preconditions on OW and out.
-template <int PX, bool WINDOW>
+template <int PX, bool WINDOW, bool CUBIC = false>
 __device__ __forceinline__ void remap_row_body(const unsigned char* __restrict__ src, const SrcRemapArgs& a, int OH, int OW, const WinSteps& ws,
         const float* __restrict__ small_maps, unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out,
         float* __restrict__ py_out) {
@@ -237,8 +419,8 @@ __device__ __forceinline__ void remap_row_body(const unsigned char* __restrict__
     auto taps_x = [&](int e) { return WINDOW ? cv_taps_at(ws.x0 + ((double)(x + e) + 0.5) * ws.xstep, a.w, a.xscale) : cv_taps(x + e, a.w, a.xscale); };
     const Taps1D ty = WINDOW ? cv_taps_at(ws.y0 + ((double)y + 0.5) * ws.ystep, a.h, a.yscale) : cv_taps(y, a.h, a.yscale);
     const size_t pix = ((size_t)n * OH + y) * OW + x;
-    if constexpr (PX == 4) remap_pixel4<true>(src, a, small_maps, n, taps_x, ty, pix, out, black_count, px_out, py_out);
-    else remap_pixel<true>(src, a, small_maps, n, taps_x(0), ty, pix, out, black_count, px_out, py_out);
+    if constexpr (PX == 4) remap_pixel4<true, CUBIC>(src, a, small_maps, n, taps_x, ty, pix, out, black_count, px_out, py_out);
+    else remap_pixel<true, CUBIC>(src, a, small_maps, n, taps_x(0), ty, pix, out, black_count, px_out, py_out);
 }
 
 __global__ __launch_bounds__(256) void remap_src_kernel(const unsigned char* __restrict__ src, SrcRemapArgs a, const float* __restrict__ small_maps,
@@ -289,6 +471,29 @@ __global__ __launch_bounds__(256) void remap_win4_dev_kernel(const unsigned char
         float* __restrict__ px_out, float* __restrict__ py_out) {
     const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
     remap_row_body<4, true>(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+}
+
+// ---- the same six row-segment kernels with the bicubic taps (stabnet_warp_rev_bundle2_cubic).  KIND 0: the whole frame at its own size
+// (remap_src_kernel's body), 1: the window in wa.ws, 2: the window loaded from device memory; `window` is read by KIND 2 only.
+template <int PX, int KIND>
+__global__ __launch_bounds__(256) void remap_cubic_kernel(const unsigned char* __restrict__ src, WinRemapArgs wa, const double* __restrict__ window,
+        const float* __restrict__ small_maps, unsigned char* __restrict__ out, int* __restrict__ black_count, float* __restrict__ px_out,
+        float* __restrict__ py_out) {
+    if constexpr (KIND == 2) {
+        const WinSteps ws = remap_win_load(window, blockIdx.z, wa.a.SH, wa.a.SW, wa.OH, wa.OW);
+        remap_row_body<PX, true, true>(src, wa.a, wa.OH, wa.OW, ws, small_maps, out, black_count, px_out, py_out);
+    } else {
+        remap_row_body<PX, KIND == 1, true>(src, wa.a, wa.OH, wa.OW, wa.ws, small_maps, out, black_count, px_out, py_out);
+    }
+}
+
+// out[(fy * 32 + fx) * 16 + k]: the weights of every phase exactly as the kernels above form them.  One thread per phase.
+__global__ __launch_bounds__(256) void remap_cubic_weights_kernel(short* __restrict__ out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;            // grid 4: 1024 phases
+    int w[16];
+    cubic_weights(e & 31, e >> 5, w);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[e * 16 + k] = (short)w[k];
 }
 
 // ---- adaptive borderless output: the largest centred window of one frame that is provably free of uncovered pixels ----
@@ -385,7 +590,7 @@ struct I420Args {
 };
 
 // PX consecutive output pixels of row y of one plane from x on; orow, black_row: the row's first output byte / count (or null)
-template <int PX>
+template <int PX, bool CUBIC = false>
 __device__ __forceinline__ void remap_plane_pixels(const unsigned char* __restrict__ im, const I420Geom& g, const float* __restrict__ mx,
         const float* __restrict__ my, int x, int y, int border, unsigned char* __restrict__ orow, int* __restrict__ black_row) {
     const SrcRemapArgs& a = g.a;
@@ -396,12 +601,30 @@ __device__ __forceinline__ void remap_plane_pixels(const unsigned char* __restri
         const Taps1D tx = cv_taps_at(g.ws.x0 + ((double)(x + e) + 0.5) * g.ws.xstep, a.w, a.xscale);
         const SrcCoord c = remap_src_coord<true>(mx, my, a, tx, ty);
         const RemapTaps t = remap_taps(c);
-        const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
-        const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix] : border;
-        const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix + 1] : border;
-        const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix] : border;
-        const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix + 1] : border;
-        unsigned o = remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
+        unsigned o;
+        if constexpr (CUBIC) {
+            int w[16];
+            cubic_weights(c.qx & 31, c.qy & 31, w);
+            if constexpr (PX == 4) {                          // the four taps of a row are one dword
+                int acc = 0;
+#pragma unroll
+                for (int k1 = 0; k1 < 4; ++k1) {
+                    const unsigned r = remap_cubic_row4(im, t.iy - 1 + k1, t.ix - 1, a.SH, a.SW, (unsigned)border);
+#pragma unroll
+                    for (int k2 = 0; k2 < 4; ++k2) acc += (int)((r >> (8 * k2)) & 0xffu) * w[k1 * 4 + k2];
+                }
+                o = remap_cubic_round(acc);
+            } else {
+                o = remap_cubic_px(im, (size_t)a.SW, 1, 0, a.SH, a.SW, t.ix, t.iy, w, border);
+            }
+        } else {
+            const bool x0 = t.ix >= 0 && t.ix < a.SW, x1 = t.ix + 1 >= 0 && t.ix + 1 < a.SW, y0 = t.iy >= 0 && t.iy < a.SH, y1 = t.iy + 1 >= 0 && t.iy + 1 < a.SH;
+            const int v00 = (x0 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix] : border;
+            const int v01 = (x1 && y0) ? (int)im[(size_t)t.iy * a.SW + t.ix + 1] : border;
+            const int v10 = (x0 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix] : border;
+            const int v11 = (x1 && y1) ? (int)im[(size_t)(t.iy + 1) * a.SW + t.ix + 1] : border;
+            o = remap_blend(v00, v01, v10, v11, t.w00, t.w01, t.w10, t.w11);
+        }
         if constexpr (PX == 4) {
             // The byte is finished in a register of its own before it is packed (an empty statement the compiler cannot see through).
             // Left to itself, hipcc folds the shift and clamp of pixels 0 and 1 into one v_ashr_pk_u8_i32 on the first accumulator's own
@@ -420,6 +643,9 @@ __device__ __forceinline__ void remap_plane_pixels(const unsigned char* __restri
 // grid (cdiv(items, blockDim.x), OH [+ 2 * (OH / 2)], N): one workgroup per row segment of ONE plane -- rows 0 .. OH - 1 are the Y plane's,
 // then the U plane's OH / 2, then the V plane's -- so the plane, its path and its vertical taps are workgroup-uniform.  items: the most
 // any plane needs (OW / 4 or OW threads for a Y row, half of that for a chroma row on the same path).
+// CUBIC: the bicubic taps on every plane (stabnet_warp_rev_bundle2_i420_cubic).  (One templated kernel, not a shared body behind two kernels:
+// handing the by-value I420Args on to a function changed the bilinear kernel's code.)
+template <bool CUBIC>
 __global__ __launch_bounds__(256) void remap_i420_kernel(const unsigned char* __restrict__ src, I420Args ia, const float* __restrict__ small_maps,
         unsigned char* __restrict__ out, int* __restrict__ black_count) {
     const int n = blockIdx.z, OH = ia.g[0].OH, CH = ia.g[1].OH;
@@ -435,8 +661,8 @@ __global__ __launch_bounds__(256) void remap_i420_kernel(const unsigned char* __
     const unsigned char* im = src + (size_t)n * ia.src_frame + ia.src_off[plane];
     unsigned char* orow = out + (size_t)n * ia.out_frame + ia.out_off[plane] + (size_t)y * g.OW;
     int* black_row = (plane == 0 && black_count != nullptr) ? black_count + ((size_t)n * OH + y) * g.OW : nullptr;
-    if (px4) remap_plane_pixels<4>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
-    else remap_plane_pixels<1>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
+    if (px4) remap_plane_pixels<4, CUBIC>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
+    else remap_plane_pixels<1, CUBIC>(im, g, mx, my, x, y, ia.border[plane], orow, black_row);
 }
 
 // STABNET_REMAP_VEC4=0: the one-pixel-per-thread kernels everywhere (debug switch; read once)
@@ -473,20 +699,25 @@ static int remap_shrink(const float* x_map, const float* y_map, int N, int H, in
 // kernels over row segments of the output.  _src is the whole frame at its own size (window not read, OH, OW == SH, SW).
 enum RemapKind { REMAP_SRC, REMAP_WIN, REMAP_WIN_DEV };
 
-static int remap_src_entry(RemapKind kind, const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
-                           const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
-                           float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
+// stabnet_warp_rev_bundle2_cubic is the same entry again (cubic: its three window kinds are the three kinds), launching the bicubic kernels.
+static int remap_src_entry(RemapKind kind, bool cubic, const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                           const float* x_map, const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out,
+                           int* black_count, float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
 #define REMAP_NAMES(n) {n, n ": src", n ": out", n ": workspace", n ": window"}
-    static const struct { const char *who, *src, *out, *workspace, *window; } names[3] = {
-        REMAP_NAMES("warp_rev_bundle2_src"), REMAP_NAMES("warp_rev_bundle2_win"), REMAP_NAMES("warp_rev_bundle2_win_dev")};
+    static const struct { const char *who, *src, *out, *workspace, *window; } all_names[4] = {
+        REMAP_NAMES("warp_rev_bundle2_src"), REMAP_NAMES("warp_rev_bundle2_win"), REMAP_NAMES("warp_rev_bundle2_win_dev"),
+        REMAP_NAMES("warp_rev_bundle2_cubic")};
 #undef REMAP_NAMES
-    const char* who = names[kind].who;
+    const auto& nm = all_names[cubic ? 3 : kind];
+    const char* who = nm.who;
     SN_REQUIRE(src && x_map && y_map && out && workspace, "%s: null pointer", who);
     SN_REQUIRE(kind == REMAP_SRC || window != nullptr, "%s: null window", who);
     SN_REQUIRE(C == 1 || C == 3, "%s: C must be 1 (grey) or 3 (BGR), got %d", who, C);
     SN_REQUIRE(N >= 1 && N <= 65535, "%s: batch %d outside 1..65535", who, N);
     SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767, "%s: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", who, SH, SW);
     SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "%s: output %dx%d outside 1..32767", who, OH, OW);
+    SN_REQUIRE(kind != REMAP_SRC || (OH == SH && OW == SW), "%s: window_kind 0 is the whole frame at its own size, got output %dx%d of source %dx%d",
+               who, OH, OW, SH, SW);
     SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "%s: maps %dx%d leave nothing at rate %d", who, H, W, rate);
     SN_REQUIRE(row_stride_bytes >= (size_t)SW * C, "%s: row stride %zu < %d * %d bytes", who, row_stride_bytes, SW, C);
     SN_REQUIRE((px_out == nullptr) == (py_out == nullptr), "%s: px_out and py_out go together", who);
@@ -501,10 +732,10 @@ static int remap_src_entry(RemapKind kind, const unsigned char* src, int N, int 
                    "%s: window (%g, %g, %g, %g) leaves the %dx%d frame", who, y0, x0, wh, ww, SH, SW);
     }
     hipStream_t st = (hipStream_t)stream; Prof* prof = static_cast<Prof*>(profp);
-    int rc = sn_check_device(src, names[kind].src, st);
-    if (rc == 0) rc = sn_check_device(out, names[kind].out, st);
-    if (rc == 0) rc = sn_check_device(workspace, names[kind].workspace, st);
-    if (rc == 0 && kind == REMAP_WIN_DEV) rc = sn_check_device(window, names[kind].window, st);
+    int rc = sn_check_device(src, nm.src, st);
+    if (rc == 0) rc = sn_check_device(out, nm.out, st);
+    if (rc == 0) rc = sn_check_device(workspace, nm.workspace, st);
+    if (rc == 0 && kind == REMAP_WIN_DEV) rc = sn_check_device(window, nm.window, st);
     if (rc) return rc;
     const int h = H / rate, w = W / rate;
     rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, prof);
@@ -522,6 +753,26 @@ static int remap_src_entry(RemapKind kind, const unsigned char* src, int N, int 
         {{PK_KERNEL_REMAP_SRC, "remap_src_kernel"}, {PK_KERNEL_REMAP_SRC4, "remap_src4_kernel"}},
         {{PK_KERNEL_REMAP_WIN, "remap_win_kernel"}, {PK_KERNEL_REMAP_WIN4, "remap_win4_kernel"}},
         {{PK_KERNEL_REMAP_WIN_DEV, "remap_win_dev_kernel"}, {PK_KERNEL_REMAP_WIN4_DEV, "remap_win4_dev_kernel"}}};
+    if (cubic) {
+        static const char* const cubic_names[3][2] = {{"remap_cubic_kernel<1, 0>", "remap_cubic_kernel<4, 0>"},
+                                                      {"remap_cubic_kernel<1, 1>", "remap_cubic_kernel<4, 1>"},
+                                                      {"remap_cubic_kernel<1, 2>", "remap_cubic_kernel<4, 2>"}};
+        const double* dwin = kind == REMAP_WIN_DEV ? window : nullptr;      // (a host window is in wa.ws)
+        const bool rec = prof && prof->begin(st);
+        if (kind == REMAP_SRC) {
+            if (v4) remap_cubic_kernel<4, 0><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+            else remap_cubic_kernel<1, 0><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+        } else if (kind == REMAP_WIN) {
+            if (v4) remap_cubic_kernel<4, 1><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+            else remap_cubic_kernel<1, 1><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+        } else {
+            if (v4) remap_cubic_kernel<4, 2><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+            else remap_cubic_kernel<1, 2><<<grid, threads, 0, st>>>(src, wa, dwin, workspace, out, black_count, px_out, py_out);
+        }
+        if (rec) prof->end(st, PK_KERNEL_REMAP_CUBIC + 2 * kind + (v4 ? 1 : 0), 0.0, bytes);
+        SN_LAUNCH_CHECK(cubic_names[kind][v4]);
+        return STABNET_OK;
+    }
     const bool rec = prof && prof->begin(st);
     if (kind == REMAP_SRC) {
         if (v4) remap_src4_kernel<<<grid, threads, 0, st>>>(src, wa.a, workspace, out, black_count, px_out, py_out);
@@ -535,6 +786,73 @@ static int remap_src_entry(RemapKind kind, const unsigned char* src, int N, int 
     }
     if (rec) prof->end(st, kernels[kind][v4].id, 0.0, bytes);
     SN_LAUNCH_CHECK(kernels[kind][v4].name);
+    return STABNET_OK;
+}
+
+// stabnet_warp_rev_bundle2_i420 and _i420_cubic: one entry, the kernel apart
+static int remap_i420_entry(bool cubic, const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, int border_y, unsigned char* out, int* black_count,
+        float* workspace, void* stream, void* profp) {
+    const char* who = cubic ? "warp_rev_bundle2_i420_cubic" : "warp_rev_bundle2_i420";
+    SN_REQUIRE(src && x_map && y_map && out && workspace, "%s: null pointer", who);
+    SN_REQUIRE(planes == 1 || planes == 3, "%s: planes must be 1 (Y only) or 3 (Y, U, V of a 4:2:0 frame), got %d", who, planes);
+    SN_REQUIRE(N >= 1 && N <= 65535, "%s: batch %d outside 1..65535", who, N);
+    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767, "%s: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", who, SH, SW);
+    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "%s: output %dx%d outside 1..32767", who, OH, OW);
+    SN_REQUIRE(planes == 1 || ((SH | SW | OH | OW) & 1) == 0, "%s: a 4:2:0 frame has even sides, got source %dx%d, output %dx%d", who, SH, SW, OH, OW);
+    const size_t src_y = (size_t)SH * SW, src_c = planes == 3 ? (size_t)(SH / 2) * (SW / 2) : 0, src_bytes = src_y + 2 * src_c;
+    SN_REQUIRE(frame_stride_bytes >= src_bytes, "%s: frame stride %zu < the frame's %zu bytes", who, frame_stride_bytes, src_bytes);
+    SN_REQUIRE(border_y >= 0 && border_y <= 255, "%s: border_y %d outside 0..255", who, border_y);
+    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "%s: maps %dx%d leave nothing at rate %d", who, H, W, rate);
+    double y0 = 0.0, x0 = 0.0, wh = (double)SH, ww = (double)SW;
+    if (window == nullptr) {
+        SN_REQUIRE(OH == SH && OW == SW, "%s: a null window is the whole frame at its own size, got output %dx%d of source %dx%d", who, OH, OW, SH, SW);
+    } else {
+        y0 = window[0]; x0 = window[1]; wh = window[2]; ww = window[3];
+        SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
+                   "%s: window (%g, %g, %g, %g) is not finite", who, y0, x0, wh, ww);
+        SN_REQUIRE(wh > 0.0 && ww > 0.0, "%s: window %g x %g is empty", who, wh, ww);
+        SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
+                   "%s: window (%g, %g, %g, %g) leaves the %dx%d frame", who, y0, x0, wh, ww, SH, SW);
+    }
+    hipStream_t st = (hipStream_t)stream; Prof* prof = static_cast<Prof*>(profp);
+    int rc = sn_check_device(src, cubic ? "warp_rev_bundle2_i420_cubic: src" : "warp_rev_bundle2_i420: src", st);
+    if (rc == 0) rc = sn_check_device(out, cubic ? "warp_rev_bundle2_i420_cubic: out" : "warp_rev_bundle2_i420: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, cubic ? "warp_rev_bundle2_i420_cubic: workspace" : "warp_rev_bundle2_i420: workspace", st);
+    if (rc) return rc;
+    const int h = H / rate, w = W / rate;
+    rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, prof);
+    if (rc) return rc;
+    I420Args ia;
+    const size_t out_y = (size_t)OH * OW, out_c = planes == 3 ? (size_t)(OH / 2) * (OW / 2) : 0;
+    ia.src_frame = frame_stride_bytes; ia.out_frame = out_y + 2 * out_c;
+    ia.src_off[0] = 0; ia.src_off[1] = src_y; ia.src_off[2] = src_y + src_c;
+    ia.out_off[0] = 0; ia.out_off[1] = out_y; ia.out_off[2] = out_y + out_c;
+    ia.border[0] = border_y; ia.border[1] = 128; ia.border[2] = 128;
+    int items = 0;
+    for (int k = 0; k < 2; ++k) {                            // luma; chroma: every length and the window halved (exact)
+        const int d = k + 1;
+        if (k == 1 && planes == 1) { ia.g[1] = ia.g[0]; ia.g[1].OH = 0; break; }
+        I420Geom& g = ia.g[k];
+        src_remap_args(g.a, SH / d, SW / d, 1, H, W, h, w, (size_t)(SW / d));
+        g.OH = OH / d; g.OW = OW / d;
+        g.ws = {x0 / d, y0 / d, (ww / d) / (double)g.OW, (wh / d) / (double)g.OH};
+    }
+    for (int p = 0; p < 3; ++p) {
+        const I420Geom& g = ia.g[p != 0];
+        const bool aligned = (((size_t)out + ia.out_off[p]) & 3) == 0 && (N == 1 || (ia.out_frame & 3) == 0);
+        ia.px4[p] = (p < planes && remap_vec4_enabled() && g.OW % 4 == 0 && aligned) ? 1 : 0;
+        if (p < planes && (ia.px4[p] ? g.OW / 4 : g.OW) > items) items = ia.px4[p] ? g.OW / 4 : g.OW;
+    }
+    const int threads = items >= 256 ? 256 : ((items + 63) & ~63);       // whole waves, a row segment each
+    const dim3 grid(cdiv(items, threads), ia.g[0].OH + (planes == 3 ? 2 * ia.g[1].OH : 0), N);
+    // algorithmic bytes: the window of every plane gathered once, the output written once, the two small maps
+    const double cf = planes == 3 ? 1.5 : 1.0, bytes = (double)N * ((wh * ww + (double)OH * OW) * cf + 8.0 * h * w);
+    const bool rec = prof && prof->begin(st);
+    if (cubic) remap_i420_kernel<true><<<grid, threads, 0, st>>>(src, ia, workspace, out, black_count);
+    else remap_i420_kernel<false><<<grid, threads, 0, st>>>(src, ia, workspace, out, black_count);
+    if (rec) prof->end(st, cubic ? PK_KERNEL_REMAP_I420_CUBIC : PK_KERNEL_REMAP_I420, 0.0, bytes);
+    SN_LAUNCH_CHECK(cubic ? "remap_i420_kernel<true>" : "remap_i420_kernel");
     return STABNET_OK;
 }
 
@@ -571,7 +889,7 @@ int stabnet_warp_rev_bundle2(const unsigned char* img, const float* x_map, const
 int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
         const float* y_map, int H, int W, int rate, unsigned char* out, int* black_count, float* workspace, float* px_out, float* py_out,
         void* stream, void* profp) {
-    return remap_src_entry(REMAP_SRC, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, nullptr, SH, SW, out, black_count, workspace,
+    return remap_src_entry(REMAP_SRC, false, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, nullptr, SH, SW, out, black_count, workspace,
                            px_out, py_out, stream, profp);
 }
 
@@ -581,7 +899,7 @@ int stabnet_warp_rev_bundle2_src(const unsigned char* src, int N, int SH, int SW
 int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
         const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
         float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
-    return remap_src_entry(REMAP_WIN, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
+    return remap_src_entry(REMAP_WIN, false, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
                            px_out, py_out, stream, profp);
 }
 
@@ -591,7 +909,7 @@ int stabnet_warp_rev_bundle2_win(const unsigned char* src, int N, int SH, int SW
 int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
         const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, unsigned char* out, int* black_count,
         float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
-    return remap_src_entry(REMAP_WIN_DEV, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
+    return remap_src_entry(REMAP_WIN_DEV, false, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
                            px_out, py_out, stream, profp);
 }
 
@@ -603,65 +921,52 @@ int stabnet_warp_rev_bundle2_win_dev(const unsigned char* src, int N, int SH, in
 int stabnet_warp_rev_bundle2_i420(const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes, const float* x_map,
         const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, int border_y, unsigned char* out, int* black_count,
         float* workspace, void* stream, void* profp) {
-    const char* who = "warp_rev_bundle2_i420";
-    SN_REQUIRE(src && x_map && y_map && out && workspace, "%s: null pointer", who);
-    SN_REQUIRE(planes == 1 || planes == 3, "%s: planes must be 1 (Y only) or 3 (Y, U, V of a 4:2:0 frame), got %d", who, planes);
-    SN_REQUIRE(N >= 1 && N <= 65535, "%s: batch %d outside 1..65535", who, N);
-    SN_REQUIRE(SH >= 1 && SH <= 32767 && SW >= 1 && SW <= 32767, "%s: source %dx%d outside 1..32767 (the remap's 16-bit pixel index)", who, SH, SW);
-    SN_REQUIRE(OH >= 1 && OH <= 32767 && OW >= 1 && OW <= 32767, "%s: output %dx%d outside 1..32767", who, OH, OW);
-    SN_REQUIRE(planes == 1 || ((SH | SW | OH | OW) & 1) == 0, "%s: a 4:2:0 frame has even sides, got source %dx%d, output %dx%d", who, SH, SW, OH, OW);
-    const size_t src_y = (size_t)SH * SW, src_c = planes == 3 ? (size_t)(SH / 2) * (SW / 2) : 0, src_bytes = src_y + 2 * src_c;
-    SN_REQUIRE(frame_stride_bytes >= src_bytes, "%s: frame stride %zu < the frame's %zu bytes", who, frame_stride_bytes, src_bytes);
-    SN_REQUIRE(border_y >= 0 && border_y <= 255, "%s: border_y %d outside 0..255", who, border_y);
-    SN_REQUIRE(H >= 1 && W >= 1 && rate >= 1 && H / rate >= 1 && W / rate >= 1, "%s: maps %dx%d leave nothing at rate %d", who, H, W, rate);
-    double y0 = 0.0, x0 = 0.0, wh = (double)SH, ww = (double)SW;
-    if (window == nullptr) {
-        SN_REQUIRE(OH == SH && OW == SW, "%s: a null window is the whole frame at its own size, got output %dx%d of source %dx%d", who, OH, OW, SH, SW);
-    } else {
-        y0 = window[0]; x0 = window[1]; wh = window[2]; ww = window[3];
-        SN_REQUIRE(std::isfinite(y0) && std::isfinite(x0) && std::isfinite(wh) && std::isfinite(ww),
-                   "%s: window (%g, %g, %g, %g) is not finite", who, y0, x0, wh, ww);
-        SN_REQUIRE(wh > 0.0 && ww > 0.0, "%s: window %g x %g is empty", who, wh, ww);
-        SN_REQUIRE(y0 >= -1e-6 && x0 >= -1e-6 && y0 + wh <= (double)SH + 1e-6 && x0 + ww <= (double)SW + 1e-6,
-                   "%s: window (%g, %g, %g, %g) leaves the %dx%d frame", who, y0, x0, wh, ww, SH, SW);
+    return remap_i420_entry(false, src, N, SH, SW, planes, frame_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, border_y, out, black_count,
+                            workspace, stream, profp);
+}
+
+/* The remaps above with cv2.remap's INTER_CUBIC in place of INTER_LINEAR (remap_cubic_kernel<PX, KIND>): 16 taps per channel at rows
+ * iy - 1 .. iy + 2, columns ix - 1 .. ix + 2, OpenCV's 15-bit table weights (g_cubic_tab through cubic_weights), out = clamp((sum +
+ * 16384) >> 15).  window_kind 0: the whole frame at its own size (window not read; OH, OW == SH, SW; with SH, SW == H, W the
+ * network-size remap), 1: window = four doubles in host memory, 2: window double [N,4] in device memory.  Coordinates, coverage and
+ * every refusal are the bilinear entries'. */
+int stabnet_warp_rev_bundle2_cubic(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, int window_kind, const double* window, int OH, int OW, unsigned char* out, int* black_count,
+        float* workspace, float* px_out, float* py_out, void* stream, void* profp) {
+    SN_REQUIRE(window_kind >= 0 && window_kind <= 2, "warp_rev_bundle2_cubic: window_kind must be 0 (none), 1 (host) or 2 (device), got %d", window_kind);
+    const RemapKind kind = window_kind == 0 ? REMAP_SRC : (window_kind == 1 ? REMAP_WIN : REMAP_WIN_DEV);
+    return remap_src_entry(kind, true, src, N, SH, SW, C, row_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, out, black_count, workspace,
+                           px_out, py_out, stream, profp);
+}
+
+/* stabnet_warp_rev_bundle2_i420 with the bicubic taps on every plane (remap_i420_kernel<true>); taps outside a plane read border_y / 128. */
+int stabnet_warp_rev_bundle2_i420_cubic(const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes, const float* x_map,
+        const float* y_map, int H, int W, int rate, const double* window, int OH, int OW, int border_y, unsigned char* out, int* black_count,
+        float* workspace, void* stream, void* profp) {
+    return remap_i420_entry(true, src, N, SH, SW, planes, frame_stride_bytes, x_map, y_map, H, W, rate, window, OH, OW, border_y, out, black_count,
+                            workspace, stream, profp);
+}
+
+/* BicubicTab_i by the functions the kernels' table is compiled from, run on the host (no GPU): out short [1024][16], entry fy * 32 + fx,
+ * tap k1 * 4 + k2. */
+int stabnet_remap_cubic_table(short* out) {
+    SN_REQUIRE(out != nullptr, "remap_cubic_table: null pointer");
+    for (int e = 0; e < 1024; ++e) {
+        int w[16];
+        cubic_weights_calc(e & 31, e >> 5, w);               // evaluated here, at run time: not a copy of the compiled table
+        for (int k = 0; k < 16; ++k) out[e * 16 + k] = (short)w[k];
     }
-    hipStream_t st = (hipStream_t)stream; Prof* prof = static_cast<Prof*>(profp);
-    int rc = sn_check_device(src, "warp_rev_bundle2_i420: src", st);
-    if (rc == 0) rc = sn_check_device(out, "warp_rev_bundle2_i420: out", st);
-    if (rc == 0) rc = sn_check_device(workspace, "warp_rev_bundle2_i420: workspace", st);
+    return STABNET_OK;
+}
+
+/* The same 16384 values written by the device, each phase through the function the remap kernels call (a read of their table): one launch. */
+int stabnet_remap_cubic_weights_dev(short* out_dev, void* stream) {
+    SN_REQUIRE(out_dev != nullptr, "remap_cubic_weights_dev: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = sn_check_device(out_dev, "remap_cubic_weights_dev: out", st);
     if (rc) return rc;
-    const int h = H / rate, w = W / rate;
-    rc = remap_shrink(x_map, y_map, N, H, W, h, w, workspace, st, prof);
-    if (rc) return rc;
-    I420Args ia;
-    const size_t out_y = (size_t)OH * OW, out_c = planes == 3 ? (size_t)(OH / 2) * (OW / 2) : 0;
-    ia.src_frame = frame_stride_bytes; ia.out_frame = out_y + 2 * out_c;
-    ia.src_off[0] = 0; ia.src_off[1] = src_y; ia.src_off[2] = src_y + src_c;
-    ia.out_off[0] = 0; ia.out_off[1] = out_y; ia.out_off[2] = out_y + out_c;
-    ia.border[0] = border_y; ia.border[1] = 128; ia.border[2] = 128;
-    int items = 0;
-    for (int k = 0; k < 2; ++k) {                            // luma; chroma: every length and the window halved (exact)
-        const int d = k + 1;
-        if (k == 1 && planes == 1) { ia.g[1] = ia.g[0]; ia.g[1].OH = 0; break; }
-        I420Geom& g = ia.g[k];
-        src_remap_args(g.a, SH / d, SW / d, 1, H, W, h, w, (size_t)(SW / d));
-        g.OH = OH / d; g.OW = OW / d;
-        g.ws = {x0 / d, y0 / d, (ww / d) / (double)g.OW, (wh / d) / (double)g.OH};
-    }
-    for (int p = 0; p < 3; ++p) {
-        const I420Geom& g = ia.g[p != 0];
-        const bool aligned = (((size_t)out + ia.out_off[p]) & 3) == 0 && (N == 1 || (ia.out_frame & 3) == 0);
-        ia.px4[p] = (p < planes && remap_vec4_enabled() && g.OW % 4 == 0 && aligned) ? 1 : 0;
-        if (p < planes && (ia.px4[p] ? g.OW / 4 : g.OW) > items) items = ia.px4[p] ? g.OW / 4 : g.OW;
-    }
-    const int threads = items >= 256 ? 256 : ((items + 63) & ~63);       // whole waves, a row segment each
-    const dim3 grid(cdiv(items, threads), ia.g[0].OH + (planes == 3 ? 2 * ia.g[1].OH : 0), N);
-    // algorithmic bytes: the window of every plane gathered once, the output written once, the two small maps
-    const double cf = planes == 3 ? 1.5 : 1.0, bytes = (double)N * ((wh * ww + (double)OH * OW) * cf + 8.0 * h * w);
-    const bool rec = prof && prof->begin(st);
-    remap_i420_kernel<<<grid, threads, 0, st>>>(src, ia, workspace, out, black_count);
-    if (rec) prof->end(st, PK_KERNEL_REMAP_I420, 0.0, bytes);
-    SN_LAUNCH_CHECK("remap_i420_kernel");
+    remap_cubic_weights_kernel<<<4, 256, 0, st>>>(out_dev);
+    SN_LAUNCH_CHECK("remap_cubic_weights_kernel");
     return STABNET_OK;
 }
 

@@ -327,12 +327,17 @@ class ClipPipeline:
 
     A stream with enable_scene_cut(): the detector's launches and the predicated reseed come with stream._enqueue inside every slot's
     graph, its state advancing in frame order on the run stream; the frame's 8 bytes {flag, D} are copied into the slot inside the
-    graph and downloaded with the slot's other outputs: the result carries "scene_cut" (0 / 1) and "scene_dist" (D; d = D / (2*H*W))."""
+    graph and downloaded with the slot's other outputs: the result carries "scene_cut" (0 / 1) and "scene_dist" (D; d = D / (2*H*W)).
+
+    interp="cubic": wherever the slot's graph calls the remap, it calls stabnet_warp_rev_bundle2_cubic (cv2.remap's INTER_CUBIC, 16 taps)
+    with the same frame, maps, window and coverage count; the default "linear" is the reference's INTER_LINEAR."""
 
     def __init__(self, stream: StabNetStream, colour: bool = True, slots: int = 3, rate: int = 4, jpeg=None, ingest=None,
-                 output: str = "network", window=None, fill=None, decoder=None):
+                 output: str = "network", window=None, fill=None, decoder=None, interp: str = "linear"):
         if stream.S != 1:
             raise _lib.StabnetError("ClipPipeline: one video stream per pipeline")
+        from .warp import check_interp
+        self.cubic = check_interp(interp, "ClipPipeline")
         if slots < 2:
             raise _lib.StabnetError("ClipPipeline: slots must be >= 2")
         if output not in ("network", "source"):
@@ -473,15 +478,28 @@ class ClipPipeline:
                           ptr(self.fill_state), ptr(self.d_win[k]), ptr(self.d_stats[k]), ptr(self.remap_ws), stream_ptr(self.dev),
                           device=self.dev)
                 entry, win = entry + "_dev", ptr(self.d_win[k])
-            _lib.call(entry, ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
-                      win, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
-                      device=self.dev)
+            if self.cubic:
+                _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
+                          2 if self.adaptive else 1, win, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0,
+                          stream_ptr(self.dev), 0, device=self.dev)
+            else:
+                _lib.call(entry, ptr(frame), 1, sh, sw, C, sw * C, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
+                          win, sh, sw, ptr(self.d_warp[k]), ptr(self.all_black_win), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
+                          device=self.dev)
         elif self.src_out:
             # the raw frame in the upload slot, warped at its own size by the network-size maps; coverage counted on the way
             ing = self.ingest
-            _lib.call("stabnet_warp_rev_bundle2_src", ptr(self.d_u8[k]), 1, ing.sh, ing.sw, ing.C, ing.sw * ing.C, ptr(st.x_map), ptr(st.y_map),
-                      H, W, self.rate, ptr(self.d_warp[k]), ptr(self.all_black_src), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0,
-                      device=self.dev)
+            if self.cubic:
+                _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(self.d_u8[k]), 1, ing.sh, ing.sw, ing.C, ing.sw * ing.C, ptr(st.x_map),
+                          ptr(st.y_map), H, W, self.rate, 0, None, ing.sh, ing.sw, ptr(self.d_warp[k]), ptr(self.all_black_src),
+                          ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0, device=self.dev)
+            else:
+                _lib.call("stabnet_warp_rev_bundle2_src", ptr(self.d_u8[k]), 1, ing.sh, ing.sw, ing.C, ing.sw * ing.C, ptr(st.x_map),
+                          ptr(st.y_map), H, W, self.rate, ptr(self.d_warp[k]), ptr(self.all_black_src), ptr(self.remap_ws), 0, 0,
+                          stream_ptr(self.dev), 0, device=self.dev)
+        elif self.colour and self.cubic:
+            _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(self.d_bgr[k]), 1, H, W, 3, W * 3, ptr(st.x_map), ptr(st.y_map), H, W, self.rate,
+                      0, None, H, W, ptr(self.d_warp[k]), None, ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), 0, device=self.dev)
         elif self.colour:
             _lib.call("stabnet_warp_rev_bundle2", ptr(self.d_bgr[k]), ptr(st.x_map), ptr(st.y_map), 1, H, W, 3, self.rate,
                       ptr(self.d_warp[k]), ptr(self.remap_ws), 0, 0, stream_ptr(self.dev), device=self.dev)

@@ -102,8 +102,21 @@ def interpolate(im: torch.Tensor, x: torch.Tensor, y: torch.Tensor, out_size=Non
     return out
 
 
-def warpRevBundle2(img: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, return_maps: bool = False):
-    """deploy_bundle.py:136-146 on the device.  img uint8 [N,H,W,3] (or [H,W,3]); x_map, y_map [N,H,W(,1)] normalised."""
+INTERPS = ("linear", "cubic")
+
+
+def check_interp(interp, what):
+    """interp: "linear" (cv2.INTER_LINEAR, the reference's) or "cubic" (cv2.INTER_CUBIC: 16 taps, csrc/remap.hip remap_cubic_kernel)."""
+    if interp not in INTERPS:
+        raise _lib.StabnetError("%s: interp must be one of %s, got %r" % (what, list(INTERPS), interp))
+    return interp == "cubic"
+
+
+def warpRevBundle2(img: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, return_maps: bool = False,
+                   interp: str = "linear"):
+    """deploy_bundle.py:136-146 on the device.  img uint8 [N,H,W,3] (or [H,W,3]); x_map, y_map [N,H,W(,1)] normalised.
+    interp="cubic": cv2.remap's INTER_CUBIC in place of INTER_LINEAR (stabnet_warp_rev_bundle2_cubic at the network's own size)."""
+    cubic = check_interp(interp, "warpRevBundle2")
     squeeze = img.dim() == 3
     if squeeze:
         img = img[None]
@@ -117,6 +130,12 @@ def warpRevBundle2(img: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, 
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=img.device)
     px = empty((N, H, W), xm) if return_maps else None
     py = empty((N, H, W), xm) if return_maps else None
+    if cubic:
+        _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(img), N, H, W, C, W * C, ptr(xm), ptr(ym), H, W, int(rate), 0, None, H, W, ptr(out), None,
+                  ptr(ws), ptr(px), ptr(py), stream_ptr(img.device), 0, device=img.device)
+        if squeeze:
+            out = out[0]
+        return (out, px, py) if return_maps else out
     _lib.call("stabnet_warp_rev_bundle2", ptr(img), ptr(xm), ptr(ym), N, H, W, C, rate, ptr(out), ptr(ws), ptr(px), ptr(py),
               stream_ptr(img.device), device=img.device)
     if squeeze:
@@ -178,13 +197,15 @@ def _check_out_and_count(out, black_count, N, OH, OW, C, dev, what):
 
 
 def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, rate: int = 4, black_count: torch.Tensor = None,
-                       out: torch.Tensor = None, return_maps: bool = False, prof=None):
+                       out: torch.Tensor = None, return_maps: bool = False, prof=None, interp: str = "linear"):
     """warpRevBundle2 at SOURCE resolution (csrc/remap.hip, stabnet_warp_rev_bundle2_src): the frame as read -- uint8 [N,SH,SW,C] /
     [SH,SW,C] / [SH,SW], any size, rows may be strided -- remapped by the network-size maps x_map, y_map [N,H,W(,1)] / [H,W].
     -> uint8 of src_u8's shape (with return_maps: (out, px, py), the float32 [N,SH,SW] source-pixel coordinates).
     black_count: optional int32 [N,SH,SW] (or [SH,SW] for one frame), += 1 where the frame does not cover the pixel -- what
-    max_inscribed_rect reads.  out: optional contiguous uint8 tensor of the result's size.  Nothing synchronises."""
+    max_inscribed_rect reads.  out: optional contiguous uint8 tensor of the result's size.  interp: "linear" or "cubic" (INTER_CUBIC,
+    stabnet_warp_rev_bundle2_cubic; coordinates and black_count are the same).  Nothing synchronises."""
     what = "warpRevBundle2_src"
+    cubic = check_interp(interp, what)
     u8, stride, shape = _check_src_u8(src_u8, what)
     N, SH, SW, C = u8.shape
     dev = u8.device
@@ -193,8 +214,12 @@ def warpRevBundle2_src(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
     px = empty((N, SH, SW), xm) if return_maps else None
     py = empty((N, SH, SW), xm) if return_maps else None
-    _lib.call("stabnet_warp_rev_bundle2_src", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), ptr(out), ptr(black_count),
-              ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    if cubic:
+        _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), 0, None, SH, SW, ptr(out),
+                  ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    else:
+        _lib.call("stabnet_warp_rev_bundle2_src", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), ptr(out), ptr(black_count),
+                  ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
     res = out.view(shape)
     return (res, px, py) if return_maps else res
 
@@ -233,15 +258,18 @@ def _check_window(window, what):
 
 
 def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, window, out_size=None, rate: int = 4,
-                       black_count: torch.Tensor = None, out: torch.Tensor = None, return_maps: bool = False, prof=None):
+                       black_count: torch.Tensor = None, out: torch.Tensor = None, return_maps: bool = False, prof=None,
+                       interp: str = "linear"):
     """warpRevBundle2_src through a WINDOW of the stabilised frame (csrc/remap.hip, stabnet_warp_rev_bundle2_win): crop and zoom in the
     one gather.  window = (y0, x0, wh, ww) in pixel-edge units of the stabilised frame at the source's size (the whole frame is
     (0, 0, SH, SW); ratio_window / fit_window make one); out_size = (OH, OW), default the source's size.  A float64 tensor [4] or [N,4]
     on the frames' device is a window in DEVICE memory (stabnet_warp_rev_bundle2_win_dev: the kernels load it when they run, so an
     earlier launch on the stream -- AdaptiveFill.update -- may have written it; values the host entry would refuse give the whole frame).
     -> uint8 [N,OH,OW,C] / [OH,OW,C] / [OH,OW] after src_u8's layout (with return_maps: (out, px, py), float32 [N,OH,OW]).
-    black_count: optional int32 [N,OH,OW], += 1 where the frame does not cover the OUTPUT pixel.  Nothing synchronises."""
+    black_count: optional int32 [N,OH,OW], += 1 where the frame does not cover the OUTPUT pixel.  interp: "linear" or "cubic"
+    (INTER_CUBIC, stabnet_warp_rev_bundle2_cubic with window_kind 1 / 2).  Nothing synchronises."""
     what = "warpRevBundle2_win"
+    cubic = check_interp(interp, what)
     u8, stride, shape = _check_src_u8(src_u8, what)
     N, SH, SW, C = u8.shape
     dev = u8.device
@@ -262,8 +290,13 @@ def warpRevBundle2_win(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.T
     ws = torch.empty(2 * N * (H // rate) * (W // rate), dtype=torch.float32, device=dev)
     px = empty((N, OH, OW), xm) if return_maps else None
     py = empty((N, OH, OW), xm) if return_maps else None
-    _lib.call(entry, ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, ptr(out),
-              ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    if cubic:
+        _lib.call("stabnet_warp_rev_bundle2_cubic", ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate),
+                  2 if entry.endswith("_dev") else 1, win, OH, OW, ptr(out), ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev),
+                  prof.handle if prof is not None else 0, device=dev)
+    else:
+        _lib.call(entry, ptr(u8), N, SH, SW, C, stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, ptr(out),
+                  ptr(black_count), ptr(ws), ptr(px), ptr(py), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
     res = out.view({2: (OH, OW), 3: (OH, OW, C), 4: (N, OH, OW, C)}[len(shape)])
     return (res, px, py) if return_maps else res
 
@@ -275,7 +308,7 @@ def i420_frame_bytes(SH: int, SW: int, planes: int = 3) -> int:
 
 def warpRevBundle2_i420(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.Tensor, size, planes: int = 3, window=None, out_size=None,
                         border_y: int = 0, rate: int = 4, black_count: torch.Tensor = None, out: torch.Tensor = None,
-                        workspace: torch.Tensor = None, prof=None):
+                        workspace: torch.Tensor = None, prof=None, interp: str = "linear"):
     """warpRevBundle2_win of planar YUV 4:2:0 frames as a Y4M stream carries them (csrc/remap.hip, stabnet_warp_rev_bundle2_i420): no
     colour conversion, the Y plane and the two half-size chroma planes are warped as the single-channel images they are, in one gather
     launch.  src_u8: uint8 on the GPU, [N, B] or [B] with B >= the frame's bytes (i420_frame_bytes(SH, SW, planes)): per frame Y [SH,SW],
@@ -284,8 +317,10 @@ def warpRevBundle2_i420(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.
     A tap outside a plane reads border_y (Y; 16 for a limited-range stream) or 128 (U, V).  black_count: optional int32 [N,OH,OW], += 1
     where the frame does not cover the luma output pixel.  out: optional contiguous uint8 tensor of N * i420_frame_bytes(OH, OW, planes)
     elements; workspace: optional float32 tensor of 2*N*(H//rate)*(W//rate) elements.  With both given nothing allocates, and nothing
-    ever synchronises.  -> uint8 [N, bytes] ([bytes] for a 1-D source)."""
+    ever synchronises.  interp: "linear" or "cubic" (INTER_CUBIC on every plane, stabnet_warp_rev_bundle2_i420_cubic).
+    -> uint8 [N, bytes] ([bytes] for a 1-D source)."""
     what = "warpRevBundle2_i420"
+    cubic = check_interp(interp, what)
     if not isinstance(src_u8, torch.Tensor) or not src_u8.is_cuda:
         raise _lib.StabnetError("%s: expected a uint8 tensor on the GPU (there is no CPU fallback)" % what)
     if src_u8.dtype != torch.uint8:
@@ -322,8 +357,9 @@ def warpRevBundle2_i420(src_u8: torch.Tensor, x_map: torch.Tensor, y_map: torch.
     elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.float32 or workspace.numel() < n_ws \
             or not workspace.is_contiguous():
         raise _lib.StabnetError("%s: workspace must be a contiguous float32 tensor of >= %d elements on %s" % (what, n_ws, dev))
-    _lib.call("stabnet_warp_rev_bundle2_i420", ptr(u8), N, SH, SW, int(planes), stride, ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW,
-              int(border_y), ptr(out), ptr(black_count), ptr(workspace), stream_ptr(dev), prof.handle if prof is not None else 0, device=dev)
+    _lib.call("stabnet_warp_rev_bundle2_i420_cubic" if cubic else "stabnet_warp_rev_bundle2_i420", ptr(u8), N, SH, SW, int(planes), stride,
+              ptr(xm), ptr(ym), H, W, int(rate), win, OH, OW, int(border_y), ptr(out), ptr(black_count), ptr(workspace), stream_ptr(dev),
+              prof.handle if prof is not None else 0, device=dev)
     return out.view(obytes) if flat else out.view(N, obytes)
 
 

@@ -59,6 +59,11 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     equals a fresh run that starts there.  Works in the serial loop, with --pipeline and with --y4m-in; <name>_scenes.json holds the
     cuts and d per frame, the Y4M report scene_cuts; --fill history empties its canvas at a cut and --score leaves the pair across a
     cut out of the stability path.  Off by default; without it nothing differs.
+  * --interp cubic: every colour, grey or planar frame that is kept is gathered with cv2.remap's INTER_CUBIC (16 taps, OpenCV's fixed-point
+    weights; csrc/remap.hip, stabnet_warp_rev_bundle2_cubic / _i420_cubic) instead of INTER_LINEAR: a sharper picture from the same maps,
+    the same coordinates and the same coverage counts.  In the serial loop, with --pipeline, with every --fill mode and with --y4m-in;
+    --fill adaptive then keeps one more pixel of margin (margin_q = 8 + 32) so that no tap of the window leaves the frame, and --fill
+    history composes the cubic frame.  The JSON reports record "interp".  The default, linear, is the reference's and changes nothing.
   * --before-ch is parsed and ignored exactly as in the reference (deploy_bundle.py:15,41): the ring depth is
     max(indices[1:]) = 32 and six frames are sampled at lags 1,2,4,8,16,32.
 """
@@ -144,6 +149,9 @@ def build_parser():
                         'with the first frame of the new scene (stabnet_ring_reseed_if); writes <name>_scenes.json')
     p.add_argument('--scene-gap', type=int, default=None, metavar='N',
                    help='--scene-cut: no cut is flagged within N frames of the last one or of the start, N >= 0 (default 8)')
+    p.add_argument('--interp', default='linear', choices=['linear', 'cubic'],
+                   help='how the kept frame is gathered from the source: linear (cv2.INTER_LINEAR, the reference\'s) or cubic '
+                        '(cv2.INTER_CUBIC, 16 taps: sharper; stabnet_warp_rev_bundle2_cubic); the maps, the network and the ingest are unchanged')
     p.add_argument('--fps', type=float, default=30.0, help='frame rate written to the .avi (taken from the input when that is an .avi)')
     p.add_argument('--y4m-in', default=None, metavar='PATH|-',
                    help='stabilise a YUV4MPEG2 stream (8-bit 4:2:0 or mono) from this file, or from stdin with -, frame by frame in bounded '
@@ -293,7 +301,7 @@ def write_scenes_json(path, args, scene_log, say=print):
 
 
 def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, enc=None, ing=None, black_src=None,
-               window=None, black_win=None, adaptive=None, fill_log=None, mosaic=None, fill_frames=None, scene_log=None):
+               window=None, black_win=None, adaptive=None, fill_log=None, mosaic=None, fill_frames=None, scene_log=None, interp='linear'):
     """The loop as the reference writes it (deploy_bundle.py:244-342): one frame at a time, the host waiting for each step;
     fps = frames / time inside the step, as the reference prints it (:285-289).  ing (--ingest device): the raw uint8 frame is
     uploaded and converted on the GPU inside the step.  black_src (--output-size source; int32 [src_h, src_w] on the device): the
@@ -303,7 +311,7 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
     history; a mosaic.Mosaic): the kept colour frame is remapped with its coordinates written out, composed over the canvas of the
     earlier frames, and the canvas goes to fill_frames; every other output is the one of a run without it.  scene_log (--scene-cut; the
     stream has enable_scene_cut()): gets (frame, cut, d) per frame from the step's device flag, read outside the timed part; at a cut the
-    mosaic's canvas is emptied before the frame is composed."""
+    mosaic's canvas is emptied before the frame is composed.  interp (--interp): the taps of every remap of a kept frame."""
     import torch
     from stabnet_amd import warp
     tot_time, length = 0.0, 0
@@ -332,28 +340,28 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
             # the window of the stabilised frame in the one gather: of the frame as read, or of the cv2-resized colour frame
             frame = cur if black_src is not None else ing.colour(cur)[0]
             win = window if adaptive is None else adaptive.update(r['x_map'], r['y_map'])     # (on the device: read there by the remap)
-            colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], win, black_count=black_win).cpu().numpy())
+            colour_out.append(warp.warpRevBundle2_win(frame, r['x_map'], r['y_map'], win, black_count=black_win, interp=interp).cpu().numpy())
             if adaptive is not None:
                 fill_log.append((adaptive.window[0].cpu().numpy(), adaptive.stats[0].cpu().numpy()))
         elif mosaic is not None:
             # the same remap as below with px_out / py_out written (the same output bytes), then the composite over the earlier frames
             if black_src is not None:
-                kept_frame, px, py = warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src, return_maps=True)
+                kept_frame, px, py = warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src, return_maps=True, interp=interp)
             else:
-                kept_frame, px, py = warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map'], return_maps=True)
+                kept_frame, px, py = warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map'], return_maps=True, interp=interp)
             colour_out.append(kept_frame.cpu().numpy())
             canvas = mosaic.update(kept_frame.reshape(1, mosaic.SH, mosaic.SW, 3), px, py, r['output'][..., 0], r['black_pix'])
             fill_frames.append(canvas[0].cpu().numpy())
         elif black_src is not None:
             # where the reference resizes the colour frame down and warps it (deploy_bundle.py:303): the frame as read, warped as it is
-            colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src).cpu().numpy())
+            colour_out.append(warp.warpRevBundle2_src(cur, r['x_map'], r['y_map'], black_count=black_src, interp=interp).cpu().numpy())
         elif ing is not None and ing.C == 3:
             # cv2.resize of the colour frame (deploy_bundle.py:303), then warpRevBundle2, both on the device
-            colour_out.append(warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map']).cpu().numpy())
+            colour_out.append(warp.warpRevBundle2(ing.colour(cur)[0], r['x_map'], r['y_map'], interp=interp).cpu().numpy())
         elif ing is None and is_colour(clip[t], H, W):
             # warpRevBundle2 (deploy_bundle.py:136-146,303) on the device: colour frame remapped by the smoothed maps
             bgr = torch.from_numpy(np.ascontiguousarray(clip[t], dtype=np.uint8)).to(dev)
-            colour_out.append(warp.warpRevBundle2(bgr, r['x_map'], r['y_map']).cpu().numpy())
+            colour_out.append(warp.warpRevBundle2(bgr, r['x_map'], r['y_map'], interp=interp).cpu().numpy())
         net_output = ((r['output'][0, :, :, 0].cpu().numpy() + 0.5) * 255).clip(0, 255).astype(np.uint8)
         frames_out.append(net_output)
         if jpeg_sink is not None:                                             # the frame that is kept, compressed on the device
@@ -369,7 +377,7 @@ def run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, bl
 
 
 def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, jpeg_sink=None, jpeg=None, ing=None, source=False,
-                  window=None, fill=None, fill_log=None, scene_log=None):
+                  window=None, fill=None, fill_log=None, scene_log=None, interp='linear'):
     """--pipeline: the same frames through stabnet_amd.deploy.ClipPipeline (upload / frame / download of neighbouring frames on
     three HIP streams).  Same output bytes; fps = frames / wall time of the whole loop, host conversion and copies included.
     window='adaptive' with fill=dict(r_min, up, margin_q): the per-frame window of --fill adaptive; fill_log gets (window, stats).
@@ -403,12 +411,12 @@ def run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blac
     black_src = black_win = None
     if ing is not None:                                                       # the raw clip: one uint8 upload per frame, nothing converted here
         pipe = ClipPipeline(stream, colour=colour, jpeg=jpeg, ingest=ing, output='source' if source else 'network', window=window,
-                            fill=fill, decoder=getattr(clip, 'decoder', None))
+                            fill=fill, decoder=getattr(clip, 'decoder', None), interp=interp)
         pipe.run(clip, sink=sink, maps=True)
         black_src = pipe.all_black_src if source else None
         black_win = pipe.all_black_win if window is not None else None
     else:
-        ClipPipeline(stream, colour=colour, jpeg=jpeg).run(Grey(), clip if colour else None, sink=sink, maps=True)
+        ClipPipeline(stream, colour=colour, jpeg=jpeg, interp=interp).run(Grey(), clip if colour else None, sink=sink, maps=True)
     tot_time = time.time() - start
     if frames_out:
         print('fps={}'.format(len(frames_out) / tot_time))
@@ -431,25 +439,25 @@ def uncovered_per_frame(frame0, xmaps, ymaps, window, out_size, dev):
     return per
 
 
-def write_fill_json(stem, mode, window, rect, out_size, uncovered, pixels_ever):
+def write_fill_json(stem, mode, window, rect, out_size, uncovered, pixels_ever, interp='linear'):
     import json
     if pixels_ever is not None:
         uncovered = dict(uncovered, pixels_ever_uncovered=pixels_ever)
     with open(stem + '_fill_window.json', 'w') as f:
         json.dump({'mode': mode, 'window': [float(v) for v in window], 'rect': [int(v) for v in rect] if rect else None,
-                   'output_size': [int(out_size[0]), int(out_size[1])], 'uncovered': uncovered}, f, indent=1)
+                   'output_size': [int(out_size[0]), int(out_size[1])], 'interp': interp, 'uncovered': uncovered}, f, indent=1)
         f.write('\n')
     print('wrote', stem + '_fill_window.json')
 
 
-def write_fill_adaptive_json(stem, params, fill_log, nodes, out_size, uncovered, pixels_ever):
+def write_fill_adaptive_json(stem, params, fill_log, nodes, out_size, uncovered, pixels_ever, interp='linear'):
     """<name>_fill_window.json of --fill adaptive: the parameters, and per frame the window the GPU chose, r_safe (the largest ratio its
     rule proves free of uncovered pixels; <= 0: none) and the number of bad nodes.  held_at_min: the frames whose r_safe lay below
     r_min -- cut at r_min, the only ones that may show uncovered pixels."""
     import json
     r_safe = [1.0 if int(st[0]) >= nodes else float(int(st[0])) / float(nodes) for _, st in fill_log]
     with open(stem + '_fill_window.json', 'w') as f:
-        json.dump({'mode': 'adaptive', 'params': params, 'output_size': [int(out_size[0]), int(out_size[1])],
+        json.dump({'mode': 'adaptive', 'params': params, 'output_size': [int(out_size[0]), int(out_size[1])], 'interp': interp,
                    'windows': [[float(v) for v in w] for w, _ in fill_log], 'r_safe': r_safe,
                    'bad_nodes': [int(st[1]) for _, st in fill_log],
                    'held_at_min': sum(1 for r in r_safe if r < params['r_min']),
@@ -523,7 +531,7 @@ def fill_second_pass(clip, ing, source, xmaps, ymaps, window, out_size, dev, ste
         frame = raw if source else ing.colour(raw)[0]
         xm, ym = torch.from_numpy(xmaps[t - 1]).to(dev), torch.from_numpy(ymaps[t - 1]).to(dev)
         cnt.zero_()
-        out = warp.warpRevBundle2_win(frame, xm, ym, window, (oh, ow), black_count=cnt)
+        out = warp.warpRevBundle2_win(frame, xm, ym, window, (oh, ow), black_count=cnt, interp=args.interp)
         if writer is not None:
             writer.write(enc.encode_bytes(out)[0])
         filled.append(out.cpu().numpy())
@@ -539,7 +547,7 @@ def fill_second_pass(clip, ing, source, xmaps, ymaps, window, out_size, dev, ste
     return per
 
 
-def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem, cuts=None):
+def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem, cuts=None, interp='linear'):
     """--score: frames 1.. of the clip as ingested (the network's grey input on the 0..255 scale) against the kept frames of the same
     instants: the network's grey output, or (filled) the window that was written, brought to the network's size by the ingest stage.
     cuts (--scene-cut): the frames of the CLIP at which a new scene starts; kept frame k is the clip's frame k + 1."""
@@ -567,6 +575,7 @@ def score_outputs(clip, frames_out, colour_out, ing, filled, H, W, dev, stem, cu
         what = 'the network\'s grey output'
     res = metrics.score_clip(unstable, stable, cuts=None if cuts is None else [c - 1 for c in cuts if c - 1 < n])
     res['stable_frames'] = what
+    res['interp'] = interp
     with open(stem + '_score.json', 'w') as f:
         json.dump(res, f, indent=1)
         f.write('\n')
@@ -620,7 +629,7 @@ def run_y4m(args, rd, stream, H, W, dev, out_file):
             start = time.time()
             r = stream.step_u8(y_view, ing)
             warp.warpRevBundle2_i420(dev_in, r['x_map'], r['y_map'], (SH, SW), planes, window=window, border_y=border_y, black_count=black,
-                                     out=dev_out, workspace=ws)
+                                     out=dev_out, workspace=ws, interp=args.interp)
             torch.cuda.synchronize()
             tot_time += time.time() - start
             if scene_cuts is not None and int(r['scene_cut'][0]):
@@ -638,7 +647,7 @@ def run_y4m(args, rd, stream, H, W, dev, out_file):
             wr.close()
     if wr is not None and wr.broken:
         say('note: the consumer of --y4m-out closed the stream after %d frames' % wr.frames_written)
-    report = {'input': rd.header_fields(), 'network_size': [H, W], 'colour_range': rd.colour_range, 'border_y': border_y,
+    report = {'input': rd.header_fields(), 'network_size': [H, W], 'colour_range': rd.colour_range, 'border_y': border_y, 'interp': args.interp,
               'window': [float(v) for v in window] if window is not None else None, 'frames': length + 1,
               'pixels_ever_uncovered': int((black > 0).sum().item()), 'max_uncovered_count': int(black.max().item())}
     if scene_cuts is not None:
@@ -814,7 +823,8 @@ def main():
                 if args.score:
                     print('note: --score scores the online frames (the network\'s grey output) as without --fill history, not the filled ones')
             elif fill == 'adaptive':
-                fill_params = dict(r_min=args.fill_min, up=args.fill_up, margin_q=8)
+                # (cubic: one more pixel, so that no 4x4 tap of the window leaves the frame: no darkened rim)
+                fill_params = dict(r_min=args.fill_min, up=args.fill_up, margin_q=8 + 32 if args.interp == 'cubic' else 8)
                 black_win = torch.zeros(kept, dtype=torch.int32, device=dev)
                 if not args.pipeline:
                     adaptive = warp.AdaptiveFill(1, kept[0], kept[1], device=dev, **fill_params)
@@ -845,12 +855,13 @@ def main():
             if args.pipeline:
                 length, tot_time, pipe_black, pipe_win = run_pipelined(stream, clip, H, W, frames_out, colour_out, xmaps, ymaps, blacks, sink,
                                                                        jpeg_options(args) if args.mjpg else None, ing, source,
-                                                                       'adaptive' if fill_params else window, fill_params, fill_log, scene_log)
+                                                                       'adaptive' if fill_params else window, fill_params, fill_log, scene_log,
+                                                                       args.interp)
                 black_src = pipe_black if source else None
                 black_win = pipe_win if (window is not None or fill_params) else None
             else:
                 length, tot_time = run_serial(stream, clip, H, W, dev, frames_out, colour_out, xmaps, ymaps, blacks, sink, enc, ing, black_src,
-                                              window, black_win, adaptive, fill_log, mosaic, fill_frames, scene_log)
+                                              window, black_win, adaptive, fill_log, mosaic, fill_frames, scene_log, args.interp)
         except Exception:
             traceback.print_exc()                    # the reference swallows per-video errors and still finalises
         finally:
@@ -890,7 +901,7 @@ def main():
                         per = uncovered_per_frame(f0, xmaps, ymaps, window, kept, dev)
                         if sum(per) != int(black_win.sum().item()):
                             print('WARNING: the coverage counted online (%d) is not the sum over the frames (%d)' % (int(black_win.sum().item()), sum(per)))
-                        write_fill_json(stem, 'ratio', window, None, kept, fill_report(per, kept), int((black_win > 0).sum().item()))
+                        write_fill_json(stem, 'ratio', window, None, kept, fill_report(per, kept), int((black_win > 0).sum().item()), args.interp)
                         if tot_time > 0:
                             print('fps={}'.format(length / tot_time))
                     elif fill_params and colour_out:                      # --fill adaptive: each frame recounted through its own window
@@ -899,7 +910,7 @@ def main():
                         if sum(per) != int(black_win.sum().item()):
                             print('WARNING: the coverage counted online (%d) is not the sum over the frames (%d)' % (int(black_win.sum().item()), sum(per)))
                         write_fill_adaptive_json(stem, fill_params, fill_log, (H // 4) * (W // 4), kept, fill_report(per, kept),
-                                                 int((black_win > 0).sum().item()))
+                                                 int((black_win > 0).sum().item()), args.interp)
                         if tot_time > 0:
                             print('fps={}'.format(length / tot_time))
                     elif mosaic is not None and fill_frames:
@@ -914,13 +925,13 @@ def main():
                             print('fill: window (y0, x0, wh, ww) = %s of the stabilised frame inside the rectangle %s, at %dx%d'
                                   % (list(fwin), ans, kept[1], kept[0]))
                             per = fill_second_pass(clip, ing, source, xmaps, ymaps, fwin, kept, dev, stem, args, fps, first)
-                            write_fill_json(stem, 'auto', fwin, ans, kept, fill_report(per, kept), None)
+                            write_fill_json(stem, 'auto', fwin, ans, kept, fill_report(per, kept), None, args.interp)
                 except Exception:
                     traceback.print_exc()
                 if args.score:
                     try:
                         score_outputs(clip, frames_out, colour_out, ing, window is not None or bool(fill_params), H, W, dev, stem,
-                                      None if scene_log is None else [t for t, cut, _ in scene_log if cut])
+                                      None if scene_log is None else [t for t, cut, _ in scene_log if cut], interp=args.interp)
                     except Exception:
                         traceback.print_exc()
 

@@ -627,6 +627,38 @@ int stabnet_warp_rev_bundle2_i420(const unsigned char* src, int N, int SH, int S
                                   const double* window, int OH, int OW, int border_y,
                                   unsigned char* out, int* black_count, float* workspace, void* stream, void* prof);
 
+/* The remaps above with cv2.remap's INTER_CUBIC in place of INTER_LINEAR (remap_cubic_kernel<PX, KIND>; tests/remap_cubic_model.py).
+ * Coordinates, their quantisation to 1/32 px (qx, qy), coverage, px_out/py_out, the refusals and the choice between the one- and the
+ * four-pixel kernel are the bilinear entries'; only the taps and the blend differ.  With ix = sat16(qx >> 5), fx = qx & 31 (same in y):
+ *   taps   rows iy - 1 .. iy + 2, columns ix - 1 .. ix + 2; a tap outside the frame reads 0 (BORDER_CONSTANT)
+ *   1-D    c[0..3] = interpolateCubic(f / 32), A = -0.75, float32, left to right, not contracted
+ *   w      [k1][k2] = saturate_cast<short>(rint(float32(cy[k1] * cx[k2]) * 32768)); an entry whose 16 taps do not sum to 32768 is
+ *          repaired as initInterTab2D does: over taps k1, k2 in {2, 3} in row order the minimum (strict <) or else the maximum
+ *          (strict >), both starting at [2][2]; diff = sum - 32768 < 0 is taken from the maximum, otherwise from the minimum
+ *   out    clamp((sum(v * w) + 16384) >> 15, 0, 255)      int32 accumulator: sum |w| <= 61952
+ * The kernels read the 1024 x 16 int16 table as a constant of the code object, compiled from this rule (no upload, no state per
+ * device).  Not separable: a two-pass form rounds differently.  window_kind 0: the whole frame at its own size (window not read, OH, OW must equal SH, SW; with SH, SW == H, W this is
+ * the network-size remap), 1: window = {y0, x0, wh, ww} in HOST memory as _win takes it, 2: window double [N,4] in DEVICE memory as
+ * _win_dev takes it (values _win would refuse give the whole frame).  Two launches. */
+int stabnet_warp_rev_bundle2_cubic(const unsigned char* src, int N, int SH, int SW, int C, size_t row_stride_bytes,
+                                   const float* x_map, const float* y_map, int H, int W, int rate,
+                                   int window_kind, const double* window, int OH, int OW,
+                                   unsigned char* out, int* black_count, float* workspace,
+                                   float* px_out, float* py_out, void* stream, void* prof);
+
+/* stabnet_warp_rev_bundle2_i420 with the bicubic taps on every plane (remap_i420_kernel<true>): a tap outside a plane reads border_y
+ * (Y) or 128 (U, V); the weights sum to 32768, so that is cv2.remap's borderValue form.  Everything else as _i420. */
+int stabnet_warp_rev_bundle2_i420_cubic(const unsigned char* src, int N, int SH, int SW, int planes, size_t frame_stride_bytes,
+                                        const float* x_map, const float* y_map, int H, int W, int rate,
+                                        const double* window, int OH, int OW, int border_y,
+                                        unsigned char* out, int* black_count, float* workspace, void* stream, void* prof);
+
+/* The 1024 x 16 weights of the bicubic remap, entry fy * 32 + fx, tap k1 * 4 + k2, int16.  _table: built on the host by the function
+ * the kernels' table is compiled from, at run time (no GPU needed).  _weights_dev: out_dev in device memory, written by one launch,
+ * every phase exactly as the remap kernels obtain it (read from their table). */
+int stabnet_remap_cubic_table(short* out);
+int stabnet_remap_cubic_weights_dev(short* out_dev, void* stream);
+
 /* Adaptive borderless output: per stream, the largest centred window of the stabilised frame that is provably free of uncovered
  * pixels, rate-limited on the way back out (fill_window_kernel).  x_map, y_map [N,H,W] as the remap receives them; h = H / rate,
  * w = W / rate.  Node (a, b) of the h x w small maps is BAD when its own coordinate (the remap's arithmetic with all the weight on the
