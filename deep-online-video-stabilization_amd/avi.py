@@ -172,8 +172,8 @@ class AviMjpegReader:
         for i in range(len(self)):
             yield self.frame(i)
 
-    def device_clip(self, device="cuda:0"):
+    def device_clip(self, device="cuda:0", parallel: bool = False):
         """The same frames decoded on the device from jpeg(i), bit for bit what frame(i) gives where Pillow is built on libjpeg-turbo
         (mjpeg.DeviceClip; raises mjpeg.Unsupported for streams outside the device decoder's scope)."""
         from .mjpeg import DeviceClip
-        return DeviceClip(self, device)
+        return DeviceClip(self, device, parallel=parallel)

@@ -53,3 +53,8 @@ inline bool jd_geom(int H, int W, int C, int subsampling, JdGeom* g) {
     g->frame = g->croff + jd_align16((size_t)g->ch * g->cw);
     return true;
 }
+
+// mjpeg_decode.hip: the IDCT and colour launches behind any entropy back end (stages 2 and 3 of stabnet_mjpeg_decode); a STABNET_* code
+int mjpegd_launch_planes(const JdGeom& g, int H, int W, const unsigned char* in, size_t in_stride, int N, const short* coef,
+                         size_t coef_stride, unsigned char* wsb, unsigned char* out, size_t row_stride, size_t frame_stride, int stages,
+                         void* stream);

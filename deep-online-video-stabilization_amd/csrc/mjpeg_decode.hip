@@ -291,6 +291,16 @@ int stabnet_mjpeg_decode(const unsigned char* in, size_t in_stride, int N, int H
             mjpegd_entropy_kernel<JD_MODE_GREY><<<grid, 256, 0, st>>>(in, in_stride, H, W, g.nmcu, g.blob_max, cw, coef_stride, status);
         SN_LAUNCH_CHECK("mjpegd_entropy_kernel");
     }
+    return mjpegd_launch_planes(g, H, W, in, in_stride, N, coef, coef_stride, wsb, out, row_stride, frame_stride, stages, stream);
+}
+
+}  // extern "C"
+
+// The launches behind the entropy decoding (stages 2 and 3), for stabnet_mjpeg_decode and stabnet_mjpeg_decode_sync alike.  Defined
+// behind the entries: kernels are emitted in the order of their first use, and tools/isa_hash.py shows them unchanged that way.
+int mjpegd_launch_planes(const JdGeom& g, int H, int W, const unsigned char* in, size_t in_stride, int N, const short* coef, size_t coef_stride,
+                         unsigned char* wsb, unsigned char* out, size_t row_stride, size_t frame_stride, int stages, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (stages < 2) return STABNET_OK;
     {
         const dim3 grid(cdiv((long)g.nblk, 32), N);
@@ -315,5 +325,3 @@ int stabnet_mjpeg_decode(const unsigned char* in, size_t in_stride, int N, int H
     }
     return STABNET_OK;
 }
-
-}  // extern "C"

@@ -2,9 +2,13 @@
 // program of tests/mjpeg_decode_fuzz_main.cpp).  stabnet_mjpeg_parse reads the marker segments of one baseline stream, finds its
 // restart intervals (FF D0..D7 inside scan data is always a marker: a linear scan of bytes that are on the host anyway) and packs
 // what the kernels of mjpeg_decode.hip read into a blob (mjpeg_decode.h); stabnet_mjpeg_entropy_host decodes the coefficients on the
-// CPU with the routine the entropy kernel runs (jpeg_entropy.h), for streams without DRI: one interval, nothing to run in parallel.
+// CPU with the routine the entropy kernel runs (jpeg_entropy.h), for streams without DRI: one interval, one sequential decode.
+// stabnet_mjpeg_entropy_sync_host is the host twin of mjpeg_decode_sync.hip, which does decode such an interval in parallel: the
+// phases of jpeg_sync.h with the lanes in a loop, for tests (tests/mjpeg_sync_fuzz_main.cpp runs it under the sanitizers).
 #include <cstdint>
 #include <cstring>
+#include <vector>
+#include "jpeg_sync.h"
 #include "jpeg_tables.h"
 #include "mjpeg_decode.h"
 
@@ -239,6 +243,84 @@ int stabnet_mjpeg_entropy_host(const unsigned char* jpeg, size_t nbytes, const u
     }
     if (status) {
         stabnet_set_error("mjpeg_entropy_host: the scan does not decode (status %d: 1 data ran out, 2 no such code, 4 run past 63, 8 offsets)", status);
+        return -1;
+    }
+    return 0;
+}
+
+/* The phases of mjpeg_decode_sync.hip with the lanes in a loop: guess, rounds inside groups of kGroup chunks, one hand-over across
+ * the groups and the rounds again, verify, repair, scan, write.  See include/stabnet_hip.h. */
+int stabnet_mjpeg_entropy_sync_host(const unsigned char* jpeg, size_t nbytes, const unsigned char* blob, size_t blob_bytes, short* coef,
+                                    size_t coef_count, int chunk_bytes, int rounds, int* stats) {
+    constexpr int kGroup = 256;
+    if (!jpeg || !blob || !coef) { stabnet_set_error("mjpeg_entropy_sync_host: null pointer"); return -1; }
+    if (chunk_bytes < 1 || chunk_bytes > (1 << 20)) { stabnet_set_error("mjpeg_entropy_sync_host: chunk_bytes %d is not in 1..2^20", chunk_bytes); return -1; }
+    if (blob_bytes < kJdBlobStarts + 2 * sizeof(int) || ((uintptr_t)blob & 3)) { stabnet_set_error("mjpeg_entropy_sync_host: bad blob"); return -1; }
+    if (rounds < 0) rounds = kJsDefaultRounds;
+    JdBlobHead h;
+    memcpy(&h, blob, sizeof(h));
+    JdGeom g;
+    const int C = h.mode == JD_MODE_GREY ? 1 : 3;
+    if (h.magic != kJdMagic || h.mode < 0 || h.mode > 2 || !jd_geom(h.H, h.W, C, h.mode == JD_MODE_420 ? 420 : 444, &g) || h.nmcu != g.nmcu ||
+        (size_t)h.nbytes != nbytes) {
+        stabnet_set_error("mjpeg_entropy_sync_host: the blob is not stabnet_mjpeg_parse's for this stream");
+        return -1;
+    }
+    if (h.nint != 1 || h.restart_mcus != g.nmcu) {
+        stabnet_set_error("mjpeg_entropy_sync_host: the stream has %d restart intervals; this back end decodes streams of one (status 8)", h.nint);
+        return -1;
+    }
+    if (coef_count < g.nblk * 64) { stabnet_set_error("mjpeg_entropy_sync_host: %zu coefficients, the frame has %zu", coef_count, g.nblk * 64); return -1; }
+    memset(coef, 0, g.nblk * 64 * sizeof(short));
+    const JdHuff* huff = reinterpret_cast<const JdHuff*>(blob + kJdBlobHuff);
+    const int* starts = reinterpret_cast<const int*>(blob + kJdBlobStarts);
+    const long a = starts[0], b = (long)starts[1] - 2;
+    if (a < 0 || b < a || (size_t)b > nbytes) { stabnet_set_error("mjpeg_entropy_sync_host: the scan does not decode (status 8: offsets)"); return -1; }
+    const int nc = js_nchunks((int)a, (int)b, chunk_bytes);
+    std::vector<JsState> entry((size_t)nc), exits((size_t)nc), old;
+    std::vector<JsSum> sums((size_t)nc);
+    auto walk = [&](int c) {
+        js_walk<false>(jpeg, (int)b, js_limit(c, nc, (int)a, chunk_bytes), entry[c], huff, h.td, h.ta, h.mode, &exits[c], &sums[c], 0, 0, 0u, 0u,
+                       0u, nullptr, kZigzag);
+    };
+    for (int c = 0; c < nc; ++c) {                        // 1. guess
+        entry[c] = js_guess(jpeg, (int)a, (int)b, c, chunk_bytes);
+        walk(c);
+    }
+    for (int pass = 0; pass < (rounds > 0 ? 2 : 0); ++pass) {       // 2. synchronise: inside the groups, then once across them
+        for (int r = 0; r < rounds; ++r) {
+            old = exits;
+            bool any = false;
+            for (int c = 1; c < nc; ++c) {
+                if (c % kGroup == 0 && (pass == 0 || r > 0)) continue;
+                if (js_same(old[c - 1], entry[c])) continue;
+                entry[c] = old[c - 1];
+                walk(c);
+                any = true;
+            }
+            if (!any) break;
+        }
+    }
+    int repaired = 0;                                      // 3. verify and repair, left to right
+    for (int c = 1; c < nc; ++c) {
+        if (js_same(exits[c - 1], entry[c])) continue;
+        entry[c] = exits[c - 1];
+        walk(c);
+        ++repaired;
+    }
+    if (stats) { stats[0] = nc; stats[1] = nc - repaired; }
+    JsSum run = {0u, 0u, 0u, 0u};                          // 4. count, scan, write (the DC sums ride along: 5.)
+    int status = 0;
+    for (int c = 0; c < nc; ++c) {
+        JsState ex;
+        JsSum s;
+        status |= js_walk<true>(jpeg, (int)b, js_limit(c, nc, (int)a, chunk_bytes), entry[c], huff, h.td, h.ta, h.mode, &ex, &s, (long)run.cnt - 1,
+                                (long)g.nblk, run.dc0, run.dc1, run.dc2, coef, kZigzag);
+        js_add(run, s);
+    }
+    if ((size_t)run.cnt < g.nblk) status |= JD_ERR_DATA;
+    if (status) {
+        stabnet_set_error("mjpeg_entropy_sync_host: the scan does not decode (status %d: 1 data ran out, 2 no such code, 4 run past 63, 8 offsets)", status);
         return -1;
     }
     return 0;

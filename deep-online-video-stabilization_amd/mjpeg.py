@@ -134,14 +134,27 @@ class MjpegDecoder:
     are entropy-decoded on the device, one lane per interval.  host_entropy=True (the default for a decoder made from a stream
     without DRI, which is a single interval): the coefficients are decoded on the CPU by the same routine and uploaded instead; the
     IDCT and colour stages are the device's either way, so the pixels are the same.
+    parallel=True (opt-in; excludes host_entropy): the second entropy back end, for streams WITHOUT restart markers -- the slot holds
+    blob + bytes and the one interval is decoded on the device by self-synchronising parallel Huffman decoding
+    (csrc/mjpeg_decode_sync.hip: one lane per chunk of chunk_bytes, at most sync_rounds rounds of state hand-over, a sequential
+    repair of what is left); the same coefficients, hence the same pixels.  None for chunk_bytes / sync_rounds: the library's defaults.
     enqueue(...) only launches (capturable in a hipGraph); decode(...) also checks the status words, which synchronises."""
 
     def __init__(self, H: int, W: int, channels: int = 3, subsampling="420", device="cuda:0", batch: int = 1, host_entropy: bool = False,
-                 max_bytes=None):
+                 max_bytes=None, parallel: bool = False, chunk_bytes=None, sync_rounds=None):
         self.H, self.W, self.C = int(H), int(W), int(channels)
         self.subsampling = int(subsampling) if self.C == 3 else 0
         self.device = torch.device(device)
         self.host_entropy = bool(host_entropy)
+        self.parallel = bool(parallel)
+        if self.parallel and self.host_entropy:
+            raise _lib.StabnetError("MjpegDecoder: parallel=True decodes the entropy-coded bytes on the device; it excludes host_entropy=True")
+        if not self.parallel and (chunk_bytes is not None or sync_rounds is not None):
+            raise _lib.StabnetError("MjpegDecoder: chunk_bytes / sync_rounds belong to parallel=True")
+        self.chunk_bytes = 0 if chunk_bytes is None else int(chunk_bytes)
+        self.sync_rounds = -1 if sync_rounds is None else int(sync_rounds)
+        if self.parallel and (self.chunk_bytes < 0 or self.sync_rounds < -1):
+            raise _lib.StabnetError("MjpegDecoder: chunk_bytes %d / sync_rounds %d" % (self.chunk_bytes, self.sync_rounds))
         L = _lib.lib()
         self.blob_max = L.stabnet_mjpeg_decode_blob_bytes(self.H, self.W, self.C, self.subsampling)
         if self.blob_max == 0:
@@ -158,9 +171,13 @@ class MjpegDecoder:
         self._reserve(batch)
 
     @classmethod
-    def for_stream(cls, jpeg, device="cuda:0", batch: int = 1, host_entropy=None):
-        """A decoder for streams shaped like this one (raises Unsupported)."""
+    def for_stream(cls, jpeg, device="cuda:0", batch: int = 1, host_entropy=None, parallel=None, chunk_bytes=None, sync_rounds=None):
+        """A decoder for streams shaped like this one (raises Unsupported).  parallel=True: a stream without DRI gets the parallel
+        entropy back end; one with DRI keeps one lane per restart interval.  The default (None) is host_entropy for a stream without DRI."""
         i = parse(jpeg)
+        if parallel and i["restart"] == 0 and not host_entropy:
+            return cls(i["H"], i["W"], i["C"], i["subsampling"] or 420, device=device, batch=batch, parallel=True, chunk_bytes=chunk_bytes,
+                       sync_rounds=sync_rounds)
         return cls(i["H"], i["W"], i["C"], i["subsampling"] or 420, device=device, batch=batch,
                    host_entropy=(i["restart"] == 0) if host_entropy is None else host_entropy)
 
@@ -173,9 +190,15 @@ class MjpegDecoder:
         self.in_stride = in_stride or self.in_stride
         self.h_in = torch.zeros((n, self.in_stride), dtype=torch.uint8).pin_memory()
         self.d_in = torch.zeros((n, self.in_stride), dtype=torch.uint8, device=self.device)
-        ws = _lib.lib().stabnet_mjpeg_decode_workspace_bytes(n, self.H, self.W, self.C, self.subsampling)
+        if self.parallel:
+            ws = _lib.lib().stabnet_mjpeg_decode_sync_workspace_bytes(n, self.H, self.W, self.C, self.subsampling, self.in_stride, self.chunk_bytes)
+        else:
+            ws = _lib.lib().stabnet_mjpeg_decode_workspace_bytes(n, self.H, self.W, self.C, self.subsampling)
+        if ws == 0:
+            _lib.check(-1, "stabnet_mjpeg_decode%s_workspace_bytes" % ("_sync" if self.parallel else ""))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.sync_stats = torch.zeros((n, 2), dtype=torch.int32, device=self.device) if self.parallel else None
         self.out = torch.empty((n, self.H, self.W, self.C), dtype=torch.uint8, device=self.device)
         self._batch = n
 
@@ -198,6 +221,9 @@ class MjpegDecoder:
         used = self.slot_bytes(len(jpeg))
         if used > slot.numel():
             raise _lib.StabnetError("%s: %d bytes do not fit the slot of %d" % (what, used, slot.numel()))
+        if self.parallel and i["intervals"] != 1:
+            raise _lib.StabnetError("%s has %d restart intervals (DRI %d); the decoder was made with parallel=True for streams without "
+                                    "restart markers" % (what, i["intervals"], i["restart"]))
         if self.host_entropy:
             rc = _lib.lib().stabnet_mjpeg_entropy_host(jpeg, len(jpeg), base, i["blob_bytes"], base + self.blob_max, self.coef_count)
             if rc != 0:
@@ -209,7 +235,15 @@ class MjpegDecoder:
 
     def enqueue(self, d_in, n: int, out, status, stages: int = 3):
         """The launches alone, on the current stream: d_in uint8 [n, in_stride] as uploaded, out uint8 [n,H,W,C] (rows and frames at
-        its strides), status int32 [n]."""
+        its strides), status int32 [n].  parallel: the chunk statistics of the call land in sync_stats[:n] when d_in is the decoder's
+        own batch (otherwise they are not kept)."""
+        if self.parallel:
+            stats = self.sync_stats if d_in is self.d_in and n <= self.sync_stats.shape[0] else None
+            _lib.call("stabnet_mjpeg_decode_sync", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling, ptr(out),
+                      out.stride(1) if out is not None else 0, out.stride(0) if out is not None else 0, ptr(status), ptr(self.workspace),
+                      self.workspace.numel(), stages, self.chunk_bytes, self.sync_rounds, ptr(stats), stream_ptr(self.device),
+                      device=self.device)
+            return
         _lib.call("stabnet_mjpeg_decode", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling, int(self.host_entropy),
                   ptr(out), out.stride(1) if out is not None else 0, out.stride(0) if out is not None else 0, ptr(status),
                   ptr(self.workspace), self.workspace.numel(), stages, stream_ptr(self.device), device=self.device)
@@ -246,11 +280,12 @@ class DeviceClip:
     """The frames of an MJPG .avi (avi.AviMjpegReader) decoded on the device as they are asked for: what crosses PCIe per frame is the
     compressed frame.  device_frame(t) -> uint8 [H,W,3] BGR / [H,W] grey in the decoder's own buffer (valid until the next call):
     the tensor the ingest reads.  clip[t] is the same frame downloaded (NumPy), for the few places that want it on the host.
+    parallel=True: a clip without restart markers is entropy-decoded on the device too (MjpegDecoder parallel=True) instead of on the host.
     Raises Unsupported when the first frame is outside the decoder's scope."""
 
-    def __init__(self, reader, device="cuda:0"):
+    def __init__(self, reader, device="cuda:0", parallel: bool = False):
         self.reader = reader
-        self.decoder = MjpegDecoder.for_stream(reader.jpeg(0), device=device)
+        self.decoder = MjpegDecoder.for_stream(reader.jpeg(0), device=device, parallel=True if parallel else None)
 
     def __len__(self):
         return len(self.reader)

@@ -38,7 +38,9 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
   * --decode device: the frames of a Motion-JPEG .avi are not decoded up front with Pillow; per frame the compressed bytes and their
     parsed description are uploaded in one copy and decoded on the GPU (csrc/mjpeg_decode.hip: bit for bit libjpeg-turbo's pixels)
     into the buffer the ingest reads.  Implies --ingest device.  A clip the decoder does not take (progressive, 4:2:2 ...) is read
-    with Pillow as with --decode host, and a note says so.
+    with Pillow as with --decode host, and a note says so.  --entropy parallel: a clip without restart markers, whose coefficients
+    are otherwise decoded on the host and uploaded, is entropy-decoded on the GPU as well (csrc/mjpeg_decode_sync.hip); the same
+    pixels, the compressed bytes cross PCIe instead of the coefficients.
   * --score: after a clip, the kept stabilised frames are scored against the input frames, both at the network's size
     (stabnet_amd/metrics.py: corner tracks and a robust homography per frame pair on the GPU, then the literature's cropping ratio,
     distortion value and stability score); <name>_score.json is written and the three numbers are printed.  The stabilised frames
@@ -118,6 +120,11 @@ def build_parser():
     p.add_argument('--decode', default='host', choices=['host', 'device'],
                    help='where the frames of a Motion-JPEG .avi are decoded: host = Pillow, the whole clip up front; device = '
                         'stabnet_amd.mjpeg.MjpegDecoder, frame by frame on the GPU from the uploaded compressed bytes (implies --ingest device)')
+    p.add_argument('--entropy', default='auto', choices=['auto', 'parallel'],
+                   help='--decode device: how a clip WITHOUT restart markers (what OpenCV, ffmpeg and cameras write) is entropy-decoded: '
+                        'auto = on the host, the coefficients are uploaded; parallel = on the GPU from the uploaded compressed bytes, by '
+                        'self-synchronising parallel Huffman decoding (csrc/mjpeg_decode_sync.hip).  A clip with restart markers is '
+                        'decoded one lane per restart interval either way')
     p.add_argument('--gray-weights', default='cv3', choices=['cv3', 'cv4'],
                    help='--ingest device: fixed-point BGR2GRAY weights of OpenCV 3 (the reference\'s era) or OpenCV 4')
     p.add_argument('--output-size', default='network', choices=['network', 'source'],
@@ -190,6 +197,8 @@ def parse_args(argv=None):
             p.error('--scene-cut needs 0 < T <= 1, got %r' % (args.scene_cut,))
         if args.scene_gap < 0:
             p.error('--scene-gap needs N >= 0, got %r' % (args.scene_gap,))
+    if args.entropy != 'auto' and args.decode != 'device':
+        p.error('--entropy %s belongs to --decode device' % args.entropy)
     if args.decode == 'device':
         args.ingest = 'device'                                 # the decoded frame lies on the GPU: that is where it is converted
     if args.output_size == 'source' and args.ingest != 'device':
@@ -756,7 +765,7 @@ def main():
                     if args.decode == 'device':
                         from stabnet_amd.mjpeg import Unsupported
                         try:
-                            dclip = rd.device_clip(dev)
+                            dclip = rd.device_clip(dev, parallel=args.entropy == 'parallel')
                         except Unsupported as e:
                             print('note: --decode device: %s: %s; this clip is decoded on the host with Pillow' % (path, e))
                     if rd.fps > 0:
@@ -765,7 +774,8 @@ def main():
                         clips.append((name, dclip))
                         print('read %s: %d MJPG frames %dx%d at %.3f fps, decoded on the GPU frame by frame (%s)'
                               % (path, len(rd), rd.width, rd.height, rd.fps, 'coefficients from the host: the streams have no restart '
-                                 'intervals' if dclip.decoder.host_entropy else 'one lane per restart interval'))
+                                 'intervals' if dclip.decoder.host_entropy else ('parallel entropy decoding on the GPU: the streams have '
+                                 'no restart intervals' if dclip.decoder.parallel else 'one lane per restart interval')))
                         continue
                     clips.append((name, np.stack(list(rd.frames()))))
                     print('read %s: %d MJPG frames %dx%d at %.3f fps, decoded on the host with Pillow (outside the timed part)'

@@ -770,6 +770,30 @@ int stabnet_mjpeg_decode_layout(int H, int W, int C, int subsampling, size_t* la
 int stabnet_mjpeg_decode(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, int coef_uploaded,
                          unsigned char* out, size_t row_stride, size_t frame_stride, int* status, void* workspace, size_t workspace_bytes,
                          int stages, void* stream);
+/* The second entropy back end: streams WITHOUT restart markers (one interval: what OpenCV, ffmpeg and cameras write) decoded on the
+ * device from the uploaded bytes, in parallel, by self-synchronising Huffman decoding (csrc/jpeg_sync.h).  The interval's bytes are
+ * cut into chunks of chunk_bytes; one lane per chunk decodes from a guessed parse state (bit position, block of the MCU, zig-zag
+ * index), lanes hand their exit states to the chunk behind them for at most `rounds` rounds inside a workgroup and once across
+ * workgroups, and an entry state is accepted only if it is the exit of the accepted walk in front of it -- so what is accepted is the
+ * sequential decode; one lane per frame walks again whatever the rounds left unaccepted.  Per-chunk block counts and DC sums are
+ * scanned and a second walk writes the coefficients: exactly those of stabnet_mjpeg_entropy_host, hence the pixels of
+ * stabnet_mjpeg_decode.  stabnet_mjpeg_decode_sync takes the arguments of stabnet_mjpeg_decode without coef_uploaded (slot = blob |
+ * stream), plus chunk_bytes (0 = default; a multiple of 4 in 8..4096), rounds (-1 = default, 0 = repair only, at most 1024) and
+ * stats (NULL, or int32 [N][2] on the device: chunks, chunks accepted as the rounds left them -- the repair walked the others; 0 0 for a
+ * refused blob).  A frame whose
+ * blob has more than one interval gets status 8.  Blocks the stream codes beyond the frame's count are dropped, fewer give status 1.
+ * The workspace is stabnet_mjpeg_decode's followed by the chunk states: stabnet_mjpeg_decode_sync_workspace_bytes (0 = bad
+ * arguments).  One memset node and four launches (three with rounds = 0) in front of the IDCT and colour launches; the count is
+ * fixed at enqueue time and nothing allocates, synchronises or copies from the host.  stages -1, -2, -3 (for measurements: the
+ * coefficients are not complete) stop after the guess launch, after the hand-over, after the repair and scan.
+ * stabnet_mjpeg_entropy_sync_host: the same phases with the lanes in a loop on the CPU, for tests (chunk_bytes >= 1; stats NULL or
+ * int [2]); arguments and result as stabnet_mjpeg_entropy_host, -1 also for a blob of several intervals. */
+size_t stabnet_mjpeg_decode_sync_workspace_bytes(int N, int H, int W, int C, int subsampling, size_t in_stride, int chunk_bytes);
+int stabnet_mjpeg_decode_sync(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, unsigned char* out,
+                              size_t row_stride, size_t frame_stride, int* status, void* workspace, size_t workspace_bytes, int stages,
+                              int chunk_bytes, int rounds, int* stats, void* stream);
+int stabnet_mjpeg_entropy_sync_host(const unsigned char* jpeg, size_t nbytes, const unsigned char* blob, size_t blob_bytes, short* coef,
+                                    size_t coef_count, int chunk_bytes, int rounds, int* stats);                            /* host */
 
 /* ---- in front of the path: frame ingest (config.py:6-21 cvt_img2train; deploy_bundle.py:215,303 cv2.resize) ----
  * A uint8 frame as read from the video, of any size, to the network's grey input and the network-size colour frame.
