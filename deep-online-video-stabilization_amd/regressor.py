@@ -113,7 +113,21 @@ class Regressor:
         self._train = None                   # (plan, workspace, theta) of the is_training=True branch, made on first use
         self.refold()
 
+    def load_params(self, params):
+        """Overwrite the parameter buffer in place: a TF-named dict (packed with this plan) or a flat array / tensor in the plan's
+        layout (e.g. a Trainer's `params`: the training and the inference plan share one layout).  The folded BN is NOT updated:
+        call refold() before the next forward."""
+        if torch.is_tensor(params):
+            flat = params.detach().reshape(-1).to(dtype=torch.float32)
+        else:
+            flat = torch.from_numpy(np.ascontiguousarray(
+                params if isinstance(params, np.ndarray) and params.ndim == 1 else self.plan.pack(params), dtype=np.float32))
+        if flat.numel() != self.params.numel():
+            raise _lib.StabnetError("load_params: %d floats given, the plan has %d" % (flat.numel(), self.params.numel()))
+        self.params.copy_(flat)
+
     def refold(self):
+        """Re-derive the folded BN (scale / shift of the moving statistics) from the current parameter buffer."""
         _lib.call("stabnet_net_fold_bn", self.plan.handle, ptr(self.params), ptr(self.fold), self.cfg.bn_eps,
                   stream_ptr(self.device), device=self.device)
 

@@ -5,7 +5,8 @@ backward are otherwise reached only through whole training steps at one small sh
 point at the row / channel counts of the 8 x 288 x 512 step and at ragged edge shapes, every output and workspace between canary
 bands, workspaces pre-filled with NaN.  References are NumPy / torch float64 written in this file; a bar that is not derived from
 the number format is 4 x the error of a float32 NumPy restatement of the same arithmetic, measured in the test at the same inputs
-(the figures measured when the test was written are in the comments marked MEASURED)."""
+(the figures measured when the test was written are in the comments marked MEASURED).  The L2 regulariser (stabnet_weight_decay)
+and the host mirror's elementwise helpers (stabnet_axpb, stabnet_interleave2) follow at the end, through their own entry points."""
 import ctypes
 
 import numpy as np
@@ -631,3 +632,227 @@ def test_argument_errors(cuda):
     refused(L.stabnet_fc_bwd(d, h, 0, d, 2, 8, 3, 0, d, d, 0, 0, 0, st), "fc_bwd")
     torch.cuda.synchronize()
     assert buf.untouched() and not host.any()                             # none of the refused calls launched anything
+
+
+# ---- i. L2 regulariser (stabnet_weight_decay) -------------------------------------------------------------------------------
+WD_N = 4096                                                # floats of the flat parameter / gradient buffer
+WD_LENS = (1, 2, 3, 4, 5, 7, 8, 9)
+WD_COEFS = (1e-4, 2e-4, 0.0)                               # slim conv weights, fc_weights / fc_bias, and a segment that is switched off
+
+
+def _wd_table(k):
+    """Segment table k: a 1 027-float segment whose offset & 3 == k, then lengths 1..9 at every offset & 3.  Placed greedily, so a
+    segment whose wanted alignment is the cursor's is ADJACENT to its predecessor and every other one leaves a gap of 1..3 floats
+    (and 5 floats lead the table) that no call may touch.  -> offsets, lengths (int64), coefficients (float32)."""
+    items = [(k, 1027)] + [(a, n) for n in WD_LENS for a in (0, 1, 2, 3)]
+    off, cur = [], 5
+    for a, n in items:
+        o = cur + ((a - cur) & 3)
+        off.append(o)
+        cur = o + n
+    assert cur <= WD_N
+    lens = np.array([n for _, n in items], np.int64)
+    coef = np.array([WD_COEFS[i % 3] for i in range(len(items))], np.float32)
+    return np.array(off, np.int64), lens, coef
+
+
+def _wd_model(params, off, lens, coef, loss0):
+    """The kernels' own summation tree, op for op (weight_decay_kernel + weight_decay_finalize_kernel, grid (64, nseg) x 256):
+    thread t of a segment squares its head / tail element and its float4s ((x2 + y2) + (z2 + w2), stride 64 * 256), the 64 lanes
+    of a wave add in an xor butterfly 32..1, the four waves as (0 + 1) + (2 + 3), the block partial is (0.5 * coef) * that -- all
+    float32; the finalize sums the 64 * nseg partials in double (thread i takes i, i + 1024, ..; butterfly; 16 waves in order)
+    and adds the float32 rounding of that onto *loss_out.  -> the float32 value the call must leave in *loss_out, and the block
+    partials [nseg, 64] it must leave in the workspace."""
+    f = np.float32
+    lane = np.arange(64)
+    parts = np.zeros((len(off), 64), f)
+    for g, (o, n, c) in enumerate(zip(off, lens, coef)):
+        head = min(int(n), (4 - (int(o) & 3)) & 3)
+        body, tail = (int(n) - head) >> 2, (int(n) - head) & 3
+        s = np.zeros(64 * 256, f)
+        t = np.arange(head + tail)
+        w = params[o + np.where(t < head, t, head + 4 * body + (t - head))]
+        s[:head + tail] = w * w
+        for start in range(0, body, 64 * 256):
+            m = min(64 * 256, body - start)
+            w4 = params[o + head + 4 * start:o + head + 4 * (start + m)].reshape(m, 4)
+            q = w4 * w4
+            s[:m] = s[:m] + ((q[:, 0] + q[:, 1]) + (q[:, 2] + q[:, 3]))
+        s = s.reshape(64, 4, 64)
+        for x in (32, 16, 8, 4, 2, 1):
+            s = s + s[:, :, lane ^ x]
+        red = s[:, :, 0]
+        parts[g] = (f(0.5) * f(c)) * ((red[:, 0] + red[:, 1]) + (red[:, 2] + red[:, 3]))
+    flat = parts.reshape(-1).astype(np.float64)
+    d = np.zeros(1024 * ((flat.size + 1023) // 1024))
+    d[:flat.size] = flat
+    acc = np.zeros(1024)
+    for row in d.reshape(-1, 1024):                         # thread i: partial[i], then partial[i + 1024], ...
+        acc = acc + row
+    acc = acc.reshape(16, 64)
+    for x in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lane ^ x]
+    tot = acc[0, 0]
+    for wv in range(1, 16):
+        tot = tot + acc[wv, 0]
+    return f(f(loss0) + f(tot)), parts
+
+
+@pytest.mark.parametrize("k", [0, 1, 2, 3])
+def test_weight_decay_matches_float64(cuda, k):
+    """stabnet_weight_decay through its own entry point: every offset & 3 crossed with lengths 1, 2, 3, 4, 5, 7, 8, 9 and 1 027
+    (scalar head, float4 body, scalar tail; segments shorter than their head; adjacent segments; gaps), coefficients 1e-4 / 2e-4 /
+    0, with and without a gradient, with and without the value, gscale 0 (the theta-only step) and 2 * regu_mul.
+
+    Gradient: grads + gscale * coef * w formed in float64 and rounded once, within 1 ulp.  (The kernel rounds gscale * coef, its
+    product with w and the sum: the first two are 2^-23 of a term that is <= 2.4e-6 * 2 / 0.1 of the gradient it is added to --
+    the gradients here are 0.1 <= |g| < 2 so that the sum does not cancel -- so the result is the correctly rounded one or its
+    neighbour.)
+
+    Value: *loss_out starts at L0 != 0 and must end at L0 + S, S = sum coef * 0.5 * sum w^2 in float64.  Bound from the summation
+    tree (see _wd_model): no segment has more than 256 float4s, so a thread adds at most ONE float4 to at most one head / tail
+    square: 1 rounding for a square, 2 for the float4's tree, 1 for the thread's add, 6 butterfly levels, 2 for the waves, 1 for
+    the product with 0.5 * coef (0.5 * coef itself is exact) = 13 roundings on any path, all terms >= 0, so every block partial is
+    within (1 + u)^13 - 1 of exact, u = 2^-24; the double sum of 64 * nseg partials adds < 2^-40; its float32 rounding u; the
+    final float32 add u * (L0 + S) / S.  With L0 = S / 4 (rounded): (13 + 1 + 1.25) u = 9.1e-7 of S < the 1e-6 of S asserted.
+    Beyond that bound the value AND the 64 * nseg float32 block partials in the workspace must equal the model of that tree BIT FOR
+    BIT: an element that moves to another thread (a wrong head length whose float4 accesses stay inside the segment) changes no
+    gradient and moves the value by roundings only -- the double sum hides them in the final float32, the partials show them."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import stream_ptr
+    from stabnet_amd.config import Config
+    L, st = _lib.lib(), stream_ptr(cuda)
+    rng = np.random.default_rng(100 + k)
+    off, lens, coef = _wd_table(k)
+    nseg = len(off)
+    ends = off + lens
+    assert (off[1:] >= ends[:-1]).all() and (off[1:] == ends[:-1]).any() and (off[1:] > ends[:-1]).any()   # disjoint; adjacent ones; gaps
+    assert {(int(o) & 3, int(n)) for o, n in zip(off, lens)} >= {(a, n) for a in range(4) for n in WD_LENS} | {(k, 1027)}
+    assert any(n < ((4 - (o & 3)) & 3) for o, n in zip(off, lens))                                         # shorter than its head
+    inside = np.zeros(WD_N, bool)
+    for o, n in zip(off, lens):
+        inside[o:o + n] = True
+    w = rng.standard_normal(WD_N).astype(np.float32)
+    g0 = (rng.uniform(0.1, 2.0, WD_N) * rng.choice([-1.0, 1.0], WD_N)).astype(np.float32)
+    S = float(sum(np.float64(c) * 0.5 * (w[o:o + n].astype(np.float64) ** 2).sum() for o, n, c in zip(off, lens, coef)))
+    L0 = np.float32(0.25 * S)
+    u = 2.0 ** -24
+    bound = (((1 + u) ** 13 - 1) + 2.0 ** -40 + u) * S + u * (float(L0) + S)
+    assert S > 0 and bound < 1e-6 * S, (S, bound)                                                         # (input condition)
+    d_off, d_len = torch.from_numpy(off).to(cuda), torch.from_numpy(lens).to(cuda)
+    d_coef = torch.from_numpy(coef).to(cuda)
+    gs_live = 2.0 * Config().regu_mul                       # (the entry point takes it as a float: the reference below rounds it too)
+
+    def run(gscale, with_grads, with_loss):
+        P, G = Guarded(cuda, WD_N, w), Guarded(cuda, WD_N, g0)
+        loss, part = Guarded(cuda, 1, np.array([L0], np.float32)), Guarded(cuda, 64 * nseg)
+        rc = L.stabnet_weight_decay(P.t.data_ptr(), G.t.data_ptr() if with_grads else 0, d_off.data_ptr(), d_len.data_ptr(),
+                                    d_coef.data_ptr(), nseg, gscale, loss.t.data_ptr() if with_loss else 0,
+                                    part.t.data_ptr() if with_loss else 0, st)
+        assert rc == 0, L.stabnet_last_error()
+        _check_all({"params": P, "grads": G, "loss_out": loss, "partials": part})
+        assert _same_bits(P.np(), w)
+        if not with_loss:
+            assert _same_bits(loss.np(), [L0]) and bool(torch.isnan(part.t).all())
+        return G.np(), float(loss.np()[0]), part.np()
+
+    for gscale in (gs_live, 0.0):
+        g, val, parts = run(gscale, True, True)
+        g_again, val_again, parts_again = run(gscale, True, True)
+        assert _same_bits(g, g_again) and val == val_again and _same_bits(parts, parts_again)                      # two calls, equal bits
+        assert _same_bits(g[~inside], g0[~inside]), "a gap between segments was written"
+        want = g0.astype(np.float64)
+        for o, n, c in zip(off, lens, coef):
+            want[o:o + n] += float(np.float32(gscale)) * np.float64(c) * w[o:o + n].astype(np.float64)
+        want32 = want.astype(np.float32)
+        if gscale == 0.0:
+            assert _same_bits(g, g0), "gscale 0 (theta-only step) changed gradient bits"
+        else:
+            assert (np.abs(g.astype(np.float64) - want32) <= np.spacing(np.abs(want32))).all()
+            on = np.zeros(WD_N, bool)
+            for o, n, c in zip(off, lens, coef):
+                on[o:o + n] = c != 0
+            assert not _same_bits(g[on], g0[on]) and _same_bits(g[inside & ~on], g0[inside & ~on])   # coef 0: untouched values
+        print("weight_decay table %d gscale %g: value %.9g float64 %.9g rel err %.2e (bound %.2e)"
+              % (k, gscale, val, float(L0) + S, abs(val - (float(L0) + S)) / S, bound / S))
+        assert abs(val - (float(L0) + S)) <= 1e-6 * S
+        model_val, model_parts = _wd_model(w, off, lens, coef, L0)
+        assert np.float32(val) == model_val, "value differs from the kernels' own summation order"
+        assert _same_bits(parts, model_parts.reshape(-1)), "block partials differ from the kernel's thread <-> element map"
+    # grads = NULL: the value alone, the same bits; loss_out = NULL: the gradient alone, the same bits
+    _, val_only, _ = run(gs_live, False, True)
+    assert val_only == val
+    g_only, _, _ = run(gs_live, True, False)
+    g_live, _, _ = run(gs_live, True, True)
+    assert _same_bits(g_only, g_live)
+
+
+def test_weight_decay_argument_errors(cuda):
+    """The refusals of stabnet_weight_decay (and of stabnet_axpb / stabnet_interleave2) return before any launch."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import stream_ptr
+    L, st = _lib.lib(), stream_ptr(cuda)
+    buf = Guarded(cuda, 1 << 12, "canary")
+    d = buf.t.data_ptr()
+    off, lens, coef = _wd_table(0)
+    d_off, d_len, d_coef = torch.from_numpy(off).to(cuda), torch.from_numpy(lens).to(cuda), torch.from_numpy(coef).to(cuda)
+    so, sl, sc = d_off.data_ptr(), d_len.data_ptr(), d_coef.data_ptr()
+
+    def refused(rc, word):
+        msg = L.stabnet_last_error()
+        assert rc == -1 and msg and word.encode() in msg, (rc, msg)
+
+    refused(L.stabnet_weight_decay(0, d, so, sl, sc, len(off), 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, 0, sl, sc, len(off), 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, so, 0, sc, len(off), 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, so, sl, 0, len(off), 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, so, sl, sc, 0, 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, so, sl, sc, 65536, 1.0, d, d, st), "bad arguments")
+    refused(L.stabnet_weight_decay(d, d, so, sl, sc, len(off), 1.0, d, 0, st), "workspace")
+    refused(L.stabnet_axpb(0, 1.0, 0.0, 4, d, st), "axpb")
+    refused(L.stabnet_axpb(d, 1.0, 0.0, 0, d, st), "axpb")
+    refused(L.stabnet_interleave2(d, 0, 4, d, st), "interleave2")
+    refused(L.stabnet_interleave2(d, d, 0, d, st), "interleave2")
+    torch.cuda.synchronize()
+    assert buf.untouched()
+
+
+# ---- j. the host mirror's elementwise helpers -------------------------------------------------------------------------------
+ELEMWISE_N = (1, 255, 256, 257, 1027)                      # one thread; one block less / exactly / plus one; five blocks, ragged
+
+
+@pytest.mark.parametrize("n", ELEMWISE_N)
+def test_axpb_bit_exact(cuda, n):
+    """stabnet_axpb: y = a * x + b, two roundings (no contraction), bit for bit against NumPy float32."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import stream_ptr
+    L, st = _lib.lib(), stream_ptr(cuda)
+    rng = np.random.default_rng(n)
+    x = rng.standard_normal(n).astype(np.float32)
+    for a, b in ((-1.0, 1.0), (0.3, -0.7), (0.0, 2.5)):      # (-1, 1) is the step's 1 - black_pix
+        X, Y = Guarded(cuda, n, x), Guarded(cuda, n)
+        assert L.stabnet_axpb(X.t.data_ptr(), a, b, n, Y.t.data_ptr(), st) == 0, L.stabnet_last_error()
+        _check_all({"x": X, "y": Y})
+        assert _same_bits(Y.np(), np.float32(a) * x + np.float32(b)) and _same_bits(X.np(), x)
+
+
+@pytest.mark.parametrize("n", ELEMWISE_N)
+def test_interleave2_bit_exact(cuda, n):
+    """stabnet_interleave2: out [n][2] = (a, b), written as float2 -- also into a view that starts 8 bytes into its allocation
+    (float2's natural alignment, not 16 bytes)."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import stream_ptr
+    L, st = _lib.lib(), stream_ptr(cuda)
+    rng = np.random.default_rng(1000 + n)
+    a, b = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    want = np.stack([a, b], axis=1).reshape(-1)
+    for shift in (0, 2):                                     # floats: the inner buffer starts 16-byte aligned
+        A, B, O = Guarded(cuda, n, a), Guarded(cuda, n, b), Guarded(cuda, 2 * n + 4)
+        out = O.t[shift:shift + 2 * n]
+        assert O.t.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 4 * shift
+        assert L.stabnet_interleave2(A.t.data_ptr(), B.t.data_ptr(), n, out.data_ptr(), st) == 0, L.stabnet_last_error()
+        _check_all({"a": A, "b": B, "out": O})
+        got = O.np()
+        assert _same_bits(got[shift:shift + 2 * n], want)
+        assert np.isnan(got[:shift]).all() and np.isnan(got[shift + 2 * n:]).all(), "write outside the [n][2] view"
+        assert _same_bits(A.np(), a) and _same_bits(B.np(), b)

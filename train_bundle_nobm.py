@@ -65,6 +65,22 @@ def latest_checkpoint(model_dir):
     return os.path.join(model_dir, max(c, key=lambda f: int(f[6:-4]))) if c else None
 
 
+def save_checkpoint(tr, path):
+    """Write a Trainer's state as one `.npz`: every variable of the plan under its TF name, plus `__adam_m` / `__adam_v` (flat,
+    trainable layout) and `__global_step` (int64 scalar).  The `__` keys are what restore_checkpoint reads back and what
+    deploy_bundle.load_weights leaves out."""
+    sd = tr.state_dict()
+    arrays = tr.plan.unpack(sd['params'])
+    np.savez(path, __adam_m=sd['adam_m'], __adam_v=sd['adam_v'], __global_step=np.int64(sd['global_step']), **arrays)
+
+
+def restore_checkpoint(tr, path):
+    """Load a save_checkpoint file into a Trainer of the same plan: parameters (moving statistics included), Adam moments, step."""
+    z = np.load(path)
+    tr.load_state_dict({'params': tr.plan.pack({k: z[k] for k in z.files if not k.startswith('__')}),
+                        'adam_m': z['__adam_m'], 'adam_v': z['__adam_v'], 'global_step': int(z['__global_step'])})
+
+
 def main():
     args = build_parser().parse_args()
     import torch
@@ -110,9 +126,7 @@ def main():
     if resume is not None:
         ck = resume
         if ck:
-            z = np.load(ck)
-            tr.load_state_dict({'params': tr.plan.pack({k: z[k] for k in z.files if not k.startswith('__')}),
-                                'adam_m': z['__adam_m'], 'adam_v': z['__adam_v'], 'global_step': int(z['__global_step'])})
+            restore_checkpoint(tr, ck)
             print('restoring {}'.format(ck))
     st_step = tr.global_step
     training_iter = args.iters if args.iters is not None else cfg.training_iter
@@ -177,10 +191,7 @@ def main():
             tr.sync_moving_stats()        # (collective: every rank) BN moving statistics are per-rank (local BN); checkpoint their mean
         if (i % cfg.save_freq == 0 or i == training_iter - 1) and rank == 0 and i > st_step:
             os.makedirs(model_dir, exist_ok=True)
-            sd = tr.state_dict()
-            arrays = tr.plan.unpack(sd['params'])
-            np.savez(os.path.join(model_dir, 'model-%d.npz' % i), __adam_m=sd['adam_m'], __adam_v=sd['adam_v'],
-                     __global_step=np.int64(sd['global_step']), **arrays)
+            save_checkpoint(tr, os.path.join(model_dir, 'model-%d.npz' % i))
         if (i % cfg.test_freq == 0 or i == training_iter - 1) and i > st_step:
             s = 0.0
             for j in range(10):                                       # test_batches
