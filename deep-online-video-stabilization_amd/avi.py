@@ -98,10 +98,17 @@ class AviMjpegWriter:
 class AviMjpegReader:
     """Frame count, fps, size and the JPEG bytes of frame i of an MJPG AVI; frames() decodes with Pillow, device_clip() on the GPU."""
 
-    def __init__(self, path):
+    def __init__(self, path, mapped: bool = False):
+        """mapped=True: the file is memory-mapped, not read: a clip of any length costs its index (two ints per frame), and jpeg(i)
+        copies one frame out of the page cache."""
         self.path = path
         with open(path, "rb") as f:
-            data = f.read()
+            if mapped:
+                import mmap
+                f.seek(0, 2)
+                data = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if f.tell() > 0 else b""
+            else:
+                data = f.read()
         if data[:4] != b"RIFF" or data[8:12] != b"AVI ":
             raise AviError("%s: not a RIFF AVI file" % path)
         self._data = data
@@ -157,7 +164,7 @@ class AviMjpegReader:
 
     def jpeg(self, i: int) -> bytes:
         off, n = self._frames[i]
-        return self._data[off:off + n]
+        return bytes(self._data[off:off + n])
 
     def frame(self, i: int):
         """Frame i decoded by Pillow: uint8 [H,W] (grey JPEG) or [H,W,3] in BGR order (as the rest of the project keeps colour)."""

@@ -220,6 +220,110 @@ __global__ __launch_bounds__(256) void mjpeg_transform_kernel(const unsigned cha
     }
 }
 
+// The same transform from a planar frame (stabnet_mjpeg_encode_i420): Y [H,W] and, for MJ_420, Cb and Cr [H/2,W/2] behind it, dense,
+// frames frame_stride bytes apart.  The samples ARE the JFIF components, so the load stage is a level shift: no colour arithmetic and no
+// 2x2 mean.  4:2:0: a lane loads four luma samples of one row of the 16x16 patch (a dword where it is aligned and inside the row) and
+// one sample each of Cb and Cr; partial MCUs replicate the edge sample of the plane.  From the first barrier on these are the lines of
+// mjpeg_transform_kernel, repeated here and not shared: that kernel's code must not move (tools/isa_hash.py).
+template <int MODE>
+__global__ __launch_bounds__(256) void mjpeg_transform_planar_kernel(const unsigned char* __restrict__ src, size_t frame_stride, int H, int W,
+                                                                     int mcux, int nmcu, const unsigned short* __restrict__ qluma,
+                                                                     const unsigned short* __restrict__ qchroma, short* __restrict__ coef,
+                                                                     size_t coef_frame_stride) {
+    static_assert(MODE == MJ_420 || MODE == MJ_GREY, "planar frames are 4:2:0 or grey");
+    constexpr int MPW = MODE == MJ_420 ? 1 : 8;                            // MCUs per wave
+    constexpr int BPM = MODE == MJ_420 ? 6 : 1;                            // blocks per MCU
+    constexpr int NB = MPW * BPM;
+    __shared__ __attribute__((aligned(16))) float s_blk[4][8 * kBlkStride];
+    __shared__ __attribute__((aligned(16))) short s_out[4][8 * 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = blockIdx.y;
+    const int m0 = (blockIdx.x * 4 + wave) * MPW;
+    const unsigned char* im = src + (size_t)n * frame_stride;
+    float* blk = s_blk[wave];
+    short* outb = s_out[wave];
+
+    if (m0 < nmcu) {
+        if (MODE == MJ_420) {
+            const int my = m0 / mcux, mx = m0 - my * mcux;
+            {
+                const int py = lane >> 2, px = (lane & 3) * 4;            // four samples of row py of the patch
+                const int y = min(my * 16 + py, H - 1), x = mx * 16 + px;
+                const unsigned char* row = im + (size_t)y * W;
+                unsigned v;
+                if (x + 4 <= W && ((uintptr_t)(row + x) & 3) == 0) {
+                    v = *reinterpret_cast<const unsigned*>(row + x);
+                } else {
+                    v = 0u;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v |= (unsigned)row[min(x + k, W - 1)] << (8 * k);
+                }
+                float* d = blk + ((py >> 3) * 2 + (px >> 3)) * kBlkStride + (py & 7) * 8 + (px & 7);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d[k] = (float)((v >> (8 * k)) & 0xffu) - 128.0f;
+            }
+            const int CH = H >> 1, CW = W >> 1;
+            const int cy = min(my * 8 + (lane >> 3), CH - 1), cx = min(mx * 8 + (lane & 7), CW - 1);
+            const unsigned char* cb = im + (size_t)H * W;
+            const unsigned char* cr = cb + (size_t)CH * CW;
+            blk[4 * kBlkStride + lane] = (float)cb[(size_t)cy * CW + cx] - 128.0f;
+            blk[5 * kBlkStride + lane] = (float)cr[(size_t)cy * CW + cx] - 128.0f;
+        } else {
+#pragma unroll
+            for (int j = 0; j < MPW; ++j) {
+                const int m = min(m0 + j, nmcu - 1);                  // past the last MCU: a copy that is never stored
+                const int my = m / mcux, mx = m - my * mcux;
+                const int y = min(my * 8 + (lane >> 3), H - 1), x = min(mx * 8 + (lane & 7), W - 1);
+                blk[j * kBlkStride + lane] = (float)im[(size_t)y * W + x] - 128.0f;
+            }
+        }
+    }
+    __syncthreads();
+    const int b = lane >> 3, r = lane & 7;
+    if (m0 < nmcu && lane < NB * 8) {               // rows: lane = (block, row)
+        float* row = blk + b * kBlkStride + r * 8;
+        float in[8], o[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) in[x] = row[x];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float s = d_tab.dct[u][0] * in[0];
+#pragma unroll
+            for (int x = 1; x < 8; ++x) s += d_tab.dct[u][x] * in[x];
+            o[u] = s;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) row[u] = o[u];
+    }
+    __syncthreads();
+    if (m0 < nmcu && lane < NB * 8) {               // columns: lane = (block, column); quantise, clamp, zig-zag
+        const float* col = blk + b * kBlkStride + r;
+        const bool luma = MODE == MJ_GREY ? true : (b < 4);
+        const unsigned short* q = luma ? qluma : qchroma;
+        float in[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) in[k] = col[k * 8];
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            float s = d_tab.dct[v][0] * in[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) s += d_tab.dct[v][k] * in[k];
+            const int nat = v * 8 + r;
+            float t = rintf(s / (float)q[nat]);
+            const float lim = nat == 0 ? 1024.0f : 1023.0f;           // every value keeps a baseline Huffman category
+            t = fminf(fmaxf(t, -lim), lim);
+            outb[b * 64 + d_tab.zzpos[nat]] = (short)(int)t;
+        }
+    }
+    __syncthreads();
+    if (m0 < nmcu) {
+        const int nvb = min(MPW, nmcu - m0) * BPM;                    // blocks of MCUs that exist
+        unsigned* dst = reinterpret_cast<unsigned*>(coef + (size_t)n * coef_frame_stride + (size_t)m0 * BPM * 64);
+        const unsigned* srcw = reinterpret_cast<const unsigned*>(outb);
+        for (int i = lane; i < nvb * 32; i += 64) dst[i] = srcw[i];
+    }
+}
+
 // ---- entropy coding ------------------------------------------------------------------------------------------------------------
 struct BitSink {
     unsigned char* out;
@@ -369,6 +473,12 @@ __global__ __launch_bounds__(256) void mjpeg_gather_kernel(const unsigned char* 
     }
 }
 
+// The launches behind the transform (entropy, layout, gather), for stabnet_mjpeg_encode and stabnet_mjpeg_encode_i420 alike.  Defined
+// behind stabnet_mjpeg_encode and in front of stabnet_mjpeg_encode_i420: kernels are emitted in the order of their first use, and
+// tools/isa_hash.py shows the existing ones unchanged that way.
+int mj_launch_tail(const MjGeom& g, const MjWs& w, int N, int restart_mcus, unsigned char* wsb, const unsigned char* header_dev, int header_bytes,
+                   unsigned char* out, size_t out_stride, int* out_bytes, hipStream_t st, Prof* prof);
+
 struct ByteOut {
     unsigned char* p;
     int cap, n;
@@ -481,13 +591,10 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
     Prof* prof = static_cast<Prof*>(profp);
     unsigned char* wsb = static_cast<unsigned char*>(workspace);
     short* coef = reinterpret_cast<short*>(wsb + w.coef);
-    int* lens = reinterpret_cast<int*>(wsb + w.lens);
-    int* offs = reinterpret_cast<int*>(wsb + w.offs);
-    unsigned char* slots = wsb + w.slots;
     const size_t coef_stride = w.frame / sizeof(short);
     const double px = (double)N * H * W, coef_bytes = (double)N * g.nblk * 128.0;
 
-    bool rec = prof && prof->begin(st);
+    const bool rec = prof && prof->begin(st);
     {
         const int mpw = g.mode == MJ_420 ? 1 : (g.mode == MJ_444 ? 2 : 8);
         const dim3 grid(cdiv(cdiv(g.nmcu, mpw), 4), N);
@@ -501,7 +608,23 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
     if (rec) prof->end(st, PK_KERNEL_MJPEG_TRANSFORM, 2.0 * 16.0 * (double)N * g.nblk * 64.0, px * C + coef_bytes);
     SN_LAUNCH_CHECK("mjpeg_transform_kernel");
 
-    rec = prof && prof->begin(st);
+    return mj_launch_tail(g, w, N, restart_mcus, wsb, header_dev, header_bytes, out, out_stride, out_bytes, st, prof);
+}
+
+}  // extern "C"
+
+namespace {
+
+int mj_launch_tail(const MjGeom& g, const MjWs& w, int N, int restart_mcus, unsigned char* wsb, const unsigned char* header_dev, int header_bytes,
+                   unsigned char* out, size_t out_stride, int* out_bytes, hipStream_t st, Prof* prof) {
+    const short* coef = reinterpret_cast<const short*>(wsb + w.coef);
+    int* lens = reinterpret_cast<int*>(wsb + w.lens);
+    int* offs = reinterpret_cast<int*>(wsb + w.offs);
+    unsigned char* slots = wsb + w.slots;
+    const size_t coef_stride = w.frame / sizeof(short);
+    const double coef_bytes = (double)N * g.nblk * 128.0;
+
+    bool rec = prof && prof->begin(st);
     {
         const dim3 grid(cdiv(g.nint, 256), N);
         if (g.mode == MJ_420)
@@ -524,6 +647,60 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
     if (rec) prof->end(st, PK_KERNEL_MJPEG_GATHER, 0.0, (double)N * 8.0 * g.nint);         // + twice the compressed bytes
     SN_LAUNCH_CHECK("mjpeg_gather_kernel");
     return STABNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* src: N planar frames frame_stride_bytes apart, each Y [H,W] and, for planes = 3, U [H/2,W/2] and V [H/2,W/2] behind it, dense (what
+ * stabnet_warp_rev_bundle2_i420 writes) -> the streams of stabnet_mjpeg_encode for C = planes, subsampling 420: header, tables,
+ * stabnet_mjpeg_max_bytes and the workspace are those. */
+int stabnet_mjpeg_encode_i420(const unsigned char* src, int N, int H, int W, int planes, size_t frame_stride_bytes, int restart_mcus,
+                              const unsigned short* luma64_dev, const unsigned short* chroma64_dev, const unsigned char* header_dev,
+                              int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
+                              size_t workspace_bytes, void* stream, void* profp) {
+    SN_REQUIRE(src && luma64_dev && header_dev && out && out_bytes && workspace, "mjpeg_encode_i420: null pointer");
+    SN_REQUIRE(planes == 1 || planes == 3, "mjpeg_encode_i420: planes must be 1 (Y) or 3 (Y, U, V of 4:2:0), got %d", planes);
+    SN_REQUIRE(planes == 1 || chroma64_dev, "mjpeg_encode_i420: null pointer (chroma table)");
+    MjGeom g;
+    SN_REQUIRE(N >= 1 && N <= 65535 && mj_geom(H, W, planes, 420, restart_mcus, &g),
+               "mjpeg_encode_i420: bad batch, shape or restart interval (1..65535)");
+    SN_REQUIRE(planes == 1 || ((H | W) & 1) == 0, "mjpeg_encode_i420: a 4:2:0 planar frame of %dx%d has an odd side, it needs even ones", W, H);
+    const size_t fb = planes == 3 ? (size_t)H * W * 3 / 2 : (size_t)H * W;
+    SN_REQUIRE(frame_stride_bytes >= fb, "mjpeg_encode_i420: frame_stride_bytes %zu < the frame's %zu bytes (%dx%d, %d plane%s)",
+               frame_stride_bytes, fb, W, H, planes, planes == 1 ? "" : "s");
+    const size_t need_out = stabnet_mjpeg_max_bytes(H, W, planes, 420, restart_mcus);
+    SN_REQUIRE(header_bytes == mj_header_size(planes), "mjpeg_encode_i420: header_bytes %d, stabnet_mjpeg_header writes %d for C = %d", header_bytes,
+               mj_header_size(planes), planes);
+    SN_REQUIRE(out_stride >= need_out, "mjpeg_encode_i420: out_stride %zu < stabnet_mjpeg_max_bytes %zu", out_stride, need_out);
+    const MjWs w = mj_ws(g);
+    if (workspace_bytes < (size_t)N * w.frame) {
+        stabnet_set_error("mjpeg_encode_i420: workspace %zu < %zu bytes", workspace_bytes, (size_t)N * w.frame);
+        return STABNET_ERR_WORKSPACE;
+    }
+    SN_REQUIRE(((uintptr_t)workspace & 15) == 0, "mjpeg_encode_i420: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    int rc = sn_check_device(src, "mjpeg_encode_i420: src", st);
+    if (rc == 0) rc = sn_check_device(out, "mjpeg_encode_i420: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "mjpeg_encode_i420: workspace", st);
+    if (rc) return rc;
+    Prof* prof = static_cast<Prof*>(profp);
+    unsigned char* wsb = static_cast<unsigned char*>(workspace);
+    short* coef = reinterpret_cast<short*>(wsb + w.coef);
+    const size_t coef_stride = w.frame / sizeof(short);
+
+    const bool rec = prof && prof->begin(st);
+    {
+        const dim3 grid(cdiv(cdiv(g.nmcu, g.mode == MJ_420 ? 1 : 8), 4), N);
+        if (g.mode == MJ_420)
+            mjpeg_transform_planar_kernel<MJ_420><<<grid, 256, 0, st>>>(src, frame_stride_bytes, H, W, g.mcux, g.nmcu, luma64_dev, chroma64_dev, coef, coef_stride);
+        else
+            mjpeg_transform_planar_kernel<MJ_GREY><<<grid, 256, 0, st>>>(src, frame_stride_bytes, H, W, g.mcux, g.nmcu, luma64_dev, luma64_dev, coef, coef_stride);
+    }
+    if (rec) prof->end(st, PK_KERNEL_MJPEG_TRANSFORM_PLANAR, 2.0 * 16.0 * (double)N * g.nblk * 64.0, (double)N * fb + (double)N * g.nblk * 128.0);
+    SN_LAUNCH_CHECK("mjpeg_transform_planar_kernel");
+    return mj_launch_tail(g, w, N, restart_mcus, wsb, header_dev, header_bytes, out, out_stride, out_bytes, st, prof);
 }
 
 }  // extern "C"

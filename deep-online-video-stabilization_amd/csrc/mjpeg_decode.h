@@ -58,3 +58,10 @@ inline bool jd_geom(int H, int W, int C, int subsampling, JdGeom* g) {
 int mjpegd_launch_planes(const JdGeom& g, int H, int W, const unsigned char* in, size_t in_stride, int N, const short* coef,
                          size_t coef_stride, unsigned char* wsb, unsigned char* out, size_t row_stride, size_t frame_stride, int stages,
                          void* stream);
+
+// mjpeg_decode.hip: the argument checks the two I420 entries share (a STABNET_* code, the sentence set), and the IDCT launch followed by
+// the crop of the padded planes to the dense I420 frame (mjpegd_planes_kernel) behind any entropy back end.  prof: Prof* or null.
+int mjpegd_clear_status(int* status, int N, void* stream);            // status[0..N) = 0, by a launch (see mjpeg_decode.hip)
+int mjpegd_i420_geom(const char* who, int N, int H, int W, int C, int subsampling, size_t frame_stride, JdGeom* g);
+int mjpegd_launch_i420(const JdGeom& g, int H, int W, const unsigned char* in, size_t in_stride, int N, const short* coef, size_t coef_stride,
+                       unsigned char* wsb, unsigned char* out, size_t frame_stride, void* stream, void* prof);

@@ -9,11 +9,14 @@
 //                           + 128, clamp; uint8 planes at MCU-padded size
 //   mjpegd_colour_kernel  : h2v2 fancy upsampling with neighbours clamped at the true chroma size, jdcolor's 16-bit fixed point,
 //                           clamp; BGR or grey at the caller's row stride, four pixels per lane, dword stores where aligned
+//   mjpegd_planes_kernel  : instead of the colour launch (stabnet_mjpeg_decode_i420): the MCU-padded planes cropped to the dense
+//                           I420 frame Y [H,W] | U [H/2,W/2] | V [H/2,W/2] that stabnet_warp_rev_bundle2_i420 reads; no arithmetic
 // Range: libjpeg looks the IDCT's result up in a table that wraps (& 1023) for values no real encoder produces; here it is a plain
 // clamp to [0, 255].
 #include "common.h"
 #include "jpeg_tables.h"
 #include "mjpeg_decode.h"
+#include "prof.h"
 
 namespace {
 
@@ -222,6 +225,49 @@ __global__ __launch_bounds__(256) void mjpegd_colour_kernel(const unsigned char*
     }
 }
 
+// The status words of the I420 entries are zeroed by a launch, not by a memset node: in a captured graph, the memset node of the BGR
+// entries has been seen to leave a wrong value in the word on the graph's first replay (the frame itself was right), and a status the
+// caller cannot trust is worth one tiny launch.
+// (A template, so that it is emitted at its first use, behind the existing kernels: tools/isa_hash.py shows those unchanged that way.)
+template <typename T>
+__global__ __launch_bounds__(256) void mjpegd_clear_status_kernel(T* __restrict__ status, int N) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n < N) status[n] = T(0);
+}
+
+// ---- planes as they are --------------------------------------------------------------------------------------------------------------
+// grid (cdiv(cdiv(W, 4), 256), H [+ 2 * (H / 2)], N): one workgroup per row segment of ONE plane, as remap_i420_kernel lays its grid
+// out -- rows 0 .. H - 1 are the Y plane's, then the Cb plane's H / 2, then the Cr plane's.  One lane = four pixels of the row: one
+// dword of the padded plane (its rows are 8-byte multiples on a 16-byte base, so the dword is aligned and inside the row), stored as a
+// dword where the destination is aligned and the four pixels exist, as bytes otherwise.  Nothing outside the frame's own H * W * 3 / 2
+// (grey: H * W) bytes is written.
+template <int MODE>
+__global__ __launch_bounds__(256) void mjpegd_planes_kernel(const unsigned char* __restrict__ ws, size_t ws_frame, size_t yoff, size_t cboff,
+                                                            size_t croff, int yw, int cw, int H, int W, unsigned char* __restrict__ out,
+                                                            size_t frame_stride) {
+    const int n = blockIdx.z;
+    int y = blockIdx.y, pw = W, sw = yw;
+    size_t soff = yoff, doff = 0;
+    if (MODE == JD_MODE_420 && y >= H) {                       // H, W even (the entry checks): chroma is H / 2 x W / 2
+        const int CH = H >> 1;
+        y -= H; pw = W >> 1; sw = cw;
+        soff = cboff; doff = (size_t)H * W;
+        if (y >= CH) { y -= CH; soff = croff; doff += (size_t)CH * pw; }
+    }
+    const int x0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x0 >= pw) return;
+    const unsigned v = *reinterpret_cast<const unsigned*>(ws + (size_t)n * ws_frame + soff + (size_t)y * sw + x0);
+    unsigned char* dst = out + (size_t)n * frame_stride + doff + (size_t)y * pw + x0;
+    if (x0 + 4 <= pw && ((uintptr_t)dst & 3) == 0) {
+        *reinterpret_cast<unsigned*>(dst) = v;
+    } else {
+        const int np = min(4, pw - x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < np) dst[k] = (unsigned char)(v >> (8 * k));
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,6 +340,49 @@ int stabnet_mjpeg_decode(const unsigned char* in, size_t in_stride, int N, int H
     return mjpegd_launch_planes(g, H, W, in, in_stride, N, coef, coef_stride, wsb, out, row_stride, frame_stride, stages, stream);
 }
 
+/* See include/stabnet_hip.h. */
+int stabnet_mjpeg_decode_i420(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, int coef_uploaded,
+                              unsigned char* out, size_t frame_stride_bytes, int* status, void* workspace, size_t workspace_bytes, void* stream,
+                              void* prof) {
+    SN_REQUIRE(in && out && status && workspace, "mjpeg_decode_i420: null pointer");
+    JdGeom g;
+    int rc = mjpegd_i420_geom("mjpeg_decode_i420", N, H, W, C, subsampling, frame_stride_bytes, &g);
+    if (rc) return rc;
+    const size_t coef_bytes = g.nblk * 64 * sizeof(short);
+    SN_REQUIRE((in_stride & 15) == 0 && ((uintptr_t)in & 15) == 0, "mjpeg_decode_i420: in and in_stride must be 16-byte aligned");
+    SN_REQUIRE(in_stride >= g.blob_max + (coef_uploaded ? coef_bytes : 0), "mjpeg_decode_i420: in_stride %zu < %zu", in_stride,
+               g.blob_max + (coef_uploaded ? coef_bytes : 0));
+    if (workspace_bytes < (size_t)N * g.frame) {
+        stabnet_set_error("mjpeg_decode_i420: workspace %zu < %zu bytes", workspace_bytes, (size_t)N * g.frame);
+        return STABNET_ERR_WORKSPACE;
+    }
+    SN_REQUIRE(((uintptr_t)workspace & 15) == 0, "mjpeg_decode_i420: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    rc = sn_check_device(in, "mjpeg_decode_i420: in", st);
+    if (rc == 0) rc = sn_check_device(out, "mjpeg_decode_i420: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "mjpeg_decode_i420: workspace", st);
+    if (rc == 0) rc = sn_check_device(status, "mjpeg_decode_i420: status", st);
+    if (rc) return rc;
+    unsigned char* wsb = static_cast<unsigned char*>(workspace);
+    rc = mjpegd_clear_status(status, N, stream);
+    if (rc) return rc;
+    const short* coef = reinterpret_cast<const short*>(wsb + g.coef);
+    size_t coef_stride = g.frame / sizeof(short);
+    if (coef_uploaded) {                     // the slot holds blob | coefficients: the IDCT reads them where they were uploaded
+        coef = reinterpret_cast<const short*>(in + g.blob_max);
+        coef_stride = in_stride / sizeof(short);
+    } else {
+        const dim3 grid(cdiv(g.nmcu, 256), N);
+        short* cw = reinterpret_cast<short*>(wsb + g.coef);
+        if (g.mode == JD_MODE_420)
+            mjpegd_entropy_kernel<JD_MODE_420><<<grid, 256, 0, st>>>(in, in_stride, H, W, g.nmcu, g.blob_max, cw, coef_stride, status);
+        else
+            mjpegd_entropy_kernel<JD_MODE_GREY><<<grid, 256, 0, st>>>(in, in_stride, H, W, g.nmcu, g.blob_max, cw, coef_stride, status);
+        SN_LAUNCH_CHECK("mjpegd_entropy_kernel");
+    }
+    return mjpegd_launch_i420(g, H, W, in, in_stride, N, coef, coef_stride, wsb, out, frame_stride_bytes, stream, prof);
+}
+
 }  // extern "C"
 
 // The launches behind the entropy decoding (stages 2 and 3), for stabnet_mjpeg_decode and stabnet_mjpeg_decode_sync alike.  Defined
@@ -323,5 +412,43 @@ int mjpegd_launch_planes(const JdGeom& g, int H, int W, const unsigned char* in,
             mjpegd_colour_kernel<JD_MODE_GREY><<<grid, 256, 0, st>>>(wsb, g.frame, g.yoff, g.cboff, g.croff, g.yw, g.cw, H, W, out, row_stride, frame_stride);
         SN_LAUNCH_CHECK("mjpegd_colour_kernel");
     }
+    return STABNET_OK;
+}
+
+// What stabnet_mjpeg_decode_i420 and stabnet_mjpeg_decode_sync_i420 accept, judged before any launch: grey of any size, 4:2:0 with even
+// sides, frames that do not overlap.
+int mjpegd_i420_geom(const char* who, int N, int H, int W, int C, int subsampling, size_t frame_stride, JdGeom* g) {
+    SN_REQUIRE(N >= 1 && N <= 65535 && jd_geom(H, W, C, subsampling, g), "%s: bad batch, shape, channels (1 | 3) or subsampling (420 | 444)", who);
+    SN_REQUIRE(g->mode != JD_MODE_444, "%s: 4:4:4 streams have no I420 frame; stabnet_mjpeg_decode reads them (BGR)", who);
+    SN_REQUIRE(g->mode != JD_MODE_420 || ((H | W) & 1) == 0,
+               "%s: a 4:2:0 stream of %dx%d has an odd side, a dense I420 frame needs even ones; stabnet_mjpeg_decode reads it (BGR)", who, W, H);
+    const size_t fb = g->mode == JD_MODE_420 ? (size_t)H * W * 3 / 2 : (size_t)H * W;
+    SN_REQUIRE(frame_stride >= fb, "%s: frame_stride_bytes %zu < the frame's %zu bytes (%dx%d, %d plane%s)", who, frame_stride, fb, W, H, C,
+               C == 1 ? "" : "s");
+    return STABNET_OK;
+}
+
+// The IDCT launch and the crop to the dense I420 frame, behind any entropy back end.
+int mjpegd_launch_i420(const JdGeom& g, int H, int W, const unsigned char* in, size_t in_stride, int N, const short* coef, size_t coef_stride,
+                       unsigned char* wsb, unsigned char* out, size_t frame_stride, void* stream, void* profp) {
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = mjpegd_launch_planes(g, H, W, in, in_stride, N, coef, coef_stride, wsb, nullptr, 0, 0, 2, stream);
+    if (rc) return rc;
+    Prof* prof = static_cast<Prof*>(profp);
+    const bool rec = prof && prof->begin(st);
+    const dim3 grid(cdiv(cdiv(W, 4), 256), g.mode == JD_MODE_420 ? H + 2 * (H / 2) : H, N);
+    if (g.mode == JD_MODE_420)
+        mjpegd_planes_kernel<JD_MODE_420><<<grid, 256, 0, st>>>(wsb, g.frame, g.yoff, g.cboff, g.croff, g.yw, g.cw, H, W, out, frame_stride);
+    else
+        mjpegd_planes_kernel<JD_MODE_GREY><<<grid, 256, 0, st>>>(wsb, g.frame, g.yoff, g.cboff, g.croff, g.yw, g.cw, H, W, out, frame_stride);
+    // bytes: the dwords read of the padded planes (the frame's size rounded up per row) + the frame written
+    if (rec) prof->end(st, PK_KERNEL_MJPEGD_PLANES, 0.0, 2.0 * (double)N * (g.mode == JD_MODE_420 ? 1.5 : 1.0) * H * W);
+    SN_LAUNCH_CHECK("mjpegd_planes_kernel");
+    return STABNET_OK;
+}
+
+int mjpegd_clear_status(int* status, int N, void* stream) {
+    mjpegd_clear_status_kernel<int><<<cdiv(N, 256), 256, 0, (hipStream_t)stream>>>(status, N);
+    SN_LAUNCH_CHECK("mjpegd_clear_status_kernel");
     return STABNET_OK;
 }

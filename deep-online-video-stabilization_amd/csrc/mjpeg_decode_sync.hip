@@ -13,7 +13,8 @@
 //   mjpegd_sync_kernel<2>   write: every lane walks its chunk from its accepted entry and stores the coefficients of its blocks, in
 //                           natural order, DC as (short)(predictor + difference) from the scanned sums
 // and the IDCT and colour launches of mjpeg_decode.hip.  A workgroup stages the bytes of its chunks (dword loads) and the four Huffman
-// tables in LDS; the walks read nothing else.
+// tables in LDS; the walks read nothing else.  stabnet_mjpeg_decode_sync_i420: the same launches in front of the IDCT and the crop to the
+// dense I420 frame (mjpeg_decode.hip: mjpegd_launch_i420), the status words zeroed by a launch instead of the memset.
 #include "common.h"
 #include "jpeg_sync.h"
 #include "jpeg_tables.h"
@@ -353,6 +354,47 @@ int stabnet_mjpeg_decode_sync(const unsigned char* in, size_t in_stride, int N, 
         rc = js_launch<JD_MODE_GREY>(in, in_stride, N, H, W, g, p.chunk, R, coef, coef_stride, status, sync, p.frame, p.nc_max, p.cpw, stats, stop, st);
     if (rc || stop) return rc;
     return mjpegd_launch_planes(g, H, W, in, in_stride, N, coef, coef_stride, wsb, out, row_stride, frame_stride, stages, stream);
+}
+
+/* See include/stabnet_hip.h: the same entropy launches, then the IDCT and the crop to the dense I420 frame. */
+int stabnet_mjpeg_decode_sync_i420(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, unsigned char* out,
+                                   size_t frame_stride_bytes, int* status, void* workspace, size_t workspace_bytes, int chunk_bytes, int rounds,
+                                   int* stats, void* stream, void* prof) {
+    SN_REQUIRE(in && out && status && workspace, "mjpeg_decode_sync_i420: null pointer");
+    JdGeom g;
+    int rc = mjpegd_i420_geom("mjpeg_decode_sync_i420", N, H, W, C, subsampling, frame_stride_bytes, &g);
+    if (rc) return rc;
+    SN_REQUIRE(js_chunk(chunk_bytes), "mjpeg_decode_sync_i420: chunk_bytes %d is not 0 (default) or a multiple of 4 in 8..4096", chunk_bytes);
+    SN_REQUIRE(rounds >= -1 && rounds <= 1024, "mjpeg_decode_sync_i420: rounds %d is not -1 (default) or 0..1024", rounds);
+    SN_REQUIRE((in_stride & 15) == 0 && ((uintptr_t)in & 15) == 0, "mjpeg_decode_sync_i420: in and in_stride must be 16-byte aligned");
+    JsPlan p;
+    SN_REQUIRE(in_stride >= g.blob_max && js_plan(g, in_stride, chunk_bytes, &p), "mjpeg_decode_sync_i420: in_stride %zu < %zu (or 2^30 and above)",
+               in_stride, g.blob_max);
+    if (workspace_bytes < (size_t)N * (g.frame + p.frame)) {
+        stabnet_set_error("mjpeg_decode_sync_i420: workspace %zu < %zu bytes", workspace_bytes, (size_t)N * (g.frame + p.frame));
+        return STABNET_ERR_WORKSPACE;
+    }
+    SN_REQUIRE(((uintptr_t)workspace & 15) == 0, "mjpeg_decode_sync_i420: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    rc = sn_check_device(in, "mjpeg_decode_sync_i420: in", st);
+    if (rc == 0) rc = sn_check_device(out, "mjpeg_decode_sync_i420: out", st);
+    if (rc == 0) rc = sn_check_device(workspace, "mjpeg_decode_sync_i420: workspace", st);
+    if (rc == 0) rc = sn_check_device(status, "mjpeg_decode_sync_i420: status", st);
+    if (rc == 0 && stats) rc = sn_check_device(stats, "mjpeg_decode_sync_i420: stats", st);
+    if (rc) return rc;
+    unsigned char* wsb = static_cast<unsigned char*>(workspace);
+    rc = mjpegd_clear_status(status, N, stream);
+    if (rc) return rc;
+    short* coef = reinterpret_cast<short*>(wsb + g.coef);
+    const size_t coef_stride = g.frame / sizeof(short);
+    unsigned char* sync = wsb + (size_t)N * g.frame;
+    const int R = rounds < 0 ? kJsDefaultRounds : rounds;
+    if (g.mode == JD_MODE_420)
+        rc = js_launch<JD_MODE_420>(in, in_stride, N, H, W, g, p.chunk, R, coef, coef_stride, status, sync, p.frame, p.nc_max, p.cpw, stats, 0, st);
+    else
+        rc = js_launch<JD_MODE_GREY>(in, in_stride, N, H, W, g, p.chunk, R, coef, coef_stride, status, sync, p.frame, p.nc_max, p.cpw, stats, 0, st);
+    if (rc) return rc;
+    return mjpegd_launch_i420(g, H, W, in, in_stride, N, coef, coef_stride, wsb, out, frame_stride_bytes, stream, prof);
 }
 
 }  // extern "C"

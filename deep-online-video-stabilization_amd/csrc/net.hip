@@ -739,6 +739,8 @@ const char* stabnet_prof_kind_name(int kind) {
         case PK_KERNEL_REMAP_CUBIC + 4: return "remap_cubic_kernel<1, 2>";
         case PK_KERNEL_REMAP_CUBIC + 5: return "remap_cubic_kernel<4, 2>";
         case PK_KERNEL_REMAP_I420_CUBIC: return "remap_i420_kernel<true>";
+        case PK_KERNEL_MJPEGD_PLANES: return "mjpegd_planes_kernel";
+        case PK_KERNEL_MJPEG_TRANSFORM_PLANAR: return "mjpeg_transform_planar_kernel";
         case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
         case PK_KERNEL_TVL1_STEP: return "tvl1_step_kernel";
         case PK_KERNEL_TVL1_FUSED: return "tvl1_fused_kernel";

@@ -14,6 +14,8 @@ enum {
     PK_KERNEL_REMAP_I420 = 59 /* remap.hip, stabnet_warp_rev_bundle2_i420; bytes = the window of every plane gathered + the planes written + small maps */,
     PK_KERNEL_REMAP_CUBIC = 250 /* + 2 * window_kind + (four-pixel path): remap_cubic_kernel<PX, KIND>, stabnet_warp_rev_bundle2_cubic; bytes as the bilinear kind's */,
     PK_KERNEL_REMAP_I420_CUBIC = 256 /* remap_i420_kernel<true>; bytes as PK_KERNEL_REMAP_I420 */,
+    PK_KERNEL_MJPEGD_PLANES = 257 /* mjpeg_decode.hip, stabnet_mjpeg_decode_i420 / _sync_i420; bytes = the planes read + the I420 frame written */,
+    PK_KERNEL_MJPEG_TRANSFORM_PLANAR = 258 /* mjpeg.hip, stabnet_mjpeg_encode_i420; bytes = the I420 frame read + the coefficients written */,
     PK_KERNEL_TF_GET_IMG = 64/* tf_image.hip; bytes = 12 tap bytes read + 4 written per destination value, every channel named */,
     PK_KERNEL_TVL1_STEP = 57, PK_KERNEL_TVL1_FUSED = 58 /* tvl1.hip, one record per launch; bytes = ten planes read + six written once, shape[0] = sweeps of the launch */,
     PK_KERNEL_TVL1_DOWN = 65, PK_KERNEL_TVL1_GRAD = 66, PK_KERNEL_TVL1_WARP = 67, PK_KERNEL_TVL1_UP = 68, PK_KERNEL_TVL1_MAP = 69 /* tvl1.hip stages; bytes = every plane read or written, once */,

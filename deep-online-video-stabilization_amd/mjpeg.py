@@ -26,6 +26,11 @@ def default_restart_mcus(channels: int = 3, subsampling="420") -> int:
     return DEFAULT_RESTART_MCUS if int(subsampling) == 420 else 4
 
 
+def planar_frame_bytes(H: int, W: int, channels: int = 3) -> int:
+    """Bytes of one dense planar frame: Y [H,W] and, for channels = 3, U and V [H/2,W/2] (I420)."""
+    return int(H) * int(W) * 3 // 2 if int(channels) == 3 else int(H) * int(W)
+
+
 def quant_tables(quality: int = 75):
     """(luma, chroma) uint16 [64], natural order: Annex K scaled by the IJG rule."""
     ql, qc = (ctypes.c_ushort * 64)(), (ctypes.c_ushort * 64)()
@@ -50,12 +55,22 @@ class MjpegEncoder:
     encode(img_u8) -> (buf uint8 [N, max_bytes], nbytes int32 [N]): device tensors, nothing synchronises, so the call can be
     captured in a hipGraph together with the launches that produce the frame.  Stream n is buf[n, :nbytes[n]]; the bytes behind it
     are undefined.  The buffers are sized for the worst case, so there is no overflow to report.
-    encode_bytes(img_u8) -> list[bytes] (synchronises, downloads)."""
+    encode_bytes(img_u8) -> list[bytes] (synchronises, downloads).
+    planar=True: the frames are planar instead, uint8 [N, frame_bytes] (rows frame_bytes or more apart): Y [H,W] and, for channels = 3,
+    U and V [H/2,W/2] behind it -- what warpRevBundle2_i420 writes and a planar MjpegDecoder fills (stabnet_mjpeg_encode_i420: no
+    colour conversion, no chroma averaging).  The streams are 4:2:0 (grey for channels = 1); colour needs even H and W."""
 
     def __init__(self, H: int, W: int, channels: int = 3, quality: int = 75, subsampling="420", restart_mcus=None, device="cuda:0",
-                 batch: int = 1, q_luma=None, q_chroma=None):
+                 batch: int = 1, q_luma=None, q_chroma=None, planar: bool = False):
         self.H, self.W, self.C, self.quality = int(H), int(W), int(channels), int(quality)
         self.subsampling = int(subsampling)
+        self.planar = bool(planar)
+        if self.planar:
+            if self.C == 3 and self.subsampling != 420:
+                raise _lib.StabnetError("MjpegEncoder: planar frames are 4:2:0, not %d" % self.subsampling)
+            if self.C == 3 and (self.H | self.W) & 1:
+                raise _lib.StabnetError("MjpegEncoder: a planar 4:2:0 frame of %dx%d has an odd side" % (self.W, self.H))
+        self.frame_bytes = planar_frame_bytes(self.H, self.W, self.C)
         self.restart_mcus = int(default_restart_mcus(channels, subsampling) if restart_mcus is None else restart_mcus)
         self.device = torch.device(device)
         if q_luma is None:
@@ -84,6 +99,12 @@ class MjpegEncoder:
     def _check(self, img):
         if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8:
             raise _lib.StabnetError("MjpegEncoder: expected a uint8 tensor on the GPU (there is no CPU fallback)")
+        if self.planar:
+            if img.dim() == 1:
+                img = img.view(1, -1)
+            if img.dim() != 2 or img.shape[1] != self.frame_bytes or img.stride(1) != 1 or (img.shape[0] > 1 and img.stride(0) < self.frame_bytes):
+                raise _lib.StabnetError("MjpegEncoder: planar frames are uint8 [N, %d] with dense rows, got %s" % (self.frame_bytes, tuple(img.shape)))
+            return img
         return img.reshape(-1, self.H, self.W, self.C).contiguous()
 
     def encode(self, img, out=None, nbytes=None, prof=None):
@@ -96,6 +117,12 @@ class MjpegEncoder:
             out, nbytes = self.out[:n], self.nbytes[:n]
         elif n > self._batch:
             self._reserve(n)
+        if self.planar:
+            _lib.call("stabnet_mjpeg_encode_i420", ptr(img), n, self.H, self.W, self.C, max(img.stride(0), self.frame_bytes), self.restart_mcus,
+                      ptr(self._tables), self._tables.data_ptr() + 128, ptr(self._header), len(self.header), ptr(out), out.stride(0),
+                      ptr(nbytes), ptr(self.workspace), self.workspace.numel(), stream_ptr(self.device),
+                      prof.handle if prof is not None else 0, device=self.device)
+            return out, nbytes
         _lib.call("stabnet_mjpeg_encode", ptr(img), n, self.H, self.W, self.C, self.subsampling, self.restart_mcus,
                   ptr(self._tables), self._tables.data_ptr() + 128, ptr(self._header), len(self.header), ptr(out), out.stride(0),
                   ptr(nbytes), ptr(self.workspace), self.workspace.numel(), stream_ptr(self.device),
@@ -110,6 +137,18 @@ class MjpegEncoder:
 
 class Unsupported(_lib.StabnetError):
     """A JPEG stream the device decoder does not take (progressive, 4:2:2, 12-bit, several scans ...): decode it with Pillow."""
+
+
+def planar_refusal(H, W, channels, subsampling):
+    """None when the planar decoder takes such a stream, else the phrase that names the sampling and the odd side."""
+    if int(channels) != 3:
+        return None
+    if int(subsampling) != 420:
+        return "a %dx%d stream sampled 4:4:4 (planar frames are 4:2:0 or grey)" % (W, H)
+    odd = [n for n, v in (("width %d" % W, W), ("height %d" % H, H)) if v & 1]
+    if odd:
+        return "a 4:2:0 stream of %dx%d with an odd %s (its chroma planes are not H/2 x W/2)" % (W, H, " and ".join(odd))
+    return None
 
 
 def parse(jpeg, blob_ptr=0, blob_cap=0):
@@ -138,12 +177,20 @@ class MjpegDecoder:
     blob + bytes and the one interval is decoded on the device by self-synchronising parallel Huffman decoding
     (csrc/mjpeg_decode_sync.hip: one lane per chunk of chunk_bytes, at most sync_rounds rounds of state hand-over, a sequential
     repair of what is left); the same coefficients, hence the same pixels.  None for chunk_bytes / sync_rounds: the library's defaults.
-    enqueue(...) only launches (capturable in a hipGraph); decode(...) also checks the status words, which synchronises."""
+    enqueue(...) only launches (capturable in a hipGraph); decode(...) also checks the status words, which synchronises.
+    planar=True (any back end): the frame is left in YCbCr -- enqueue / decode fill uint8 [N, frame_bytes], each row Y [H,W] and, for colour,
+    U (Cb) and V (Cr) [H/2,W/2] behind it, dense: what warpRevBundle2_i420 and a planar MjpegEncoder read (stabnet_mjpeg_decode_i420 /
+    _sync_i420).  Grey streams of any size and 4:2:0 streams with even H and W; Unsupported for 4:4:4 and for an odd side."""
 
     def __init__(self, H: int, W: int, channels: int = 3, subsampling="420", device="cuda:0", batch: int = 1, host_entropy: bool = False,
-                 max_bytes=None, parallel: bool = False, chunk_bytes=None, sync_rounds=None):
+                 max_bytes=None, parallel: bool = False, chunk_bytes=None, sync_rounds=None, planar: bool = False):
         self.H, self.W, self.C = int(H), int(W), int(channels)
         self.subsampling = int(subsampling) if self.C == 3 else 0
+        self.planar = bool(planar)
+        why = planar_refusal(self.H, self.W, self.C, self.subsampling) if self.planar else None
+        if why:
+            raise Unsupported("MjpegDecoder: planar=True does not take " + why)
+        self.frame_bytes = planar_frame_bytes(self.H, self.W, self.C)
         self.device = torch.device(device)
         self.host_entropy = bool(host_entropy)
         self.parallel = bool(parallel)
@@ -171,15 +218,16 @@ class MjpegDecoder:
         self._reserve(batch)
 
     @classmethod
-    def for_stream(cls, jpeg, device="cuda:0", batch: int = 1, host_entropy=None, parallel=None, chunk_bytes=None, sync_rounds=None):
+    def for_stream(cls, jpeg, device="cuda:0", batch: int = 1, host_entropy=None, parallel=None, chunk_bytes=None, sync_rounds=None,
+                   planar: bool = False):
         """A decoder for streams shaped like this one (raises Unsupported).  parallel=True: a stream without DRI gets the parallel
         entropy back end; one with DRI keeps one lane per restart interval.  The default (None) is host_entropy for a stream without DRI."""
         i = parse(jpeg)
         if parallel and i["restart"] == 0 and not host_entropy:
             return cls(i["H"], i["W"], i["C"], i["subsampling"] or 420, device=device, batch=batch, parallel=True, chunk_bytes=chunk_bytes,
-                       sync_rounds=sync_rounds)
+                       sync_rounds=sync_rounds, planar=planar)
         return cls(i["H"], i["W"], i["C"], i["subsampling"] or 420, device=device, batch=batch,
-                   host_entropy=(i["restart"] == 0) if host_entropy is None else host_entropy)
+                   host_entropy=(i["restart"] == 0) if host_entropy is None else host_entropy, planar=planar)
 
     def _reserve(self, n: int, in_stride=None):
         if n <= self._batch and in_stride is None:
@@ -199,7 +247,10 @@ class MjpegDecoder:
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=self.device)
         self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
         self.sync_stats = torch.zeros((n, 2), dtype=torch.int32, device=self.device) if self.parallel else None
-        self.out = torch.empty((n, self.H, self.W, self.C), dtype=torch.uint8, device=self.device)
+        if self.planar:
+            self.out = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=self.device)
+        else:
+            self.out = torch.empty((n, self.H, self.W, self.C), dtype=torch.uint8, device=self.device)
         self._batch = n
 
     def slot_bytes(self, nbytes: int) -> int:
@@ -233,10 +284,28 @@ class MjpegDecoder:
             slot[self.blob_max:used].numpy()[...] = np.frombuffer(jpeg, np.uint8)
         return used
 
-    def enqueue(self, d_in, n: int, out, status, stages: int = 3):
+    def enqueue(self, d_in, n: int, out, status, stages: int = 3, prof=None):
         """The launches alone, on the current stream: d_in uint8 [n, in_stride] as uploaded, out uint8 [n,H,W,C] (rows and frames at
         its strides), status int32 [n].  parallel: the chunk statistics of the call land in sync_stats[:n] when d_in is the decoder's
-        own batch (otherwise they are not kept)."""
+        own batch (otherwise they are not kept).  planar: out uint8 [n, frame_bytes] (rows at its stride), stages must stay 3; prof
+        records the launch that crops the planes."""
+        if self.planar:
+            if stages != 3:
+                raise _lib.StabnetError("MjpegDecoder: planar=True has no stages; the BGR decoder stops early for tests")
+            if out is None or out.dim() != 2 or out.shape[1] != self.frame_bytes or out.stride(1) != 1:
+                raise _lib.StabnetError("MjpegDecoder: planar=True fills uint8 [n, %d] with dense rows" % self.frame_bytes)
+            stride = max(out.stride(0), self.frame_bytes)
+            hp = prof.handle if prof is not None else 0
+            if self.parallel:
+                stats = self.sync_stats if d_in is self.d_in and n <= self.sync_stats.shape[0] else None
+                _lib.call("stabnet_mjpeg_decode_sync_i420", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling, ptr(out),
+                          stride, ptr(status), ptr(self.workspace), self.workspace.numel(), self.chunk_bytes, self.sync_rounds, ptr(stats),
+                          stream_ptr(self.device), hp, device=self.device)
+            else:
+                _lib.call("stabnet_mjpeg_decode_i420", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling,
+                          int(self.host_entropy), ptr(out), stride, ptr(status), ptr(self.workspace), self.workspace.numel(),
+                          stream_ptr(self.device), hp, device=self.device)
+            return
         if self.parallel:
             stats = self.sync_stats if d_in is self.d_in and n <= self.sync_stats.shape[0] else None
             _lib.call("stabnet_mjpeg_decode_sync", ptr(d_in), d_in.stride(0), n, self.H, self.W, self.C, self.subsampling, ptr(out),
@@ -255,7 +324,8 @@ class MjpegDecoder:
                                     "code, 4 run past coefficient 63, 8 bad description)" % bad[0])
 
     def decode(self, jpegs, out=None, first_frame: int = 0, check: bool = True):
-        """jpegs: list of bytes of one geometry.  out: the caller's uint8 [N,H,W,C] device tensor instead of the decoder's own."""
+        """jpegs: list of bytes of one geometry.  out: the caller's uint8 [N,H,W,C] device tensor ([N, frame_bytes] for planar=True)
+        instead of the decoder's own."""
         if isinstance(jpegs, (bytes, bytearray, memoryview)):
             jpegs = [jpegs]
         n = len(jpegs)
@@ -270,9 +340,11 @@ class MjpegDecoder:
         self._ev.record(torch.cuda.current_stream(self.device))
         if out is None:
             out = self.out[:n]
-        self.enqueue(self.d_in, n, out.view(n, self.H, self.W, self.C), self.status[:n])
+        self.enqueue(self.d_in, n, out if self.planar else out.view(n, self.H, self.W, self.C), self.status[:n])
         if check:
             self.check(self.status[:n], first_frame)
+        if self.planar:
+            return out
         return out if self.C == 3 else out.view(n, self.H, self.W)
 
 

@@ -54,6 +54,18 @@ which the reference does in NumPy on the host.  Differences forced by the offlin
     frame read black: Y 0 or 16, U = V = 128).  The test list is not read; --fill R is honoured; every message goes to stderr; at the
     end frames, fps and the luma pixels ever uncovered are reported, and <out>.json is written beside a --y4m-out file.  Without
     --y4m-out nothing is written but the report.
+  * --avi-in PATH [--avi-out PATH] [--y4m-out PATH|-]: a 4:2:0 (or grey) Motion-JPEG .avi in YCbCr end to end, frame by frame in bounded
+    memory.  Per frame the compressed bytes are uploaded once, the decoder leaves its Y / Cb / Cr planes as they are
+    (csrc/mjpeg_decode.hip, stabnet_mjpeg_decode_i420), the network reads the Y plane (JFIF is full range: no table), the planes are
+    warped as they are (stabnet_warp_rev_bundle2_i420; taps outside the frame read Y 0, U = V = 128) and the encoder starts from the
+    planes (csrc/mjpeg.hip, stabnet_mjpeg_encode_i420): no colour conversion and no chroma resampling in either direction, and only
+    compressed bytes cross PCIe.  --avi-out writes a 4:2:0 (grey) MJPG .avi at --jpeg-quality and the input's rate (or --fps), --y4m-out
+    a C420jpeg / Cmono full-range stream at the input's rate; both may be given, with neither the run is a dry run.  Frame 0 seeds the
+    ring and is written as decoded.  --fill R, --interp cubic, --scene-cut and --entropy parallel work as elsewhere; <out>.json holds
+    the Y4M loop's report plus decode_backend and jpeg.  The test list is not read; every message goes to stderr.  A file that is no
+    MJPG .avi, a first frame the planar decoder does not take (4:4:4, 4:2:2, an odd side: such clips keep the test-list route), and a
+    later frame that differs or does not decode each end the run with one sentence and a non-zero status; the files written so far are
+    closed valid.
   * --scene-cut [T] [--scene-gap 8]: scene cuts.  The loop is recurrent -- every frame is regressed against 32 earlier stabilised frames
     -- so after a cut the network would warp the new scene against the old one.  With the flag, the frame's graph starts with a cut
     decision on the GPU (csrc/scene.hip: the distance d between the 4 x 4 x 32 tile histograms of consecutive grey frames, a cut when
@@ -167,13 +179,46 @@ def build_parser():
     p.add_argument('--y4m-out', default=None, metavar='PATH|-',
                    help='with --y4m-in: write the stabilised stream (the input\'s size, chroma tag, frame rate, aspect and range) to this '
                         'file, with <PATH>.json beside it, or to stdout with -; without it only the report is printed')
+    p.add_argument('--avi-in', default=None, metavar='PATH',
+                   help='stabilise a 4:2:0 (or grey) Motion-JPEG .avi frame by frame in bounded memory, in YCbCr end to end: the planes are '
+                        'decoded on the GPU as they are (stabnet_mjpeg_decode_i420), warped as they are (stabnet_warp_rev_bundle2_i420) and '
+                        'encoded as they are (stabnet_mjpeg_encode_i420); only compressed bytes cross PCIe; the test list is not read; '
+                        'every message goes to stderr')
+    p.add_argument('--avi-out', default=None, metavar='PATH',
+                   help='with --avi-in: write the stabilised clip as a 4:2:0 (or grey) Motion-JPEG .avi at --jpeg-quality and the input\'s '
+                        'frame rate (or --fps), with <PATH>.json beside it; --y4m-out PATH|- may be given as well or instead (C420jpeg / '
+                        'Cmono, full range); with neither only the report is printed')
     return p
 
 
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
-    if args.y4m_out is not None and args.y4m_in is None:
+    given = sys.argv[1:] if argv is None else list(argv)
+    args.fps_given = any(a == '--fps' or a.startswith('--fps=') for a in given)
+    if args.avi_out is not None and args.avi_in is None:
+        p.error('--avi-out needs --avi-in: it is the output of the Motion-JPEG stream loop')
+    if args.avi_in is not None:
+        if args.y4m_in is not None:
+            p.error('--avi-in and --y4m-in each name the input of a stream loop: give one of them')
+        if args.jpeg_subsampling != '420':
+            p.error('--avi-in keeps the planes of a 4:2:0 clip as they are: --jpeg-subsampling 444 is not available in the Motion-JPEG stream loop')
+        if args.pipeline:
+            p.error('--avi-in runs its own serial loop: it is not available with --pipeline')
+        if args.mjpg:
+            p.error('--avi-in writes its Motion-JPEG clip with --avi-out: it is not available with --mjpg')
+        if args.score:
+            p.error('--avi-in keeps no frames to score: it is not available with --score')
+        if args.synthetic:
+            p.error('--avi-in names the input: it is not available with --synthetic')
+        if args.fill in ('auto', 'adaptive', 'history'):
+            p.error('--avi-in honours --fill R only: --fill %s is not available in the Motion-JPEG stream loop' % args.fill)
+        if not 1 <= args.jpeg_quality <= 100:
+            p.error('--jpeg-quality needs 1 <= Q <= 100, got %r' % (args.jpeg_quality,))
+        if args.fps_given and not 0.0 < args.fps < float('inf'):
+            p.error('--fps needs a positive finite rate, got %r' % (args.fps,))
+        args.ingest, args.output_size, args.decode = 'device', 'source', 'device'
+    if args.y4m_out is not None and args.y4m_in is None and args.avi_in is None:
         p.error('--y4m-out needs --y4m-in: it is the output of the Y4M loop')
     if args.y4m_in is not None:
         if args.pipeline:
@@ -699,6 +744,188 @@ def main_y4m(args):
             os.dup2(os.open(os.devnull, os.O_WRONLY), sys.stdout.fileno())          # nothing more to say to a closed pipe, at exit either
 
 
+class AviStreamError(RuntimeError):
+    """--avi-in: a sentence that ends the run (a file, a first frame or a later frame that is refused)."""
+
+
+def avi_probe(args):
+    """--avi-in, before the GPU is touched: the opened reader and the parsed header of its first frame, or AviStreamError with the sentence.
+    -> (reader, info of mjpeg.parse)"""
+    from stabnet_amd import _lib, avi, mjpeg
+    try:
+        rd = avi.AviMjpegReader(args.avi_in, mapped=True)
+    except (avi.AviError, OSError, ValueError) as e:
+        raise AviStreamError('%s is not a Motion-JPEG .avi that can be read: %s' % (args.avi_in, e))
+    if len(rd) == 0:
+        raise AviStreamError('%s holds no frame' % args.avi_in)
+    route = 'the test-list route (--decode device, or Pillow) still reads such clips'
+    try:
+        info = mjpeg.parse(rd.jpeg(0))
+    except mjpeg.Unsupported as e:
+        raise AviStreamError('the first frame of %s is outside the planar decoder\'s scope (%s); %s' % (args.avi_in, e, route))
+    except _lib.StabnetError as e:
+        raise AviStreamError('the first frame of %s is no complete baseline JPEG stream (%s)' % (args.avi_in, e))
+    why = mjpeg.planar_refusal(info['H'], info['W'], info['C'], info['subsampling'])
+    if why:
+        raise AviStreamError('the planar decoder does not take the first frame of %s: %s; %s' % (args.avi_in, why, route))
+    return rd, info
+
+
+def run_avi(args, rd, info, stream, H, W, dev, y4m_file, avi_path):
+    """--avi-in: the online loop over the frames of a 4:2:0 (or grey) Motion-JPEG .avi, in YCbCr end to end and in bounded memory -- one
+    pinned slot and fixed device buffers, no per-frame list; only the coverage image accumulates (the reader keeps two ints per frame).
+    Per frame: the compressed bytes (blob + stream, or blob + host coefficients for a clip without restart markers under --entropy auto)
+    into the pinned slot and up in one copy; the planes decoded as they are into a fixed buffer (stabnet_mjpeg_decode_i420); the frame's
+    graph on the Y plane's view (ingest without a table: JFIF is full range; then the network); the planar warp into the fixed output
+    buffer; for --avi-out the planar encoder and the download of the stream's bytes, for --y4m-out the download of the planes.  Frame 0
+    seeds the ring and is written as decoded (re-encoded from its planes for the .avi, so that every frame has the run's tables and
+    restart interval).  A later frame that is refused ends the run with AviStreamError after the outputs are closed valid.
+    -> the report that <out>.json holds."""
+    import json
+    import torch
+    from stabnet_amd import _lib, warp, y4m
+    from stabnet_amd.avi import AviMjpegWriter
+    from stabnet_amd.ingest import FrameIngest
+    from stabnet_amd.mjpeg import MjpegDecoder, MjpegEncoder, default_restart_mcus
+    say = lambda *a: print(*a, file=sys.stderr)
+    SH, SW, planes = info['H'], info['W'], info['C']
+    lanes = info['restart'] != 0
+    parallel = not lanes and args.entropy == 'parallel'
+    backend = 'restart lanes' if lanes else ('parallel' if parallel else 'host coefficients')
+    fps = args.fps if args.fps_given else (rd.rate / rd.scale if rd.rate > 0 and rd.scale > 0 else args.fps)
+    rate_scale = (rd.rate, rd.scale) if rd.rate > 0 and rd.scale > 0 else (30, 1)
+    window = warp.ratio_window(SH, SW, args.fill) if args.fill is not None else None
+    say('note: --avi-in: %d MJPG frames %dx%d (%s) at %.3f fps, entropy decoding: %s; the planes stay YCbCr: the Y plane feeds the %dx%d network, '
+        'the planes are warped as they are (taps outside the frame read Y = 0, U = V = 128)'
+        % (len(rd), SW, SH, 'grey' if planes == 1 else '4:2:0', rd.fps, backend, W, H))
+    if window is not None:
+        say('note: --fill %g: every written frame is the window (y0, x0, wh, ww) = %s of the stabilised frame, at %dx%d' % (args.fill, list(window), SW, SH))
+    dec = MjpegDecoder(SH, SW, planes, info['subsampling'] or 420, device=dev, host_entropy=not lanes and not parallel, parallel=parallel, planar=True)
+    fb = dec.frame_bytes
+    ing = FrameIngest(SH, SW, 1, H, W, gray=args.gray_weights, device=dev)
+    dev_in, dev_out = (torch.empty((1, fb), dtype=torch.uint8, device=dev) for _ in range(2))
+    y_view = dev_in[0, :SH * SW].view(SH, SW)
+    ws = torch.empty(2 * (H // 4) * (W // 4), dtype=torch.float32, device=dev)
+    black = torch.zeros((SH, SW), dtype=torch.int32, device=dev)
+    enc = aw = yw = pin_out = None
+    restart = default_restart_mcus(planes, 420)
+    if avi_path is not None:
+        enc = MjpegEncoder(SH, SW, planes, quality=args.jpeg_quality, restart_mcus=restart, device=dev, planar=True)
+        aw = AviMjpegWriter(avi_path, SW, SH, fps)
+    if y4m_file is not None:
+        yw = y4m.Y4mWriter(y4m_file, SW, SH, rate_scale, 'mono' if planes == 1 else '420jpeg', colour_range='full')
+        pin_out = torch.empty(fb, dtype=torch.uint8).pin_memory()
+
+    def decode(t):
+        """frame t -> dev_in; StabnetError names the frame"""
+        jpeg = rd.jpeg(t)
+        need = dec.slot_bytes(len(jpeg))
+        if need > dec.in_stride:
+            dec._reserve(1, (need + 4095) & ~4095)
+        used = dec.stage(jpeg, dec.h_in[0], t)
+        dec.d_in[0, :used].copy_(dec.h_in[0, :used], non_blocking=True)
+        dec.enqueue(dec.d_in, 1, dev_in, dec.status[:1])
+        dec.check(dec.status[:1], t)                                               # (synchronises: the slot is free again)
+
+    def write(frame):
+        """the planes of one output frame (device, [1, fb]) to the outputs; False when the consumer of a Y4M pipe has gone"""
+        if aw is not None:
+            aw.write(enc.encode_bytes(frame)[0])
+        if yw is not None:
+            pin_out.copy_(frame[0])
+            torch.cuda.synchronize()
+            return yw.write(pin_out.numpy())
+        return True
+
+    length, tot_time, failed = 0, 0.0, None
+    scene_cuts = [] if args.scene_cut is not None else None
+    try:
+        decode(0)
+        stream.start_u8(y_view, ing)                                               # ring = 32 x the first frame
+        torch.cuda.synchronize()
+        alive = write(dev_in)                                                      # the first frame as decoded (deploy_bundle.py:215)
+        for t in range(1, len(rd)):
+            if not alive:
+                break
+            try:
+                decode(t)
+            except _lib.StabnetError as e:
+                failed = 'frame %d of %s is refused: %s; the outputs hold the %d frames before it' % (t, args.avi_in, e, t)
+                break
+            torch.cuda.synchronize()
+            start = time.time()
+            r = stream.step_u8(y_view, ing)
+            warp.warpRevBundle2_i420(dev_in[0], r['x_map'], r['y_map'], (SH, SW), planes, window=window, border_y=0, black_count=black,
+                                     out=dev_out[0], workspace=ws, interp=args.interp)
+            torch.cuda.synchronize()
+            tot_time += time.time() - start
+            if scene_cuts is not None and int(r['scene_cut'][0]):
+                scene_note(scene_cuts, t, 1, int(r['scene_dist'].cpu().numpy()[0]), H, W, say)
+            alive = write(dev_out)
+            length += 1
+            if length % 10 == 0:
+                say('length: ' + str(length))
+                say('fps={}'.format(length / tot_time))
+    finally:
+        say('total length={}'.format(length + 2))
+        if aw is not None:
+            aw.close()
+        if yw is not None:
+            yw.close()
+    if yw is not None and yw.broken:
+        say('note: the consumer of --y4m-out closed the stream after %d frames' % yw.frames_written)
+    report = {'input': {'path': args.avi_in, 'width': SW, 'height': SH, 'frames': len(rd), 'rate': rd.rate, 'scale': rd.scale,
+                        'sampling': 'grey' if planes == 1 else '420', 'restart': info['restart']},
+              'network_size': [H, W], 'colour_range': 'full', 'border_y': 0, 'interp': args.interp,
+              'window': [float(v) for v in window] if window is not None else None, 'frames': length + 1,
+              'pixels_ever_uncovered': int((black > 0).sum().item()), 'max_uncovered_count': int(black.max().item()),
+              'decode_backend': backend, 'jpeg': {'quality': args.jpeg_quality, 'restart_mcus': restart} if aw is not None else None}
+    if scene_cuts is not None:
+        report.update(scene_cuts=[t for t, _, _ in scene_cuts], scene_threshold=args.scene_cut)
+    if failed:
+        report['stopped'] = failed
+    say('avi: %d frames (the first as decoded, %d stabilised), fps=%s (the step and the warp), %d of %d luma pixels were uncovered in some frame'
+        % (length + 1, length, length / tot_time if tot_time > 0 else 'n/a', report['pixels_ever_uncovered'], SH * SW))
+    for path in [p for p in (avi_path, y4m_file if isinstance(y4m_file, str) else None) if p is not None][:1]:
+        with open(path + '.json', 'w') as f:
+            json.dump(report, f, indent=1)
+            f.write('\n')
+        say('wrote %s' % (path + '.json'))
+    if aw is not None:
+        say('wrote %s (%d frames, MJPG q%d 4:2:0 planar, %.3f fps)' % (avi_path, aw.frames_written, args.jpeg_quality, fps))
+    if yw is not None and isinstance(y4m_file, str):
+        say('wrote %s (%d frames)' % (y4m_file, yw.frames_written))
+    if failed:
+        raise AviStreamError(failed)
+    return report
+
+
+def main_avi(args):
+    """--avi-in: stdout may be the video (--y4m-out -), so everything the driver prints goes to stderr; whatever is refused ends the run
+    with its sentence and a non-zero status -- before anything touches the GPU when the file or its first frame is what is refused."""
+    import contextlib
+    real_stdout = sys.stdout.buffer
+    with contextlib.redirect_stdout(sys.stderr):
+        try:
+            rd, info = avi_probe(args)
+        except AviStreamError as e:
+            sys.exit('deploy_bundle.py: --avi-in: %s' % e)
+        import torch
+        from stabnet_amd import _lib, avi, y4m
+        stream, H, W, dev = setup_stream(args)
+        try:
+            run_avi(args, rd, info, stream, H, W, dev, real_stdout if args.y4m_out == '-' else args.y4m_out, args.avi_out)
+        except (AviStreamError, avi.AviError, y4m.Y4mError, _lib.StabnetError, OSError) as e:
+            sys.exit('deploy_bundle.py: --avi-in: %s' % e)
+        finally:
+            torch.cuda.synchronize()
+    if args.y4m_out == '-':
+        try:
+            real_stdout.flush()
+        except BrokenPipeError:
+            os.dup2(os.open(os.devnull, os.O_WRONLY), sys.stdout.fileno())          # nothing more to say to a closed pipe, at exit either
+
+
 def setup_stream(args):
     """The network of a run from the flags: the size, the weights, the stream with its frame graph.  -> (stream, H, W, device)"""
     import torch
@@ -739,6 +966,8 @@ def main():
     args = parse_args()
     if args.y4m_in is not None:
         return main_y4m(args)
+    if args.avi_in is not None:
+        return main_avi(args)
     import torch
     from stabnet_amd import synthetic, warp
     stream, H, W, dev = setup_stream(args)

@@ -732,6 +732,18 @@ int stabnet_mjpeg_encode(const unsigned char* img, int N, int H, int W, int C, i
                          const unsigned short* luma64_dev, const unsigned short* chroma64_dev, const unsigned char* header_dev,
                          int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
                          size_t workspace_bytes, void* stream, void* prof);
+/* The same streams from a PLANAR frame: src holds N frames frame_stride_bytes apart (>= the frame's size), each Y [H,W] and, for
+ * planes = 3, U [H/2,W/2] and V [H/2,W/2] behind it, all dense -- the layout stabnet_warp_rev_bundle2_i420 writes and
+ * stabnet_mjpeg_decode_i420 fills.  The samples are taken as the JFIF components they are (full range, chroma centred): the load
+ * stage of mjpeg_transform_planar_kernel is the level shift alone, no colour arithmetic and no 2x2 mean; partial MCUs replicate the
+ * edge sample of each plane.  Header, tables, stabnet_mjpeg_max_bytes and stabnet_mjpeg_workspace_bytes are those of C = planes,
+ * subsampling 420, and every other argument is stabnet_mjpeg_encode's.  planes = 3 needs even H and W; any base pointer and stride
+ * are accepted (aligned dwords are read where the address allows).  Refused with STABNET_ERR_BAD_ARG before any launch: planes not 1 | 3,
+ * an odd side with planes = 3, a stride below the frame's size, and what stabnet_mjpeg_encode refuses. */
+int stabnet_mjpeg_encode_i420(const unsigned char* src, int N, int H, int W, int planes, size_t frame_stride_bytes, int restart_mcus,
+                              const unsigned short* luma64_dev, const unsigned short* chroma64_dev, const unsigned char* header_dev,
+                              int header_bytes, unsigned char* out, size_t out_stride, int* out_bytes, void* workspace,
+                              size_t workspace_bytes, void* stream, void* prof);
 
 /* ---- in front of the ingest: Motion-JPEG decoding of the frame as read (the reference reads its clips with cv2.VideoCapture) ----
  * Baseline JPEG (SOF0, 8-bit samples, 8-bit DQT, Huffman tables of the stream's own DHT or Annex K when it has none; grey 1x1,
@@ -794,6 +806,21 @@ int stabnet_mjpeg_decode_sync(const unsigned char* in, size_t in_stride, int N, 
                               int chunk_bytes, int rounds, int* stats, void* stream);
 int stabnet_mjpeg_entropy_sync_host(const unsigned char* jpeg, size_t nbytes, const unsigned char* blob, size_t blob_bytes, short* coef,
                                     size_t coef_count, int chunk_bytes, int rounds, int* stats);                            /* host */
+/* The decoder's planes as they are, for the planar warp and the planar encoder: stabnet_mjpeg_decode / _sync without the colour stage.
+ * The arguments of the twin without row_stride and stages, plus prof (NULL, or a profiler: only the new launch is recorded).  out
+ * receives N frames frame_stride_bytes apart, each Y [H,W] followed, for C = 3, by U (Cb) [H/2,W/2] and V (Cr) [H/2,W/2], all dense:
+ * what stabnet_warp_rev_bundle2_i420 reads.  The entropy and IDCT launches are the twin's; mjpegd_planes_kernel then crops the
+ * MCU-padded planes to the frame (no arithmetic: Y is libjpeg-turbo's Y exactly, Cb / Cr are the samples its upsampler starts from).
+ * Any out pointer and any stride >= the frame's size are accepted; nothing outside a frame's own H * W * 3 / 2 (grey: H * W) bytes
+ * is written.  Taken: grey streams of any size, 4:2:0 streams with even H and W.  Refused with STABNET_ERR_BAD_ARG before any launch:
+ * 4:2:0 with an odd side, 4:4:4 (both keep the BGR entries), a stride below the frame's size, null pointers, and what the twin
+ * refuses.  The workspace is the twin's.  The status words are zeroed by a launch of their own instead of the twins' memset node. */
+int stabnet_mjpeg_decode_i420(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, int coef_uploaded,
+                              unsigned char* out, size_t frame_stride_bytes, int* status, void* workspace, size_t workspace_bytes, void* stream,
+                              void* prof);
+int stabnet_mjpeg_decode_sync_i420(const unsigned char* in, size_t in_stride, int N, int H, int W, int C, int subsampling, unsigned char* out,
+                                   size_t frame_stride_bytes, int* status, void* workspace, size_t workspace_bytes, int chunk_bytes, int rounds,
+                                   int* stats, void* stream, void* prof);
 
 /* ---- in front of the path: frame ingest (config.py:6-21 cvt_img2train; deploy_bundle.py:215,303 cv2.resize) ----
  * A uint8 frame as read from the video, of any size, to the network's grey input and the network-size colour frame.
