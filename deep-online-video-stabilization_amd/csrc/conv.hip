@@ -505,6 +505,7 @@ static int device_cus(int& cus) {
     cus = cached;
     return STABNET_OK;
 }
+static thread_local int g_last_launch_kind = -1;   // stabnet_conv_last_launch_kind
 static int g_reserved_cus = 0;    // CUs the persistent grids leave to a communication stream (stabnet_conv_reserve_cus)
 // persistent grids are sized for the CUs that are NOT reserved (never fewer than an eighth of the chip)
 static int usable_cus(int cus) { return std::max(cus / 8, cus - std::max(0, g_reserved_cus)); }
@@ -703,6 +704,7 @@ int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands
     SN_REQUIRE(a.splitk == 1 || a.partial != nullptr, "conv: split-K needs a workspace");
     const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, true, lowk_ring);
     SN_REQUIRE(r.family != CONV_IGEMM || a.x_ld == a.Cin, "conv: a strided input (x_ld %d != Cin %d) needs the ring kernel", a.x_ld, a.Cin);
+    g_last_launch_kind = r.prof_kind;
     const bool rec = prof != nullptr && prof->begin(st);
     int rc;
     switch (r.family) {
@@ -781,6 +783,7 @@ int conv_launch_pair(const ConvArgs& a, const ConvPair& pr, hipStream_t st, Prof
     r.family = packed ? CONV_PACKED : CONV_RING_PRO;
     r.operand = packed ? 4 : 0;
     r.kg = r.pro = 1;
+    g_last_launch_kind = pro ? route_prof_kind(r) : PK_KERNEL_CONV_PAIR + mode * 2 + (bk32 ? 1 : 0);
     const bool rec = prof != nullptr && prof->begin(st);
     int rc;
     if (pro) {
@@ -833,6 +836,7 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
     P.c3.splitk = 1;                                                  // the accumulators handed to the epilogue are the full sum
     P.c3.steps_per_split = conv_total_steps(c3);
     const int tiles_m = cdiv(c2.M, 64);
+    g_last_launch_kind = PK_KERNEL_CONV_B2B + (c2.Cout == 128 ? 1 : 0);
     const bool rec = prof != nullptr && prof->begin(st);
     if (c2.Cout == 64) {
         conv_b2b_f32_kernel<2><<<std::min(tiles_m, sw().b2b_wgs_per_cu * usable_cus(cus)), 256, 0, st>>>(P);
@@ -876,14 +880,17 @@ static int fill_args(ConvArgs& a, const float* x, const float* w, const float* b
 
 extern "C" {
 
-/* Tuning hook: force the tile (0 = 128x128, 1 = 128x64, 2 = 64x64) and split-K of every subsequent convolution;
- * tile < 0 restores the built-in choice.  Not thread-safe; used by tools/autotune.py only. */
+/* CUs the persistent grids (ring, back-to-back, the N groups of the A-stationary and patch kernels) leave free from the next launch
+ * on: usable_cus() = max(CUs / 8, CUs - reserved).  A negative value stores 0; returns the previous value.  Which workgroup computes
+ * which tile changes with it, the arithmetic of a tile does not: results are bit-identical for every value.  Not thread-safe. */
 int stabnet_conv_reserve_cus(int reserved) {
     const int prev = g_reserved_cus;
     g_reserved_cus = reserved < 0 ? 0 : reserved;
     return prev;
 }
 
+/* Tuning hook: force the tile (0 = 128x128, 1 = 128x64, 2 = 64x64) and split-K of every subsequent convolution;
+ * tile < 0 restores the built-in choice.  Not thread-safe; used by tools/autotune.py and the tests. */
 void stabnet_conv_tuning_override(int tile, int splitk) {
     g_force_tile = tile < 0 ? -1 : tile;
     g_force_split = splitk;
@@ -932,6 +939,11 @@ int stabnet_conv2d_fwd(const float* x, const float* w_ohwi, const float* bias, c
     return stabnet_conv2d_fwd_ex(x, w_ohwi, bias, in_scale, in_shift, residual, res_H, res_W, res_stride, nullptr, nullptr,
                                  y, N, H, W, Cin, Cout, KH, KW, stride, pad, relu_out, workspace, workspace_bytes, stream);
 }
+
+/* The Profiler kind (stabnet_prof_kind_name) of the convolution kernel this thread launched last through conv_launch() -- the forward
+ * operators, dgrad, the layers of a plan --, conv_launch_pair() or conv_b2b_launch(): the route the launch itself took with its
+ * pointers bound, not a plan-time view.  -1 before the first launch.  Host only. */
+int stabnet_conv_last_launch_kind(void) { return g_last_launch_kind; }
 
 int stabnet_conv2d_fwd_ex(const float* x, const float* w_ohwi, const float* bias, const float* in_scale,
                           const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,

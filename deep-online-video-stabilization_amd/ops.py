@@ -5,7 +5,29 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import StabnetError
 from ._tensor import dev_f32, empty, ptr, stream_ptr
+
+
+def _out(out, shape, like):
+    """The tensor an operator writes: the caller's `out` (contiguous float32 of `shape` on like's device -- a view of a larger buffer
+    will do) or a fresh one."""
+    if out is None:
+        return empty(tuple(shape), like)
+    if not (isinstance(out, torch.Tensor) and out.device == like.device and out.dtype == torch.float32 and out.is_contiguous() and
+            tuple(out.shape) == tuple(shape)):
+        raise StabnetError("out: expected a contiguous float32 tensor of shape %s on %s" % (tuple(shape), like.device))
+    return out
+
+
+def _workspace(workspace, nbytes, like):
+    """(tensor, bytes) of an operator's scratch: the caller's `workspace` (contiguous, at least `nbytes` long) or a fresh one."""
+    if workspace is None:
+        return torch.empty(max(nbytes, 4), dtype=torch.uint8, device=like.device), nbytes
+    have = workspace.numel() * workspace.element_size()
+    if not (workspace.device == like.device and workspace.is_contiguous() and have >= nbytes):
+        raise StabnetError("workspace: expected a contiguous tensor of at least %d bytes on %s" % (nbytes, like.device))
+    return workspace, have
 
 
 def pack_conv_weight(w_hwio, cin_pad: int = 16) -> np.ndarray:
@@ -23,7 +45,7 @@ def unpack_conv_weight(w_ohwi, cin: int) -> np.ndarray:
 
 
 def conv2d(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=None, res_stride=1, stride=1, pad=0,
-           relu_out=False, out_scale=None, out_shift=None):
+           relu_out=False, out_scale=None, out_shift=None, out=None, workspace=None):
     x = dev_f32(x, "x")
     w = dev_f32(w_ohwi, "w")
     N, H, W, Cin = x.shape
@@ -31,10 +53,9 @@ def conv2d(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=None, re
     assert Cw == Cin, "weight Cin %d != input Cin %d" % (Cw, Cin)
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
-    y = empty((N, Ho, Wo, Cout), x)
+    y = _out(out, (N, Ho, Wo, Cout), x)
     L = _lib.lib()
-    ws_bytes = L.stabnet_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(workspace, int(L.stabnet_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)), x)
     rH, rW = (residual.shape[1], residual.shape[2]) if residual is not None else (0, 0)
     _lib.call("stabnet_conv2d_fwd_ex", ptr(x), ptr(w), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(residual), rH, rW,
               res_stride, ptr(out_scale), ptr(out_shift), ptr(y), N, H, W, Cin, Cout, KH, KW, stride, pad,
@@ -42,8 +63,20 @@ def conv2d(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=None, re
     return y
 
 
+def conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride=1, pad=0):
+    """Bytes of scratch conv2d asks for (split-K slabs; 0 without a K split)."""
+    return int(_lib.lib().stabnet_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad))
+
+
+def conv2d_packed_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride=1, pad=0, splitk=0):
+    """Bytes of scratch conv2d_packed asks for: the planned split's slabs, or those of the caller's `splitk`."""
+    Ho = (H + 2 * pad - KH) // stride + 1
+    Wo = (W + 2 * pad - KW) // stride + 1
+    return max(conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad), max(splitk, 0) * N * Ho * Wo * Cout * 4)
+
+
 def conv2d_packed(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=None, res_stride=1, stride=1, pad=0,
-                  relu_out=False, out_scale=None, out_shift=None, splitk=0):
+                  relu_out=False, out_scale=None, out_shift=None, splitk=0, out=None, workspace=None):
     """conv2d on the packed split kernels (stabnet_conv2d_fwd_packed): float32-level results on the bf16 matrix pipe."""
     x = dev_f32(x, "x")
     w = dev_f32(w_ohwi, "w")
@@ -52,14 +85,13 @@ def conv2d_packed(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=N
     assert Cw == Cin, "weight Cin %d != input Cin %d" % (Cw, Cin)
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
-    y = empty((N, Ho, Wo, Cout), x)
+    y = _out(out, (N, Ho, Wo, Cout), x)
     L = _lib.lib()
     n_img = int(L.stabnet_conv_weight_image_floats(Cout, KH, KW, Cin))
     img = torch.empty(max(n_img, 1), dtype=torch.float32, device=x.device)
     if n_img > 0:                      # (Cin not a multiple of 32: no image exists and the call runs the exact-f32 kernels on w_ohwi)
         _lib.call("stabnet_conv_weight_split_image", ptr(w), Cout, KH, KW, Cin, ptr(img), stream_ptr(x.device), device=x.device)
-    ws_bytes = max(int(L.stabnet_conv2d_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)), max(splitk, 0) * N * Ho * Wo * Cout * 4)
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(workspace, conv2d_packed_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad, splitk), x)
     rH, rW = (residual.shape[1], residual.shape[2]) if residual is not None else (0, 0)
     _lib.call("stabnet_conv2d_fwd_packed", ptr(x), ptr(w), ptr(img), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(residual), rH, rW,
               res_stride, ptr(out_scale), ptr(out_shift), ptr(y), N, H, W, Cin, Cout, KH, KW, stride, pad, int(relu_out), int(splitk),
@@ -68,7 +100,7 @@ def conv2d_packed(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=N
 
 
 def conv3x3_conv1x1(x, w2_ohwi, mid_scale, mid_shift, w3_ohwi, bias3=None, residual=None, res_stride=1, stride=1, relu_out=False,
-                    out_scale=None, out_shift=None, x_ch0=0, res_ch0=0):
+                    out_scale=None, out_shift=None, x_ch0=0, res_ch0=0, out=None):
     """The tail of a bottleneck unit as one launch (stabnet_conv3x3_conv1x1_fwd): conv2 3x3 (pad 1, `stride`) -> folded BN + ReLU
     -> conv3 1x1 with conv2d's epilogue.  x [N,H,W,Cx]: the conv reads channels x_ch0 .. x_ch0 + C of every pixel (Cx > C: the
     inference plan's merged shortcut|conv1 buffer); residual [N,rH,rW,Cr]: channels res_ch0 .. res_ch0 + Cout likewise."""
@@ -81,7 +113,7 @@ def conv3x3_conv1x1(x, w2_ohwi, mid_scale, mid_shift, w3_ohwi, bias3=None, resid
     assert tuple(w2.shape) == (C, 3, 3, C) and tuple(w3.shape[1:]) == (1, 1, C) and x_ch0 + C <= Cx
     Ho = (H + 2 - 3) // stride + 1
     Wo = (W + 2 - 3) // stride + 1
-    y = empty((N, Ho, Wo, Cout), x)
+    y = _out(out, (N, Ho, Wo, Cout), x)
     rH = rW = res_ld = 0
     rp = 0
     if residual is not None:
@@ -146,15 +178,21 @@ def conv2d_wgrad_rowrun(x, dy, w_shape, stride=1, pad=0, dw=None):
     return dw
 
 
-def conv2d_dgrad(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None):
+def conv2d_dgrad_workspace_bytes(x_shape, w_shape, stride=1, pad=0, split=False):
+    """Bytes of scratch conv2d_dgrad (split=True: conv2d_dgrad_split) asks for."""
+    N, H, W, Cin = x_shape
+    Cout, KH, KW, _ = w_shape
+    fn = _lib.lib().stabnet_conv2d_dgrad_split_workspace_bytes if split else _lib.lib().stabnet_conv2d_dgrad_workspace_bytes
+    return int(fn(N, H, W, Cin, Cout, KH, KW, stride, pad))
+
+
+def conv2d_dgrad(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None, out=None, workspace=None):
     dy = dev_f32(dy, "dy")
     w = dev_f32(w_ohwi, "w")
     N, H, W, Cin = x_shape
     Cout, KH, KW, _ = w.shape
-    dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
-    L = _lib.lib()
-    nbytes = L.stabnet_conv2d_dgrad_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    dx = _out(out, x_shape, dy)
+    ws, nbytes = _workspace(workspace, conv2d_dgrad_workspace_bytes(x_shape, w.shape, stride, pad), dy)
     _lib.call("stabnet_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), ptr(residual), N, H, W, Cin, Cout, KH, KW, stride, pad,
               ptr(ws), nbytes, stream_ptr(dy.device), device=dy.device)
     return dx
@@ -214,15 +252,16 @@ def conv_weight_split_images_table(w_base, img_base, entries):
     return img_base
 
 
-def conv2d_dgrad_split(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None, dx=None, workspace=None):
+def conv2d_dgrad_split(dy, w_ohwi, x_shape, stride=1, pad=0, residual=None, dx=None, workspace=None, out=None):
     """conv2d_dgrad as the training step runs it with split operands: -> (dx, packed), packed = True if the launch went to a packed
-    split kernel (False: the exact-f32 kernels took it).  residual may be dx (given)."""
+    split kernel (False: the exact-f32 kernels took it).  residual may be dx (given; `out` is another name of `dx`)."""
     import ctypes
     N, H, W, Cin = x_shape
     Cout, KH, KW, _ = w_ohwi.shape
-    if dx is None:
-        dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
-    nbytes = int(_lib.lib().stabnet_conv2d_dgrad_split_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, pad))
+    assert dx is None or out is None, "dx and out name the same tensor: give one"
+    if dx is None:                     # (a dx of any shape with x_shape's element count is taken as it is)
+        dx = _out(out, x_shape, dy)
+    nbytes = conv2d_dgrad_workspace_bytes(x_shape, w_ohwi.shape, stride, pad, split=True)
     if workspace is None:
         workspace = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dy.device)
     route = ctypes.c_int(-1)

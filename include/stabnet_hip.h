@@ -118,6 +118,9 @@ int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, 
 /* The Profiler kind (see stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry, with
  * (prologue != 0) or without in_scale / in_shift: which kernel the call runs.  Host only, no GPU needed; < 0 on a bad geometry. */
 int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int prologue, int splitk);
+/* The Profiler kind of the convolution kernel the calling thread launched last (forward operators, back-to-back, dgrad, the conv
+ * layers of a plan): the route the launch itself took with its pointers bound.  -1 before the first launch.  Host only. */
+int stabnet_conv_last_launch_kind(void);
 /* The tail of a slim bottleneck_v2 unit as ONE launch (resnet_v2 `bottleneck`, called at s_net_bundle_nobm.py:252-253; what the
  * inference plan runs for the block-1 / block-2 units of a frame): conv2 (3x3, pad 1, stride 1 | 2, C -> C channels, C = 64 | 128,
  * no bias) -> folded batch_norm (mid_scale, mid_shift) + ReLU -> conv3 (1x1, C -> Cout, Cout % C == 0) with conv2d_fwd_ex's
@@ -302,8 +305,10 @@ int stabnet_probe_comm_proxy(const float* src, float* dst, long n_floats, int wo
                              void* stream);
 /* CUs the persistent convolution kernels leave free (0 = none, the default): their grids are sized for (CUs - reserved) x
  * workgroups-per-CU, so that a collective's kernel on a communication stream finds CU slots without waiting for a kernel
- * boundary.  A process-wide setting read at launch time (train.Trainer sets it from STABNET_COMM_RESERVED_CUS when it has a
- * process group); returns the previous value. */
+ * boundary.  Never fewer than an eighth of the chip stays usable: the grids are sized for max(CUs / 8, CUs - reserved) CUs, so any
+ * reserved >= CUs - CUs / 8 behaves alike; a negative value stores 0.  The setting moves tiles between workgroups only: results are
+ * bit-identical for every value.  A process-wide setting read at launch time (train.Trainer sets it from STABNET_COMM_RESERVED_CUS
+ * when it has a process group); returns the previous value. */
 int stabnet_conv_reserve_cus(int reserved);
 
 /* ---- training: backward of the warp / sampler and the loss kernels ---------------------------------------

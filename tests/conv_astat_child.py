@@ -2,6 +2,9 @@
 test is one run of this script under its own STABNET_CONV_* environment.  `python conv_astat_child.py <out.npz> <part> ...`:
   ops      every case of CASES through ops.conv2d_packed (splitk = 1) and ops.conv2d: got_<i>, f32_<i>, and the kernel the packed
            call runs (stabnet_conv2d_packed_kind, conv_route()'s own answer): kernel_<i>;
+           -- every packed output a freshly poisoned caller-owned buffer (_poison.py);
+  grid:U   GRID_CASE through ops.conv2d_packed (splitk = 1) with all, U and CUs / 8 usable CUs (stabnet_conv_reserve_cus, the
+           reservation argument): grid_<usable>, grid_usable (the three counts), grid_kernel, cus;
   forward  one regressor forward at (1, 96, 160) in operand mode 4 under the Profiler: theta, names, launches;
   routes   the Profiler names of one forward at (1, 96, 160) and at (1, 360, 640): names_small, names_large;
   deploy   one deploy step at 360 x 640: theta, x_map, y_map, output."""
@@ -13,6 +16,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # N, H, W, Cin, Cout, bias, residual (0 none, 1 same, 2 strided), out BN, relu
 CASES = [
@@ -24,11 +28,14 @@ CASES = [
     (1, 18, 32, 96, 256, False, 0, False, False),     # K = 96, three steps
     (1, 9, 13, 128, 256, True, 2, False, True),       # residual read with res_stride = 2
 ]
+# the N-group sweep: 36 M tiles of 32 rows (the last of 30) and 12 column blocks (the last tile ragged), so that 2 x usable CUs / M tiles
+# gives three, two (of 8 and 4 blocks) and one N group at 256, 37 and 32 usable CUs
+GRID_CASE = (1, 25, 46, 128, 372, True, 1, False, True)
 
 
 def case_data(i):
-    """The float32 inputs of case i (shared with the test, which evaluates the oracle on them)."""
-    N, H, W, Cin, Cout, bias, res, out_bn, relu = CASES[i]
+    """The float32 inputs of case i, -1: of GRID_CASE (shared with the test, which evaluates the oracle on them)."""
+    N, H, W, Cin, Cout, bias, res, out_bn, relu = CASES[i] if i >= 0 else GRID_CASE
     rng = np.random.default_rng(100 + i)
     d = {"x": rng.standard_normal((N, H, W, Cin)).astype(np.float32),
          "w": (rng.standard_normal((1, 1, Cin, Cout)) * np.sqrt(2.0 / Cin)).astype(np.float32)}
@@ -47,16 +54,45 @@ def forward_input(H, W, in_ch):
     return np.random.default_rng(11).uniform(-0.5, 0.5, (1, H, W, in_ch)).astype(np.float32)
 
 
+def grid_sweep(res, dev, u_odd, case, d, k, pad):
+    """case = (N, H, W, Cin, Cout, ...), d its data: the packed convolution at every usable CU count, each into freshly poisoned
+    buffers; the reservation is put back whatever happens."""
+    import _poison
+    from stabnet_amd import _lib, ops
+    L = _lib.lib()
+    N, H, W, Cin, Cout = case[:5]
+    t = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+    args = (t(d["x"]), t(ops.pack_conv_weight(d["w"])), t(d["b"]), None, None, t(d.get("r")), 1, 1, pad, bool(case[-1]))
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    assert cus // 8 < u_odd < cus
+    ws = ops.conv2d_packed_workspace_bytes(N, H, W, Cin, Cout, k, k, 1, pad, 1)
+    prev = L.stabnet_conv_reserve_cus(0)
+    try:
+        for usable, reserved in ((cus, 0), (u_odd, cus - u_odd), (cus // 8, cus)):
+            L.stabnet_conv_reserve_cus(reserved)
+            res["grid_%d" % usable] = _poison.run(dev, ops.conv2d_packed, (N, H, W, Cout), ws, *args, out_scale=t(d["osc"]),
+                                                  out_shift=t(d["osh"]), splitk=1, what="usable %d" % usable)
+    finally:
+        L.stabnet_conv_reserve_cus(prev)
+    res["grid_usable"] = np.array([cus, u_odd, cus // 8])
+    res["cus"] = np.int64(cus)
+    kind = int(L.stabnet_conv2d_packed_kind(N, H, W, Cin, Cout, k, k, 1, pad, 0, 1))
+    assert kind > 0, kind
+    res["grid_kernel"] = np.array(L.stabnet_prof_kind_name(kind).decode())
+
+
 def _ops(res, dev):
+    import _poison
     from stabnet_amd import _lib, ops
     L = _lib.lib()
     t = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
     for i, case in enumerate(CASES):
         d = case_data(i)
         args = (t(d["x"]), t(ops.pack_conv_weight(d["w"])), t(d["b"]), None, None, t(d["r"]), 2 if case[6] == 2 else 1, 1, 0, case[8])
-        res["got_%d" % i] = ops.conv2d_packed(*args, out_scale=t(d["osc"]), out_shift=t(d["osh"]), splitk=1).cpu().numpy()
-        res["f32_%d" % i] = ops.conv2d(*args, out_scale=t(d["osc"]), out_shift=t(d["osh"])).cpu().numpy()
         N, H, W, Cin, Cout = case[:5]
+        res["got_%d" % i] = _poison.run(dev, ops.conv2d_packed, (N, H, W, Cout), ops.conv2d_packed_workspace_bytes(N, H, W, Cin, Cout, 1, 1, 1, 0, 1),
+                                        *args, out_scale=t(d["osc"]), out_shift=t(d["osh"]), splitk=1, what="case %d" % i)
+        res["f32_%d" % i] = ops.conv2d(*args, out_scale=t(d["osc"]), out_shift=t(d["osh"])).cpu().numpy()
         kind = int(L.stabnet_conv2d_packed_kind(N, H, W, Cin, Cout, 1, 1, 1, 0, 0, 1))
         assert kind > 0, kind
         res["kernel_%d" % i] = np.array(L.stabnet_prof_kind_name(kind).decode())
@@ -109,6 +145,9 @@ def main(out, parts):
     prof = Profiler(max_records=4096, device=dev)
     if "ops" in parts:
         _ops(res, dev)
+    for part in parts:
+        if part.startswith("grid:"):
+            grid_sweep(res, dev, int(part[5:]), GRID_CASE, case_data(-1), 1, 0)
     if "forward" in parts:
         res["theta"], res["names"], res["launches"] = _forward(dev, 96, 160, prof)
     if "routes" in parts:

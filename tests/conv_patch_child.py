@@ -6,6 +6,8 @@ test is one run of this script under its own STABNET_CONV_* environment.  `pytho
            canaries intact), and the kernel the packed call runs (stabnet_conv2d_packed_kind, conv_route()'s own answer): kernel_<i>;
   ops2     the cases of KG2 (Cin = 64: an even number of K steps) with splitk = 2, the two equal K halves the ring kernel runs inside
            the workgroup: got2_<i>, f322_<i>, guards2_<i>, kernel2_<i>;
+  grid:U   GRID_CASE through ops.conv2d_packed (splitk = 1, freshly poisoned caller-owned buffers: _poison.py) with all, U and CUs / 8
+           usable CUs (stabnet_conv_reserve_cus, the reservation argument): grid_<usable>, grid_usable, grid_kernel, cus;
   twice    case REPLAY a second time, and once more as the replay of a captured graph: again, replay;
   routes   the Profiler names and stabnet_net_num_launches of one mode-4 forward at (1, 96, 160) and at (1, 360, 640);
   deploy   one deploy step at 360 x 640: theta, x_map, y_map, output."""
@@ -31,6 +33,9 @@ CASES = [
     (1, 12, 40, 96, 32, 32, True, True, True),        # x_ld > Cin over several patches
     (1, 9, 17, 32, 72, 0, True, False, False),
 ]
+# the N-group sweep: 6 x 6 patches (the last of 5 x 5 pixels) and 10 column blocks (the last tile ragged), so that 2 x usable CUs /
+# patches gives the most (five / three), two (the second shorter) and one N group at 256, 37 and 32 usable CUs
+GRID_CASE = (1, 45, 45, 32, 308, 0, True, False, True)
 KG2 = [i for i, c in enumerate(CASES) if c[3] == 64]
 REPLAY = 5
 GUARD = 4096
@@ -38,8 +43,8 @@ CANARY = 0x7FC0BEEF                                        # a NaN pattern no ke
 
 
 def case_data(i):
-    """The float32 inputs of case i (shared with the test, which evaluates the oracle on them)."""
-    N, H, W, Cin, Cout, extra, bias, out_bn, relu = CASES[i]
+    """The float32 inputs of case i, -1: of GRID_CASE (shared with the test, which evaluates the oracle on them)."""
+    N, H, W, Cin, Cout, extra, bias, out_bn, relu = CASES[i] if i >= 0 else GRID_CASE
     rng = np.random.default_rng(300 + i)
     d = {"x": rng.standard_normal((N, H, W, Cin)).astype(np.float32),
          "w": (rng.standard_normal((3, 3, Cin, Cout)) * np.sqrt(2.0 / (9 * Cin))).astype(np.float32)}
@@ -90,6 +95,7 @@ class _Call:
         N, H, W, Cin, Cout = self.case[:5]
         yh = self.yb.cpu().numpy().view(np.uint32)
         ok = (yh[:GUARD] == CANARY).all() and (yh[GUARD + self.ny:] == CANARY).all()
+        ok = ok and not (yh[GUARD:GUARD + self.ny] == CANARY).any()            # every element of y was written
         self.yb.fill_(CANARY)
         return yh[GUARD:GUARD + self.ny].view(np.float32).reshape(N, H, W, Cout).copy(), np.int64(ok)
 
@@ -129,7 +135,7 @@ def _twice(res, dev):
 
 
 def main(out, parts):
-    from conv_astat_child import _deploy, _forward
+    from conv_astat_child import _deploy, _forward, grid_sweep
     from stabnet_amd.deploy import Profiler
     dev = torch.device("cuda:0")
     res = {}
@@ -139,6 +145,9 @@ def main(out, parts):
         _ops(res, dev, KG2, 2, "2")
     if "twice" in parts:
         _twice(res, dev)
+    for part in parts:
+        if part.startswith("grid:"):
+            grid_sweep(res, dev, int(part[5:]), GRID_CASE, case_data(-1), 3, 1)
     if "routes" in parts:
         prof = Profiler(max_records=4096, device=dev)
         _, res["names_small"], res["launches_small"] = _forward(dev, 96, 160, prof)

@@ -14,7 +14,9 @@ K = 64 case would run the exact-f32 register-staged kernel in both arms).  Which
      record count, gives the theta of the STABNET_CONV_ASTAT=0 child bit for bit, within 2e-6 of the float64 evaluation;
   4. with default switches no launch at (1, 96, 160) takes the new kernel (M <= 1224 there: below the smallest M of the rule), at
      (1, 360, 640) at least one does (block 2: M = 3600);
-  5. one deploy step at 360 x 640 with default switches: theta, maps and output image equal bit for bit with and without the route."""
+  5. one deploy step at 360 x 640 with default switches: theta, maps and output image equal bit for bit with and without the route;
+  6. the N-group count follows the usable CUs (stabnet_conv_reserve_cus; conv.hip launch_astat): conv_astat_child.GRID_CASE with all,
+     37 and CUs / 8 usable CUs runs the most, two (the second shorter) and one group, every time the bits of the ring kernel."""
 import functools
 import os
 import subprocess
@@ -23,7 +25,7 @@ import sys
 import numpy as np
 import pytest
 
-from conv_astat_child import CASES, case_data, forward_input
+from conv_astat_child import CASES, GRID_CASE, case_data, forward_input
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,8 +35,8 @@ FORCED = {"STABNET_CONV_ASTAT_MIN_M": "1", "STABNET_CONV_ASTAT_MIN_COUT": "1", "
           "STABNET_CONV_TILE": "2", "STABNET_CONV_SPLITK": "1"}
 RING = "conv_ring_f32_kernel<0, 4, 1, 0>"                  # what every case runs with the route off
 ARMS = {
-    "on32": (dict(FORCED, STABNET_CONV_ASTAT="1"), ("ops", "forward")),
-    "off": (dict(FORCED, STABNET_CONV_ASTAT="0"), ("ops", "forward")),
+    "on32": (dict(FORCED, STABNET_CONV_ASTAT="1"), ("ops", "forward", "grid:37")),
+    "off": (dict(FORCED, STABNET_CONV_ASTAT="0"), ("ops", "forward", "grid:37")),
     "default": ({}, ("routes", "deploy")),
     "default_off": ({"STABNET_CONV_ASTAT": "0"}, ("deploy",)),
 }
@@ -126,6 +128,40 @@ def test_forward_runs_the_new_kernel(cuda, tmp_path_factory, bm):
     err = float(np.abs(on["theta"].astype(np.float64) - _theta64()).max())
     print("theta max error vs float64: %.3e" % err)
     assert err < F32_BAR
+
+
+def _groups(usable, mtiles, nblk):
+    """conv.hip launch_astat: (N groups, 32-column blocks per group) of a launch with `usable` CUs."""
+    cdiv = lambda a, b: -(-a // b)
+    groups = min(cdiv(nblk, 4), max(1, 2 * usable // mtiles))
+    per = 4 * cdiv(cdiv(nblk, groups), 4)
+    return cdiv(nblk, per), per
+
+
+@pytest.mark.parametrize("bm", BMS)
+def test_n_groups_follow_the_usable_cus(cuda, tmp_path_factory, bm):
+    tmp = str(tmp_path_factory.getbasetemp())
+    on, off = _child("on%d" % bm, tmp), _child("off", tmp)
+    assert str(on["grid_kernel"]) == KERNEL + "%d>" % bm and str(off["grid_kernel"]) == RING
+    N, H, W, Cin, Cout = GRID_CASE[:5]
+    mtiles, nblk = -(-N * H * W // bm), 2 * -(-Cout // 64)
+    usable = [int(u) for u in on["grid_usable"]]
+    assert usable == [int(on["cus"]), 37, int(on["cus"]) // 8] and (N * H * W) % bm != 0 and Cout % 64 != 0
+    counts = [_groups(u, mtiles, nblk) for u in usable]
+    print("conv_astat_f32_kernel<%d>: M tiles %d, column blocks %d, (usable CUs, N groups, blocks per group) = %s" % (
+        bm, mtiles, nblk, [(u,) + c for u, c in zip(usable, counts)]))
+    assert len({g for g, _ in counts}) == 3 and counts[0][0] == -(-nblk // 4) and counts[2][0] == 1
+    assert 1 < counts[1][0] < counts[0][0] and nblk % counts[1][1] != 0        # strictly between, its last group shorter than the others
+    # the bars of the packed kernels, then bit for bit: every group count, and the ring kernel at the same usable CUs
+    from oracle import stabnet_oracle as O
+    d = case_data(-1)
+    want = np.maximum(O.conv2d(d["x"], d["w"], 1, ((0, 0), (0, 0)), d["b"]) + d["r"], 0)
+    scale = np.abs(want).max()
+    for u in usable:
+        got = on["grid_%d" % u]
+        assert np.abs(got - want).max() <= 2e-5 * scale, u
+        assert np.array_equal(got.view(np.uint32), on["grid_%d" % usable[0]].view(np.uint32)), u
+        assert np.array_equal(got.view(np.uint32), off["grid_%d" % u].view(np.uint32)), u
 
 
 def test_default_routing_leaves_small_shapes_alone(cuda, tmp_path_factory):

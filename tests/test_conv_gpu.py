@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import _poison
 from oracle import stabnet_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -110,10 +111,14 @@ def test_split_k_inside_the_workgroup(cuda, N, H, W, Cin, Cout, k, stride, pad, 
     t = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(cuda)
     args = (t(x), t(ops.pack_conv_weight(w)), t(b), None, None, t(r), 1, stride, pad, relu)
     L = _lib.lib()
+    # each of the two runs writes a freshly poisoned caller-owned buffer (_poison.py): a tile that is never written is NaN, not the
+    # other run's values handed back by the caching allocator
+    geom = (N, H, W, Cin, Cout, k, k, stride, pad)
     try:
         L.stabnet_conv_tuning_override(2, 3)             # the 64 x 64 tile, three K slices
-        got3 = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
-        got3b = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
+        ws = ops.conv2d_workspace_bytes(*geom)
+        got3 = _poison.run(cuda, ops.conv2d, want.shape, ws, *args, out_scale=t(osc), out_shift=t(osh))
+        got3b = _poison.run(cuda, ops.conv2d, want.shape, ws, *args, out_scale=t(osc), out_shift=t(osh))
         L.stabnet_conv_tuning_override(2, 1)
         got1 = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
     finally:
@@ -165,8 +170,9 @@ def test_two_k_groups_with_prologue(cuda, N, H, W, Cin, Cout, bias, res, relu, o
     L = _lib.lib()
     try:
         L.stabnet_conv_tuning_override(2, 2)             # the 64 x 64 tile, two K slices
-        got2 = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
-        got2b = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
+        ws = ops.conv2d_workspace_bytes(N, H, W, Cin, Cout, 1, 1, 1, 0)
+        got2 = _poison.run(cuda, ops.conv2d, want.shape, ws, *args, out_scale=t(osc), out_shift=t(osh))      # (freshly poisoned buffers)
+        got2b = _poison.run(cuda, ops.conv2d, want.shape, ws, *args, out_scale=t(osc), out_shift=t(osh))
         L.stabnet_conv_tuning_override(2, 1)
         got1 = ops.conv2d(*args, out_scale=t(osc), out_shift=t(osh)).cpu().numpy()
     finally:
@@ -271,9 +277,9 @@ def test_conv3x3_conv1x1_one_launch(cuda, N, H, W, C, Cout, stride, bias, res, r
     xg = t(xfull)
     rg = xg if res_in_x else t(r)
     W2, W3 = t(ops.pack_conv_weight(w2)), t(ops.pack_conv_weight(w3))
-    got = ops.conv3x3_conv1x1(xg, W2, t(msc), t(msh), W3, t(b3), rg, 2 if res == 2 else 1, stride, relu, t(osc), t(osh), x_ch0=x_ch0)
-    got_b = ops.conv3x3_conv1x1(xg, W2, t(msc), t(msh), W3, t(b3), rg, 2 if res == 2 else 1, stride, relu, t(osc), t(osh), x_ch0=x_ch0)
-    got, got_b = got.cpu().numpy(), got_b.cpu().numpy()
+    b2b_args = (xg, W2, t(msc), t(msh), W3, t(b3), rg, 2 if res == 2 else 1, stride, relu, t(osc), t(osh))
+    got = _poison.run(cuda, ops.conv3x3_conv1x1, want.shape, None, *b2b_args, x_ch0=x_ch0)      # (each run into a freshly poisoned buffer)
+    got_b = _poison.run(cuda, ops.conv3x3_conv1x1, want.shape, None, *b2b_args, x_ch0=x_ch0)
     assert got.shape == want.shape and np.isfinite(got).all()
     scale = np.abs(want).max()
     assert np.abs(got - want).max() <= (6e-5 if out_bn else 3e-5) * scale, np.abs(got - want).max() / scale

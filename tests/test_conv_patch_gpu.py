@@ -12,7 +12,9 @@ for the two-K-half cases; STABNET_CONV_TILE=2 / STABNET_CONV_SPLITK=1 keep the p
   3. with default switches no launch of a forward at (1, 96, 160) takes the new kernel (M <= 1224 there), at (1, 360, 640) at least one
      does (block 1's conv2: M = 14400); the Profiler's record count is stabnet_net_num_launches in both;
   4. one deploy step at 360 x 640 with default switches: theta, maps and output image equal bit for bit with and without the route;
-  5. the same input twice gives equal bits, and so does the replay of a captured graph."""
+  5. the same input twice gives equal bits, and so does the replay of a captured graph;
+  6. the N-group count follows the usable CUs (stabnet_conv_reserve_cus; conv.hip launch_patch_one): conv_patch_child.GRID_CASE with
+     all, 37 and CUs / 8 usable CUs runs the most, two (the second shorter) and one group, every time the bits of the ring kernel."""
 import functools
 import os
 import subprocess
@@ -21,7 +23,7 @@ import sys
 import numpy as np
 import pytest
 
-from conv_patch_child import CASES, KG2, case_data
+from conv_patch_child import CASES, GRID_CASE, KG2, case_data
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,9 +36,9 @@ RING = {"": "conv_ring_f32_kernel<1, 4, 1, 0>", "2": "conv_ring_f32_kernel<1, 4,
 RUNS = ([("%dx%dx%dx%d-%d+%d" % CASES[i][:6], i, "") for i in range(len(CASES))] +
         [("%dx%dx%dx%d-%d+%d-halves" % CASES[i][:6], i, "2") for i in KG2])
 ARMS = {
-    "on1": (dict(FORCED, STABNET_CONV_PATCH="1", STABNET_CONV_PATCH_CFG="1"), ("ops", "ops2", "twice")),
-    "on2": (dict(FORCED, STABNET_CONV_PATCH="1", STABNET_CONV_PATCH_CFG="2"), ("ops", "ops2", "twice")),
-    "off": (dict(FORCED, STABNET_CONV_PATCH="0"), ("ops", "ops2")),
+    "on1": (dict(FORCED, STABNET_CONV_PATCH="1", STABNET_CONV_PATCH_CFG="1"), ("ops", "ops2", "twice", "grid:37")),
+    "on2": (dict(FORCED, STABNET_CONV_PATCH="1", STABNET_CONV_PATCH_CFG="2"), ("ops", "ops2", "twice", "grid:37")),
+    "off": (dict(FORCED, STABNET_CONV_PATCH="0"), ("ops", "ops2", "grid:37")),
     "default": ({}, ("routes", "deploy")),
     "default_off": ({"STABNET_CONV_PATCH": "0"}, ("deploy",)),
 }
@@ -103,6 +105,50 @@ def test_keeps_the_bars_of_the_packed_kernels(cuda, tmp_path_factory, i, t, cfg)
     assert err <= (4e-5 if CASES[i][7] else 2e-5) * scale, "max err vs oracle %g (scale %g)" % (err, scale)
     diff = np.abs(got - f32).max()
     assert diff <= 4e-6 * scale, "max difference to the exact-f32-MFMA kernels %g (scale %g)" % (diff, scale)
+
+
+def _lds_bytes(cfg, Cin):
+    """conv_patch_kernel.h sn_patch_lds_bytes of form cfg (as _kernel above)."""
+    ph, pw, wr, ns = FORMS[cfg]
+    return (ph + 2) * ((((pw + 2) * (6 * Cin + 16) + 127) & ~255) + 128) + 4 * 4096
+
+
+def _groups(cfg, usable, mtiles, nblk, Cin):
+    """conv.hip launch_patch_one: (N groups, 32-column blocks per group) of a launch of form cfg with `usable` CUs."""
+    cdiv = lambda a, b: -(-a // b)
+    ph, pw, wr, ns = FORMS[cfg]
+    cs = 4 // ((ph // 4) * (pw // 8) // wr)
+    slots = min(1 if wr >= 4 else 2, 160 * 1024 // _lds_bytes(cfg, Cin)) * usable
+    groups = min(cdiv(nblk, cs), max(1, slots // mtiles))
+    per = cs * cdiv(cdiv(nblk, groups), cs)
+    return cdiv(nblk, per), per
+
+
+@pytest.mark.parametrize("cfg", sorted(FORMS))
+def test_n_groups_follow_the_usable_cus(cuda, tmp_path_factory, cfg):
+    tmp = str(tmp_path_factory.getbasetemp())
+    on, off = _child("on%d" % cfg, tmp), _child("off", tmp)
+    assert str(on["grid_kernel"]) == KERNEL + "%d, %d, %d, %d>" % FORMS[cfg] and str(off["grid_kernel"]) == RING[""]
+    N, H, W, Cin, Cout = GRID_CASE[:5]
+    ph, pw = FORMS[cfg][:2]
+    mtiles, nblk = N * -(-H // ph) * -(-W // pw), 2 * -(-Cout // 64)
+    usable = [int(u) for u in on["grid_usable"]]
+    assert usable == [int(on["cus"]), 37, int(on["cus"]) // 8] and H % ph != 0 and W % pw != 0 and Cout % 64 != 0
+    counts = [_groups(cfg, u, mtiles, nblk, Cin) for u in usable]
+    print("conv_patch_f32_kernel<%d, %d, %d, %d>: patches %d, column blocks %d, (usable CUs, N groups, blocks per group) = %s" % (
+        FORMS[cfg] + (mtiles, nblk, [(u,) + c for u, c in zip(usable, counts)])))
+    cs = 4 // ((ph // 4) * (pw // 8) // FORMS[cfg][2])
+    assert len({g for g, _ in counts}) == 3 and counts[0][0] == -(-nblk // cs) and counts[2][0] == 1
+    assert 1 < counts[1][0] < counts[0][0] and nblk % counts[1][1] != 0        # strictly between, its last group shorter than the others
+    from oracle import stabnet_oracle as O
+    d = case_data(-1)
+    want = np.maximum(O.conv2d(d["x"], d["w"], 1, ((1, 1), (1, 1)), d["b"]), 0)
+    scale = np.abs(want).max()
+    for u in usable:
+        got = on["grid_%d" % u]
+        assert np.abs(got - want).max() <= 2e-5 * scale, u
+        assert np.array_equal(got.view(np.uint32), on["grid_%d" % usable[0]].view(np.uint32)), u
+        assert np.array_equal(got.view(np.uint32), off["grid_%d" % u].view(np.uint32)), u
 
 
 def test_default_routing_leaves_small_shapes_alone(cuda, tmp_path_factory):
