@@ -10,7 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (4, 96, 160)])
+@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (4, 96, 160), (3, 90, 130), (1, 75, 101)])
 def test_lockstep_towers_match_tower_after_tower(cuda, N, H, W):
     from stabnet_amd import _lib, synthetic
     from stabnet_amd._tensor import ptr, stream_ptr

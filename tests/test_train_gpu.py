@@ -80,6 +80,15 @@ def test_training_step_matches_autograd_oracle(cuda):
         assert err < 2e-2, "%s: element err %g with the forward's decisions forced" % (name, err)
         assert l2 < 6e-3, "%s: relative L2 err %g with the forward's decisions forced" % (name, l2)
     assert whole < 1e-4, whole
+    # The two per-tensor bars above are set by the 21 `/biases` in front of a batch-statistics BN, whose gradient is exactly zero and
+    # whose float32 value is cancellation noise (class Z of tests/_train_bars.py).  Every tensor that carries a gradient (class R)
+    # is held to 8 x what a float32 evaluation of the oracle itself reaches at this size, the whole gradient likewise.
+    import _train_bars as B
+    got_g = tr.plan.unpack(np.concatenate([got_flat, np.zeros(tr.plan.n_floats - tr.nt, np.float32)]))
+    m = B.measure_gradient({k: got_g[k] for k in P if B.trainable(k)},
+                           {k: (pf[k].grad.numpy() if pf[k].grad is not None else np.zeros(P[k].shape)) for k in P if B.trainable(k)})
+    print(B.report("MEASURED 2x64x96 (decisions forced)", m, N, H, W))
+    B.check_gradient(m, N, H, W, which=("R", "whole"))
     # (b) un-forced: whole-gradient agreement
     u_abs, u_l2, whole_u, _ = gradient_errors(tr.plan, got_flat, want_flat)
     print("MEASURED (un-forced) worst element %.3e worst tensor L2 %.3e whole L2 %.3e" % (u_abs, u_l2, whole_u))
