@@ -37,5 +37,5 @@ int sn_check_device(const void* p, const char* what, hipStream_t st) {
 
 extern "C" {
 const char* stabnet_last_error(void) { return g_err; }
-int stabnet_abi_version(void) { return 4; }
+int stabnet_abi_version(void) { return 5; }
 }

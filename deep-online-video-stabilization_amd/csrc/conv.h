@@ -86,6 +86,18 @@ struct ConvRoute {
 // read as the plan holds it) counts as met -- `reduce` is then the launcher's for every launch a plan makes.  Reads nothing but its
 // arguments, the once-per-process STABNET_CONV_* switches and the tuning hooks (stabnet_conv_tuning_*).
 ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound, bool lowk_ring = false /* see conv_launch() */);
+// The grid of the conv launch of route `r` on a chip of `cus` CUs (less the reserved ones, stabnet_conv_reserve_cus): the ONE rule the
+// launchers size their grids by.  tiles = units of work the workgroups walk: (M tile, N tile, K slice) of the 64 x 64 kernels (K
+// groups inside the workgroup are no tiles), (M tile | patch, pass over the column blocks its waves take side by side) of the
+// A-stationary and patch kernels; wgs = gx * gy * gz workgroups.  Host only: reads no device.
+struct ConvGrid { long tiles, wgs; int gx, gy, gz; };
+ConvGrid conv_grid(const ConvRoute& r, const ConvArgs& a, int cus);
+// LDS the A-stationary kernel's planes / the patch kernel's launch take for `a`, and the limits the launchers hold them to
+size_t conv_astat_plane_bytes(const ConvRoute& r, const ConvArgs& a);
+size_t conv_astat_plane_limit();
+size_t conv_patch_lds_bytes(const ConvRoute& r, const ConvArgs& a);
+size_t conv_patch_lds_limit();
+int conv_plan_total_steps(const ConvArgs& a);   // K-steps of the whole reduction (all slices)
 // Kernel name of a PK_KERNEL_CONV_* Profiler kind as rocprofv3 prints the instantiation; null for any other kind.
 const char* conv_prof_kind_name(int kind);
 // Pre-split weight image of a convolution whose weights are [Cout][K] rows (K % 32 == 0): per (64-channel N tile, 32-deep K step)

@@ -438,6 +438,83 @@ const char* conv_prof_kind_name(int kind) {
     return (kind >= 0 && kind < (int)names.size() && !names[kind].empty()) ? names[kind].c_str() : nullptr;
 }
 
+// ---- the grid of a launch (conv.h conv_grid) ---------------------------------------------------------------------------
+static int g_reserved_cus = 0;    // CUs the persistent grids leave to a communication stream (stabnet_conv_reserve_cus)
+// persistent grids are sized for the CUs that are NOT reserved (never fewer than an eighth of the chip)
+static int usable_cus(int cus) { return std::max(cus / 8, cus - std::max(0, g_reserved_cus)); }
+
+// Register-staged kernel: one workgroup per (M tile, N tile, K slice).
+static ConvGrid igemm_grid(const ConvArgs& a, int bm, int bn) {
+    ConvGrid g{};
+    g.gx = cdiv(a.M, bm); g.gy = cdiv(a.Cout, bn); g.gz = a.splitk;
+    g.tiles = g.wgs = (long)g.gx * g.gy * g.gz;
+    return g;
+}
+// Every ring launch.  The grid is persistent: at most the resident workgroups -- 3 per CU (48 KiB of LDS each), 2 of the packed
+// split kernel (60 KiB), one when K splits inside the workgroup (KG x that; the K slices are then no tiles of their own).
+static ConvGrid ring_grid(const ConvRoute& r, const ConvArgs& a, int cus) {
+    ConvGrid g{};
+    const int per_cu = r.kg > 1 ? 1 : (r.operand == 4 ? sw().packed_wgs_per_cu : sw().ring_wgs_per_cu);
+    g.tiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * (r.kg > 1 ? 1 : a.splitk);
+    g.gx = (int)std::min<long>(g.tiles, (long)per_cu * usable_cus(cus));
+    g.gy = g.gz = 1;
+    g.wgs = g.gx;
+    return g;
+}
+// The A-stationary packed kernel: grid = (M tiles, N groups).  A group is a multiple of four 32-column blocks (one per wave and pass);
+// N is cut into groups only as far as it takes to fill the resident slots (two workgroups of 64 KB of LDS per CU): every further
+// group splits the A tile once more.  Tiles: (M tile, pass of four column blocks).
+static ConvGrid astat_grid(const ConvArgs& a, int bm, int cus) {
+    ConvGrid g{};
+    const int mtiles = cdiv(a.M, bm), nblk = 2 * cdiv(a.Cout, 64);
+    int groups = (int)std::min<long>(cdiv(nblk, 4), std::max<long>(1, 2L * usable_cus(cus) / mtiles));
+    groups = cdiv(nblk, 4 * cdiv(cdiv(nblk, groups), 4));            // as the kernel derives the group size from it: no empty group
+    g.gx = mtiles; g.gy = groups; g.gz = 1;
+    g.tiles = (long)mtiles * cdiv(nblk, 4);
+    g.wgs = (long)mtiles * groups;
+    return g;
+}
+// The patch-stationary packed kernel: grid = (patches, N groups).  A group is a multiple of the CS column blocks the workgroup's waves
+// work on side by side; N is cut into groups only as far as it takes to fill the resident slots: every further group loads and splits
+// the patch once more.  Tiles: (patch, pass of CS column blocks).
+static ConvGrid patch_grid(const ConvArgs& a, int ph, int pw, int wr, int cus) {
+    ConvGrid g{};
+    const size_t lds = sn_patch_lds_bytes(ph, pw, a.Cin);
+    const int cs = 4 / ((ph / 4) * (pw / 8) / wr);
+    const int mtiles = a.N * cdiv(a.Ho, ph) * cdiv(a.Wo, pw), nblk = 2 * cdiv(a.Cout, 64);
+    const long slots = (long)std::min<size_t>(wr >= 4 ? 1 : 2, SN_PATCH_LDS_MAX / lds) * usable_cus(cus);
+    int groups = (int)std::min<long>(cdiv(nblk, cs), std::max<long>(1, slots / mtiles));
+    groups = cdiv(nblk, cs * cdiv(cdiv(nblk, groups), cs));          // as the kernel derives the group size from it: no empty group
+    g.gx = mtiles; g.gy = groups; g.gz = 1;
+    g.tiles = (long)mtiles * cdiv(nblk, cs);
+    g.wgs = (long)mtiles * groups;
+    return g;
+}
+ConvGrid conv_grid(const ConvRoute& r, const ConvArgs& a, int cus) {
+    switch (r.family) {
+        case CONV_IGEMM: {
+            int bm, bn;
+            tile_dims(r.tile, bm, bn);
+            return igemm_grid(a, bm, bn);
+        }
+        case CONV_ASTAT: return astat_grid(a, r.astat_bm, cus);
+        case CONV_PATCH: {
+            if (r.patch_cfg < 1 || r.patch_cfg > SN_PATCH_FORMS) return ConvGrid{};
+            const PatchForm& f = g_patch_forms[r.patch_cfg - 1];
+            return patch_grid(a, f.ph, f.pw, f.wr, cus);
+        }
+        default: return ring_grid(r, a, cus);
+    }
+}
+size_t conv_astat_plane_bytes(const ConvRoute& r, const ConvArgs& a) { return (size_t)r.astat_bm * a.K * 6; }
+size_t conv_astat_plane_limit() { return (size_t)SN_ASTAT_A_BYTES; }
+size_t conv_patch_lds_bytes(const ConvRoute& r, const ConvArgs& a) {
+    if (r.patch_cfg < 1 || r.patch_cfg > SN_PATCH_FORMS) return 0;
+    return sn_patch_lds_bytes(g_patch_forms[r.patch_cfg - 1].ph, g_patch_forms[r.patch_cfg - 1].pw, a.Cin);
+}
+size_t conv_patch_lds_limit() { return SN_PATCH_LDS_MAX; }
+int conv_plan_total_steps(const ConvArgs& a) { return conv_total_steps(a); }
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 template <int BM, int BN, int BK, int WM, int WN, int MODE, int NBUF, int BF16 = 0>
 static int launch_one_nb(const ConvArgs& a, hipStream_t st) {
@@ -457,8 +534,8 @@ static int launch_one_nb(const ConvArgs& a, hipStream_t st) {
         }
         configured = true;
     }
-    dim3 grid(cdiv(a.M, BM), cdiv(a.Cout, BN), a.splitk);
-    kern<<<grid, 256, lds, st>>>(a);
+    const ConvGrid g = igemm_grid(a, BM, BN);
+    kern<<<dim3(g.gx, g.gy, g.gz), 256, lds, st>>>(a);
     SN_LAUNCH_CHECK("conv_igemm_f32_kernel");
     return STABNET_OK;
 }
@@ -506,9 +583,6 @@ static int device_cus(int& cus) {
     return STABNET_OK;
 }
 static thread_local int g_last_launch_kind = -1;   // stabnet_conv_last_launch_kind
-static int g_reserved_cus = 0;    // CUs the persistent grids leave to a communication stream (stabnet_conv_reserve_cus)
-// persistent grids are sized for the CUs that are NOT reserved (never fewer than an eighth of the chip)
-static int usable_cus(int cus) { return std::max(cus / 8, cus - std::max(0, g_reserved_cus)); }
 
 // The ONE mapping from a route's (MODE, operand, KG, PRO) to the instantiation of conv_ring_f32_kernel (256 threads per K group);
 // false: the library has no such kernel.
@@ -533,14 +607,11 @@ static bool launch_ring_operand(const ConvRoute& r, const ConvArgs& a, int grid,
     return false;
 }
 
-// Every ring launch.  The grid is persistent: at most the resident workgroups -- 3 per CU (48 KiB of LDS each), 2 of the packed
-// split kernel (60 KiB), one when K splits inside the workgroup (KG x that; the K slices are then no tiles of their own).
+// Every ring launch, on ring_grid()'s persistent grid.
 static int launch_ring_route(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
     int cus = 0;
     if (const int rc = device_cus(cus)) return rc;
-    const int per_cu = r.kg > 1 ? 1 : (r.operand == 4 ? sw().packed_wgs_per_cu : sw().ring_wgs_per_cu);
-    const long ntiles = (long)cdiv(a.M, 64) * cdiv(a.Cout, 64) * (r.kg > 1 ? 1 : a.splitk);
-    const int grid = (int)std::min<long>(ntiles, (long)per_cu * usable_cus(cus));
+    const int grid = ring_grid(r, a, cus).gx;
     bool ok = false;
     switch (r.operand) {
         case 0: ok = launch_ring_operand<0>(r, a, grid, st); break;
@@ -555,27 +626,21 @@ static int launch_ring_route(const ConvRoute& r, const ConvArgs& a, hipStream_t 
     return STABNET_OK;
 }
 
-// The A-stationary packed kernel: grid = (M tiles, N groups).  A group is a multiple of four 32-column blocks (one per wave and pass);
-// N is cut into groups only as far as it takes to fill the resident slots (two workgroups of 64 KB of LDS per CU): every further
-// group splits the A tile once more.
+// The A-stationary packed kernel, on astat_grid()'s (M tiles, N groups).
 static int launch_astat(const ConvRoute& r, const ConvArgs& a, hipStream_t st) {
     int cus = 0;
     if (const int rc = device_cus(cus)) return rc;
     const int bm = r.astat_bm;
     SN_REQUIRE(bm == 32 && a.K % 32 == 0 && (size_t)bm * a.K * 6 <= (size_t)SN_ASTAT_A_BYTES && a.splitk == 1,
                "conv: the A-stationary kernel takes BM %d x K %d without a K split only if the planes fit %d bytes", bm, a.K, SN_ASTAT_A_BYTES);
-    const int mtiles = cdiv(a.M, bm), nblk = 2 * cdiv(a.Cout, 64);
-    int groups = (int)std::min<long>(cdiv(nblk, 4), std::max<long>(1, 2L * usable_cus(cus) / mtiles));
-    groups = cdiv(nblk, 4 * cdiv(cdiv(nblk, groups), 4));            // as the kernel derives the group size from it: no empty group
-    const dim3 grid(mtiles, groups);
+    const ConvGrid g = astat_grid(a, bm, cus);
+    const dim3 grid(g.gx, g.gy);
     conv_astat_f32_kernel<32><<<grid, 256, 0, st>>>(a);
     SN_LAUNCH_CHECK("conv_astat_f32_kernel");
     return STABNET_OK;
 }
 
-// The patch-stationary packed kernel: grid = (patches, N groups).  A group is a multiple of the CS column blocks the workgroup's waves
-// work on side by side; N is cut into groups only as far as it takes to fill the resident slots: every further group loads and splits
-// the patch once more.
+// The patch-stationary packed kernel, on patch_grid()'s (patches, N groups).
 template <int PH, int PW, int WR, int NS>
 static int launch_patch_one(const ConvArgs& a, int cus, hipStream_t st) {
     const size_t lds = sn_patch_lds_bytes(PH, PW, a.Cin);
@@ -589,12 +654,8 @@ static int launch_patch_one(const ConvArgs& a, int cus, hipStream_t st) {
         }
         configured = SN_PATCH_LDS_MAX;
     }
-    constexpr int cs = 4 / ((PH / 4) * (PW / 8) / WR);
-    const int mtiles = a.N * cdiv(a.Ho, PH) * cdiv(a.Wo, PW), nblk = 2 * cdiv(a.Cout, 64);
-    const long slots = (long)std::min<size_t>(WR >= 4 ? 1 : 2, SN_PATCH_LDS_MAX / lds) * usable_cus(cus);
-    int groups = (int)std::min<long>(cdiv(nblk, cs), std::max<long>(1, slots / mtiles));
-    groups = cdiv(nblk, cs * cdiv(cdiv(nblk, groups), cs));          // as the kernel derives the group size from it: no empty group
-    const dim3 grid(mtiles, groups);
+    const ConvGrid g = patch_grid(a, PH, PW, WR, cus);
+    const dim3 grid(g.gx, g.gy);
     kern<<<grid, 256, lds, st>>>(a);
     SN_LAUNCH_CHECK("conv_patch_f32_kernel");
     return STABNET_OK;

@@ -22,6 +22,7 @@
 #include "ring.h"
 #include "train_layers.h"
 #include "warp.h"
+#include "../../include/stabnet_hip.h"   // the STABNET_SI_* fields of stabnet_net_step_info (and a check of this file's entries against their declarations)
 
 extern "C" int stabnet_black_accumulate(const float* black, int* all_black, long n, void* stream);
 
@@ -44,6 +45,8 @@ struct Step {
     ConvArgs conv_pair;                          // training plans: the same conv over BOTH towers' batches (N doubled), own split-K plan
     int pair_ok;                                 // 1: conv_launch_pair() can run it (64x64 register-staged plan, tower rows % 64 == 0)
     long in_off, out_off, res_off, w_off, b_off, bn_off;
+    long in_base;                                // S_CONV: first float of the buffer the input lives in (in_off, or the merged buffer's)
+    size_t in_floats, res_floats;                // S_CONV: floats of that buffer (all x_ld columns; the stem's border too) / of the residual's
     long obn_off;                                // inference only: folded BN + ReLU of the CONSUMER fused behind this conv
     int inf_preactivated;                        // inference only: the input tensor already holds relu(bn(.)) -> no prologue
     long wimg_off;                               // inference only: this conv's pre-split weight image inside the image region of `fold`
@@ -213,6 +216,7 @@ static Step conv_step(Net& net, const TensorRef& in, const TensorRef& out, int K
     s.splitk_bytes = conv_plan(a);
     net.splitk_bytes = std::max(net.splitk_bytes, s.splitk_bytes);
     s.in_off = in.off; s.out_off = out.off; s.res_off = res ? res->off : NONE;
+    s.in_base = in.off; s.in_floats = in.size; s.res_floats = res ? res->size : 0;
     s.w_off = w_off; s.b_off = b_off; s.bn_off = bn_off;
     s.obn_off = NONE; s.inf_preactivated = 0; s.fvec_off = NONE; s.wimg_off = NONE;
     net.flops += 2.0 * a.M * (double)(a.KH * a.KW * (real_cin ? real_cin : a.Cin)) * a.Cout;   // algorithmic (un-padded)
@@ -344,7 +348,7 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
             {
                 const long w = (long)net->add_param(S + "conv2/weights", PK_CONV_W, b.dbn, 3, 3, b.dbn, b.dbn);
                 net->steps.push_back(conv_step(*net, r1, r2, 3, stride, 1, w, NONE, bn1, nullptr, 1));
-                if (merged_ld) net->steps.back().conv.x_ld = merged_ld;
+                if (merged_ld) { net->steps.back().conv.x_ld = merged_ld; net->steps.back().in_base = merged_buf.off; }
                 ui.w2 = w;
             }
             if (!merged_ld) done(r1);
@@ -546,15 +550,48 @@ struct MeshTail { int gh, gw; float lim; float* Hs; int* head_adv; int depth; bo
 // own mode.  run_forward and stabnet_net_num_launches both follow this.
 static bool b2b_fused(const Net* net) { return net->bf16_operands == 0 || net->bf16_operands == 4; }
 
-static int run_forward(const Net* net, const float* params, const float* fold, const float* x, float* theta,
-                       float* ws, hipStream_t st, Prof* prof = nullptr, bool skip_pad = false, MeshTail* mesh = nullptr) {
+// An S_CONV step of an inference plan as run_steps() launches it: the plan's ConvArgs with every pointer bound.  w_img: the
+// pre-split weight image the launch comes with (null: none).  Host arithmetic on the four base pointers only -- stabnet_net_step_info
+// binds a step to placeholder bases to ask conv_route() for the launcher's own view.
+static ConvArgs bind_conv(const Net* net, const Step& s, const float* params, const float* fold, float* ws, const float*& w_img) {
+    const float* scale = fold;
+    const float* shift = fold + net->G;
+    ConvArgs a = s.conv;
+    a.x = ws + s.in_off;
+    a.y = ws + s.out_off;
+    a.w = a.rowrun ? fold + 2 * net->G : params + s.w_off;
+    a.bias = s.b_off >= 0 ? params + s.b_off : nullptr;
+    a.residual = s.res_off >= 0 ? ws + s.res_off : nullptr;
+    const bool prologue = s.bn_off >= 0 && !s.inf_preactivated;
+    a.in_scale = prologue ? scale + s.bn_off : nullptr;
+    a.in_shift = prologue ? shift + s.bn_off : nullptr;
+    if (s.obn_off >= 0) {
+        a.out_scale = scale + s.obn_off;
+        a.out_shift = shift + s.obn_off;
+        a.relu_out = 1;
+    }
+    if (s.fvec_off >= 0) {                     // merged shortcut | conv1: everything per channel
+        const float* v = fold + 2 * net->G + net->stem_w_floats + s.fvec_off;
+        a.bias = v; a.out_scale = v + a.Cout; a.out_shift = v + 2 * a.Cout; a.out_floor = v + 3 * a.Cout;
+        a.relu_out = 0;
+    }
+    a.partial = ws + net->act_floats;
+    w_img = (net->bf16_operands == 4 && s.wimg_off >= 0 && !net->keep_all) ? fold + 2 * net->G + net->stem_w_floats + net->merge_floats + s.wimg_off : nullptr;
+    return a;
+}
+
+// Steps first..last of the inference forward (run_forward: all of them; stabnet_net_run_steps: the caller's range).  The fused head's
+// last launch belongs to the last step.
+static int run_steps(const Net* net, const float* params, const float* fold, const float* x, float* theta,
+                     float* ws, hipStream_t st, int first, int last, Prof* prof = nullptr, bool skip_pad = false, MeshTail* mesh = nullptr) {
     float* splitk = ws + net->act_floats;
     const float* scale = fold;
     const float* shift = fold + net->G;
     // inference head, batch <= 8: reduce_mean finalize folded into fc_1, output layer + mesh as one launch (head.hip)
     const bool fused_head = head_fused_supported(net->N, net->t_last.C, net->fc_dims);
     if (mesh) mesh->done = false;
-    for (const Step& s : net->steps) {
+    for (int si = first; si <= last; ++si) {
+        const Step& s = net->steps[si];
         int rc = STABNET_OK;
         if (s.kind == S_PAD && skip_pad) continue;
         if (s.kind == S_FC && fused_head && (s.in_off == net->t_gap.off || s.out_off == EXT_OUT)) continue;   // fc_1 rides with the GAP, the output layer with the mesh
@@ -565,28 +602,9 @@ static int run_forward(const Net* net, const float* params, const float* fold, c
                 else rc = launch_pad_channels(x, ws + s.out_off, (long)s.N * s.H * s.W, s.C, net->in_ch_act, st);
                 break;
             case S_CONV: {
-                ConvArgs a = s.conv;
-                a.x = ws + s.in_off;
-                a.y = ws + s.out_off;
-                a.w = a.rowrun ? fold + 2 * net->G : params + s.w_off;
-                a.bias = s.b_off >= 0 ? params + s.b_off : nullptr;
-                a.residual = s.res_off >= 0 ? ws + s.res_off : nullptr;
-                const bool prologue = s.bn_off >= 0 && !s.inf_preactivated;
-                a.in_scale = prologue ? scale + s.bn_off : nullptr;
-                a.in_shift = prologue ? shift + s.bn_off : nullptr;
-                if (s.obn_off >= 0) {
-                    a.out_scale = scale + s.obn_off;
-                    a.out_shift = shift + s.obn_off;
-                    a.relu_out = 1;
-                }
-                if (s.fvec_off >= 0) {                     // merged shortcut | conv1: everything per channel
-                    const float* v = fold + 2 * net->G + net->stem_w_floats + s.fvec_off;
-                    a.bias = v; a.out_scale = v + a.Cout; a.out_shift = v + 2 * a.Cout; a.out_floor = v + 3 * a.Cout;
-                    a.relu_out = 0;
-                }
-                a.partial = splitk;
-                rc = conv_launch(a, st, prof, net->bf16_operands,
-                                 (net->bf16_operands == 4 && s.wimg_off >= 0 && !net->keep_all) ? fold + 2 * net->G + net->stem_w_floats + net->merge_floats + s.wimg_off : nullptr);
+                const float* w_img = nullptr;
+                const ConvArgs a = bind_conv(net, s, params, fold, ws, w_img);
+                rc = conv_launch(a, st, prof, net->bf16_operands, w_img);
                 break;
             }
             case S_CONV_B2B: {
@@ -636,7 +654,7 @@ static int run_forward(const Net* net, const float* params, const float* fold, c
         }
         if (rc) return rc;
     }
-    if (fused_head) {                                         // output_layer (+ mesh + ring-head advance) as one launch
+    if (fused_head && last + 1 == (int)net->steps.size()) {   // output_layer (+ mesh + ring-head advance) as one launch
         const bool rec = prof != nullptr && prof->begin(st);
         const int rc = launch_theta_mesh(ws + net->t_fc[2].off, params + net->fc_w[3], params + net->fc_b[3], net->N, net->n_theta, theta,
                                          mesh ? mesh->gh : 1, mesh ? mesh->gw : 1, mesh ? mesh->lim : 0.f, mesh ? mesh->Hs : nullptr,
@@ -647,6 +665,11 @@ static int run_forward(const Net* net, const float* params, const float* fold, c
         if (mesh) mesh->done = true;
     }
     return STABNET_OK;
+}
+
+static int run_forward(const Net* net, const float* params, const float* fold, const float* x, float* theta,
+                       float* ws, hipStream_t st, Prof* prof = nullptr, bool skip_pad = false, MeshTail* mesh = nullptr) {
+    return run_steps(net, params, fold, x, theta, ws, st, 0, (int)net->steps.size() - 1, prof, skip_pad, mesh);
 }
 
 extern "C" {
@@ -911,6 +934,88 @@ int stabnet_backbone_fwd_infer(const void* netp, const float* params, const floa
     if (rc) return rc;
     return run_forward(net, params, fold, x_tensor, theta, static_cast<float*>(workspace), (hipStream_t)stream,
                        static_cast<Prof*>(prof));
+}
+
+int stabnet_net_num_steps(const void* netp) { return netp ? (int)static_cast<const Net*>(netp)->steps.size() : -1; }
+int stabnet_net_step_info_fields(void) { return STABNET_SI_FIELDS; }
+
+/* What plan step `step` of an inference plan is and, for a convolution, everything its launch is made of (include/stabnet_hip.h).
+ * Host only: the step is bound to placeholder bases (conv_route() and conv_grid() look at no memory) and asked for the route and
+ * the grid the launcher would take on a chip of `cus` CUs. */
+int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int cap) {
+    const Net* net = static_cast<const Net*>(netp);
+    SN_REQUIRE(net && info, "step_info: null pointer");
+    SN_REQUIRE(!net->keep_all, "step_info: inference plans only (keep_activations = 0)");
+    SN_REQUIRE(step >= 0 && step < (int)net->steps.size(), "step_info: step %d outside the plan's %d steps", step, (int)net->steps.size());
+    SN_REQUIRE(cus > 0 && cap >= STABNET_SI_FIELDS, "step_info: cus %d must be positive and info hold %d fields (cap %d)", cus, STABNET_SI_FIELDS, cap);
+    const Step& s = net->steps[step];
+    for (int i = 0; i < STABNET_SI_FIELDS; ++i) info[i] = 0;
+    info[STABNET_SI_KIND] = s.kind;
+    if (s.kind != S_CONV) return STABNET_OK;
+    // placeholder bases, far enough apart that no two bound pointers meet; never dereferenced
+    const float* params = reinterpret_cast<const float*>((size_t)1 << 40);
+    const float* fold = reinterpret_cast<const float*>((size_t)2 << 40);
+    float* ws = reinterpret_cast<float*>((size_t)3 << 40);
+    const float* w_img = nullptr;
+    const ConvArgs a = bind_conv(net, s, params, fold, ws, w_img);
+    const ConvRoute r = conv_route(a, net->bf16_operands, w_img != nullptr, true);
+    const ConvGrid g = conv_grid(r, a, cus);
+    info[STABNET_SI_N] = a.N; info[STABNET_SI_H] = a.H; info[STABNET_SI_W] = a.W; info[STABNET_SI_CIN] = a.Cin;
+    info[STABNET_SI_HO] = a.Ho; info[STABNET_SI_WO] = a.Wo; info[STABNET_SI_COUT] = a.Cout;
+    info[STABNET_SI_KH] = a.KH; info[STABNET_SI_KW] = a.KW; info[STABNET_SI_STRIDE] = a.stride; info[STABNET_SI_PAD] = a.pad;
+    info[STABNET_SI_X_LD] = a.x_ld; info[STABNET_SI_RES_LD] = a.res_ld;
+    info[STABNET_SI_RES_H] = a.res_H; info[STABNET_SI_RES_W] = a.res_W; info[STABNET_SI_RES_STRIDE] = a.res_stride;
+    info[STABNET_SI_ROWRUN] = a.rowrun; info[STABNET_SI_RELU_OUT] = a.relu_out;
+    info[STABNET_SI_M] = a.M; info[STABNET_SI_K] = a.K;
+    info[STABNET_SI_IN_OFF] = s.in_off; info[STABNET_SI_IN_BASE] = s.in_base; info[STABNET_SI_IN_FLOATS] = (long)s.in_floats;
+    info[STABNET_SI_OUT_OFF] = s.out_off; info[STABNET_SI_OUT_FLOATS] = (long)a.M * a.Cout;
+    info[STABNET_SI_RES_OFF] = s.res_off >= 0 ? s.res_off : -1; info[STABNET_SI_RES_FLOATS] = (long)s.res_floats;
+    info[STABNET_SI_SCRATCH_OFF] = (long)net->act_floats;
+    info[STABNET_SI_SCRATCH_FLOATS] = r.reduce ? (long)a.splitk * a.M * a.Cout : 0;
+    info[STABNET_SI_W_OFF] = s.w_off; info[STABNET_SI_BIAS_OFF] = s.b_off >= 0 ? s.b_off : -1;
+    info[STABNET_SI_PRO_BN_OFF] = a.in_scale ? s.bn_off : -1;
+    info[STABNET_SI_OUT_BN_OFF] = s.obn_off >= 0 ? s.obn_off : -1;
+    info[STABNET_SI_MERGED_OFF] = s.fvec_off >= 0 ? (long)(2 * net->G + net->stem_w_floats) + s.fvec_off : -1;
+    info[STABNET_SI_W_ROWRUN_OFF] = a.rowrun ? (long)(2 * net->G) : -1;
+    info[STABNET_SI_W_IMAGE_OFF] = w_img ? (long)(w_img - fold) : -1;
+    info[STABNET_SI_INF_PREACTIVATED] = s.inf_preactivated; info[STABNET_SI_PROLOGUE] = a.in_scale ? 1 : 0;
+    info[STABNET_SI_SPLITK] = a.splitk; info[STABNET_SI_STEPS_PER_SPLIT] = a.steps_per_split; info[STABNET_SI_TOTAL_STEPS] = conv_plan_total_steps(a);
+    info[STABNET_SI_FAMILY] = r.family; info[STABNET_SI_MODE] = r.mode; info[STABNET_SI_OPERAND] = r.operand; info[STABNET_SI_KG] = r.kg;
+    info[STABNET_SI_PRO] = r.pro; info[STABNET_SI_NBUF] = r.nbuf; info[STABNET_SI_BK] = r.bk; info[STABNET_SI_TILE] = r.tile;
+    info[STABNET_SI_ASTAT_BM] = r.astat_bm; info[STABNET_SI_PATCH_CFG] = r.patch_cfg; info[STABNET_SI_REDUCE] = r.reduce;
+    info[STABNET_SI_PROF_KIND] = r.prof_kind;
+    info[STABNET_SI_TILES] = g.tiles; info[STABNET_SI_WGS] = g.wgs; info[STABNET_SI_GX] = g.gx; info[STABNET_SI_GY] = g.gy; info[STABNET_SI_GZ] = g.gz;
+    info[STABNET_SI_DIV_HW_MUL] = a.div_hw_mul; info[STABNET_SI_DIV_HW_SHIFT] = a.div_hw_shift;
+    info[STABNET_SI_DIV_W_MUL] = a.div_w_mul; info[STABNET_SI_DIV_W_SHIFT] = a.div_w_shift;
+    info[STABNET_SI_LDS_BYTES] = r.family == CONV_ASTAT ? (long)conv_astat_plane_bytes(r, a) : r.family == CONV_PATCH ? (long)conv_patch_lds_bytes(r, a) : 0;
+    info[STABNET_SI_LDS_LIMIT] = r.family == CONV_ASTAT ? (long)conv_astat_plane_limit() : r.family == CONV_PATCH ? (long)conv_patch_lds_limit() : 0;
+    return STABNET_OK;
+}
+
+/* Steps first..last of stabnet_backbone_fwd_infer on the caller's workspace, bound and launched by the code of the whole forward
+ * (run_steps); nothing outside the range is launched.  x_tensor / theta may be null when no step of the range reads / writes them. */
+int stabnet_net_run_steps(const void* netp, const float* params, const float* fold, const float* x_tensor, float* theta,
+                          void* workspace, size_t workspace_bytes, int first, int last, void* stream) {
+    const Net* net = static_cast<const Net*>(netp);
+    SN_REQUIRE(net && params && fold && workspace, "net_run_steps: null pointer");
+    SN_REQUIRE(!net->keep_all, "net_run_steps: inference plans only (keep_activations = 0)");
+    SN_REQUIRE(first >= 0 && first <= last && last < (int)net->steps.size(), "net_run_steps: steps %d..%d outside the plan's %d steps", first, last,
+               (int)net->steps.size());
+    if (workspace_bytes < stabnet_net_workspace_bytes(netp)) {
+        stabnet_set_error("net_run_steps: workspace %zu B < %zu B needed", workspace_bytes, stabnet_net_workspace_bytes(netp));
+        return STABNET_ERR_WORKSPACE;
+    }
+    const bool fused_head = head_fused_supported(net->N, net->t_last.C, net->fc_dims);
+    for (int i = first; i <= last; ++i) {
+        const Step& s = net->steps[i];
+        SN_REQUIRE(s.kind != S_PAD || x_tensor != nullptr, "net_run_steps: step %d reads x_tensor", i);
+        SN_REQUIRE(!(s.kind == S_FC && s.out_off == EXT_OUT) || theta != nullptr, "net_run_steps: step %d writes theta", i);
+    }
+    SN_REQUIRE(!(fused_head && last + 1 == (int)net->steps.size()) || theta != nullptr, "net_run_steps: the last step writes theta");
+    int rc = sn_check_device(params, "net_run_steps: params", (hipStream_t)stream);
+    if (rc == 0) rc = sn_check_device(workspace, "net_run_steps: workspace", (hipStream_t)stream);
+    if (rc) return rc;
+    return run_steps(net, params, fold, x_tensor, theta, static_cast<float*>(workspace), (hipStream_t)stream, first, last);
 }
 
 /* History ring initialisation: `depth` copies of the first frame, zero masks (deploy_bundle.py:216-224). */

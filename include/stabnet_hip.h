@@ -191,6 +191,60 @@ size_t stabnet_net_fold_floats(const void* net);
 int stabnet_backbone_fwd_infer(const void* net, const float* params, const float* fold, const float* x_tensor,
                                float* theta, void* workspace, size_t workspace_bytes, void* stream, void* prof);
 
+/* ---- inference plans, one step at a time (keep_activations = 0 only) -------------------------------------------
+ * A plan is a list of steps: 0 pad / embed the input, 1 convolution, 2 max-pool, 3 global pool, 4 fully connected, 5 conv2 -> conv3
+ * as one launch (STABNET_CONV_B2B_PLAN=1 plans).  stabnet_net_step_info() says what a step is and, for a convolution (kind 1),
+ * everything its launch is made of, as the forward would bind and route it in the plan's operand mode (stabnet_net_set_bf16_operands)
+ * on a chip of `cus` CUs.  HOST ONLY: no GPU is needed and the device is not read -- `cus` is the caller's (an MI355X has 256).
+ * info[STABNET_SI_*], `cap` >= STABNET_SI_FIELDS (= stabnet_net_step_info_fields()) longs; every field of a non-conv step but KIND is 0:
+ *   geometry      N H W CIN HO WO COUT KH KW STRIDE PAD, X_LD / RES_LD (floats between pixels of the input / residual), RES_H RES_W
+ *                 RES_STRIDE, ROWRUN (the stem's row-run operand), RELU_OUT (the flag as bound), M = N*HO*WO, K
+ *   workspace     float offsets: IN_OFF (first float read), IN_BASE / IN_FLOATS (the whole buffer the input lives in: all X_LD columns,
+ *                 the row-run stem's border and slack row), OUT_OFF / OUT_FLOATS, RES_OFF (-1: none) / RES_FLOATS (whole buffer, all
+ *                 RES_LD columns), SCRATCH_OFF (the split-K slabs start here) / SCRATCH_FLOATS (splitk * M * COUT when a reduce launch
+ *                 follows, else 0)
+ *   params        float offsets into `params`: W_OFF (OHWI weights), BIAS_OFF (-1: none)
+ *   fold          PRO_BN_OFF / OUT_BN_OFF: channel offset c of the input prologue / the consumer's BN + ReLU (scale fold[c ..], shift
+ *                 fold[bn_channels + c ..]; -1: none); MERGED_OFF: float offset of the [bias | scale | shift | floor][COUT] vectors
+ *                 of a merged shortcut | conv1 launch (they REPLACE bias, output BN and the ReLU flag; -1: none); W_ROWRUN_OFF: the
+ *                 row-run copy of the stem's weights (-1: not row-run); W_IMAGE_OFF: the pre-split weight image the launch comes with
+ *                 (-1: none)
+ *   flags         INF_PREACTIVATED (the input already holds relu(bn(.))), PROLOGUE (the launch applies BN + ReLU to its input)
+ *   K split       SPLITK, STEPS_PER_SPLIT, TOTAL_STEPS (K-steps of the whole reduction)
+ *   route         conv_route()'s answer for the bound launch: FAMILY (0 register-staged, 1 ring, 2 ring with K groups, 3 ring with
+ *                 prologue, 4 packed, 5 packed with two K groups, 6 A-stationary, 7 patch-stationary), MODE, OPERAND, KG, PRO, NBUF, BK,
+ *                 TILE, ASTAT_BM, PATCH_CFG, REDUCE (a split-K reduce launch follows), PROF_KIND (stabnet_prof_kind_name)
+ *   grid          TILES and WGS = GX * GY * GZ workgroups by the launchers' own rule: (M tile, N tile, K slice) of the 64 x 64 kernels,
+ *                 (M tile | patch, pass over the column blocks a workgroup's waves take side by side) of the A-stationary and patch kernels
+ *   index math    DIV_HW_MUL / _SHIFT, DIV_W_MUL / _SHIFT: the multiply-high constants the kernels divide by HO*WO and WO with
+ *   LDS           LDS_BYTES / LDS_LIMIT: the A-stationary kernel's planes, the patch kernel's launch, and what the launcher holds them to
+ * stabnet_net_run_steps() enqueues steps first..last of stabnet_backbone_fwd_infer on the caller's workspace, bound and launched by the
+ * forward's own code, and nothing else (the fused head's last launch belongs to the last step).  x_tensor / theta may be NULL when no
+ * step of the range reads / writes them.  Returns an error and launches nothing for a training plan, a bad range or a workspace
+ * smaller than stabnet_net_workspace_bytes(). */
+enum {
+    STABNET_SI_KIND = 0,
+    STABNET_SI_N, STABNET_SI_H, STABNET_SI_W, STABNET_SI_CIN, STABNET_SI_HO, STABNET_SI_WO, STABNET_SI_COUT, STABNET_SI_KH, STABNET_SI_KW,
+    STABNET_SI_STRIDE, STABNET_SI_PAD, STABNET_SI_X_LD, STABNET_SI_RES_LD, STABNET_SI_RES_H, STABNET_SI_RES_W, STABNET_SI_RES_STRIDE,
+    STABNET_SI_ROWRUN, STABNET_SI_RELU_OUT, STABNET_SI_M, STABNET_SI_K,
+    STABNET_SI_IN_OFF, STABNET_SI_IN_BASE, STABNET_SI_IN_FLOATS, STABNET_SI_OUT_OFF, STABNET_SI_OUT_FLOATS, STABNET_SI_RES_OFF,
+    STABNET_SI_RES_FLOATS, STABNET_SI_SCRATCH_OFF, STABNET_SI_SCRATCH_FLOATS,
+    STABNET_SI_W_OFF, STABNET_SI_BIAS_OFF, STABNET_SI_PRO_BN_OFF, STABNET_SI_OUT_BN_OFF, STABNET_SI_MERGED_OFF, STABNET_SI_W_ROWRUN_OFF,
+    STABNET_SI_W_IMAGE_OFF, STABNET_SI_INF_PREACTIVATED, STABNET_SI_PROLOGUE,
+    STABNET_SI_SPLITK, STABNET_SI_STEPS_PER_SPLIT, STABNET_SI_TOTAL_STEPS,
+    STABNET_SI_FAMILY, STABNET_SI_MODE, STABNET_SI_OPERAND, STABNET_SI_KG, STABNET_SI_PRO, STABNET_SI_NBUF, STABNET_SI_BK, STABNET_SI_TILE,
+    STABNET_SI_ASTAT_BM, STABNET_SI_PATCH_CFG, STABNET_SI_REDUCE, STABNET_SI_PROF_KIND,
+    STABNET_SI_TILES, STABNET_SI_WGS, STABNET_SI_GX, STABNET_SI_GY, STABNET_SI_GZ,
+    STABNET_SI_DIV_HW_MUL, STABNET_SI_DIV_HW_SHIFT, STABNET_SI_DIV_W_MUL, STABNET_SI_DIV_W_SHIFT,
+    STABNET_SI_LDS_BYTES, STABNET_SI_LDS_LIMIT,
+    STABNET_SI_FIELDS
+};
+int stabnet_net_num_steps(const void* net);
+int stabnet_net_step_info_fields(void);
+int stabnet_net_step_info(const void* net, int step, int cus, long* info, int cap);
+int stabnet_net_run_steps(const void* net, const float* params, const float* fold, const float* x_tensor, float* theta,
+                          void* workspace, size_t workspace_bytes, int first, int last, void* stream);
+
 /* ---- inference: the non-convolution layers and the head of the plan, one entry per operator -----------------
  * The launchers that stabnet_backbone_fwd_infer / stabnet_deploy_frame / stabnet_net_fold_bn run, reachable one at a time.
  * The plan hands them shapes it laid out itself; these entries refuse (STABNET_ERR_BAD_ARG, nothing launched) what the
