@@ -65,7 +65,6 @@ class Trainer:
         # f32-MFMA launch beside the packed ones (wgrad, the 3x3 forward pairs: 60 % of the matrix time, neither can read a weight
         # image) runs 4-8 % slower.  It pays at larger batches (16 / 32 / 64 pairs per GPU: +2 / +3 / +6 %).
         if split_operands is None:
-            import os
             split_operands = os.environ.get("STABNET_TRAIN_SPLIT", "0") == "1"
         self.split_operands = bool(split_operands)
         if self.split_operands:

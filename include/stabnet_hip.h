@@ -510,7 +510,18 @@ int stabnet_tower_bwd(const void* net, const float* params, const float* d_theta
 /* The same backward in stabnet_net_num_grad_stages() stages (0: FC head + block4, 1: block3, 2: block2, 3: block1 + stem;
  * call them in this order).  When stage k's kernels are done the gradients in [lo, hi) of stabnet_net_grad_bucket(k) are
  * final for this tower -- a data-parallel host hands that bucket to the collective while the earlier layers are still in
- * backward (reverse layer order).  The BN gamma / beta sections (stabnet_net_bn_grad_range) are final after the last stage. */
+ * backward (reverse layer order).  The BN gamma / beta sections (stabnet_net_bn_grad_range) are final after the last stage.
+ * THE BUCKET CONTRACT (tests/test_bwd_stages_gpu.py, on snapshots of the buffer after every stage call, for this entry and for
+ * stabnet_towers_bwd_stage; tests/test_parallel_cpu.py for the layout):
+ *   - a stage writes only its own bucket and the BN range: nothing below, nothing above, nothing outside [0, trainable floats);
+ *   - an earlier stage's bucket is never touched again -- what stage k leaves there is what the whole backward leaves there;
+ *   - every weight and bias tensor of the bucket receives its gradient in that stage (no reduction is left pending), as an ADD
+ *     into whatever the buffer held; four stage calls give the bits of one stabnet_tower_bwd;
+ *   - the boundaries between stage buckets, and every conv weight / bias offset, are multiples of 4 floats (16 bytes): the float4
+ *     read-modify-writes of the slab reduction and of the FC weight gradient cannot reach into a neighbouring bucket.  The
+ *     boundary between bucket 0 and the BN range is written with 4-byte scalar accesses on both sides.
+ * The stages must be called in the order 0, 1, 2, 3, once each per backward: stage k reads the d(activation) stage k - 1 left in the
+ * workspace.  NOTHING ENFORCES THE ORDER -- a call out of order returns STABNET_OK and a wrong gradient. */
 int stabnet_tower_bwd_stage(const void* net, const float* params, const float* d_theta, float* grads, void* workspace,
                             size_t workspace_bytes, int stage, void* stream, void* prof);
 /* One backward stage of BOTH towers in lockstep (after stabnet_towers_fwd_train): the bucket of stage k then holds the sum of

@@ -90,3 +90,71 @@ def test_grad_buckets_partition_the_trainables():
         assert stage == want[key], (name, stage)
     # sizes: 121.6 MB in all at the reference's shapes; the FC + block4 bucket carries most of it
     assert abs(plan.n_trainable * 4 / 1e6 - 121.6) < 2.0 and (ranges[0][1] - ranges[0][0]) > 0.6 * plan.n_trainable
+
+
+def _plan_ranges(N, H, W):
+    import ctypes
+    from stabnet_amd import _lib
+    from stabnet_amd.config import Config
+    from stabnet_amd.regressor import NetPlan
+    plan = NetPlan(N, H, W, Config(height=H, width=W, batch_size=N), keep_activations=True)
+    lo, hi = ctypes.c_long(), ctypes.c_long()
+    ranges = []
+    for k in range(_lib.lib().stabnet_net_num_grad_stages()):
+        _lib.call("stabnet_net_grad_bucket", plan.handle, k, ctypes.byref(lo), ctypes.byref(hi))
+        ranges.append((lo.value, hi.value))
+    _lib.call("stabnet_net_bn_grad_range", plan.handle, ctypes.byref(lo), ctypes.byref(hi))
+    return plan, ranges, (lo.value, hi.value)
+
+
+def test_grad_buckets_do_not_depend_on_the_frame():
+    """Host-only: the bucket bounds and the name -> stage map are the network's, not the frame's -- the same at the three plan sizes
+    the GPU bucket tests run (tests/test_bwd_stages_gpu.py), so every rank of any shard size cuts the gradient alike."""
+    want = {"block4": 0, "fc/": 0, "block3": 1, "block2": 2, "block1": 3, "resnet_v2_50/conv1/": 3}
+    seen = []
+    for N, H, W in ((2, 64, 96), (3, 90, 130), (1, 75, 101)):
+        plan, ranges, bn = _plan_ranges(N, H, W)
+        assert len(ranges) == 4 and ranges[-1][0] == 0 and ranges[0][1] == bn[0] and bn[1] == plan.n_trainable
+        for k in range(3):
+            assert ranges[k][0] == ranges[k + 1][1] and ranges[k][0] < ranges[k][1]
+        stages = {}
+        for name, off, kind, dims, aux in plan.table:
+            if kind in (2, 3, 4, 5):
+                if kind in (2, 3):
+                    assert bn[0] <= off and off + dims[0] <= bn[1], name              # gamma / beta: inside the BN range, whole
+                continue
+            n = int(np.prod([d for d in dims if d > 0]))
+            stage = next(k for k, (a, b) in enumerate(ranges) if a <= off < b)
+            assert off + n <= ranges[stage][1], (name, "straddles the end of bucket", stage)
+            assert stage == want[next(k for k in want if k in name)], (name, stage)
+            stages[name] = stage
+        seen.append((ranges, bn, stages))
+    assert seen[0] == seen[1] == seen[2]
+
+
+def test_stage_bucket_boundaries_are_vector_aligned():
+    """Host-only: the 16-byte granule.  The slab reduction (csrc/conv_bwd.hip, wgrad_reduce_kernel / wgrad_reduce4_kernel), the FC
+    weight gradient (fc_bwd_w_kernel) and weight decay's body read-modify-write the gradient buffer one float4 per thread, while an
+    earlier stage's bucket is in flight on the communication stream.  Each such access starts at (tensor offset + a multiple of 4)
+    and every conv / FC tensor's element count is a multiple of 4 (wgrad_launch_g refuses anything else), so it stays inside its own
+    tensor exactly if every conv weight and bias OFFSET is a multiple of 4 floats -- and then no access can cross a boundary between
+    two stage buckets, which must themselves lie on the granule: B_k.lo for k = 0, 1, 2.
+
+    The B_0 / BN boundary is the one place the layout does not align by construction: the FC head ends with 50 x 512 + 50 floats.
+    What writes either side of it: fc_bias (the last tensor of B_0) receives `db[n] += bacc`, a 4-byte scalar read-modify-write, one
+    thread per output (fc_bwd_w_kernel; only dW is float4, and inside its rows: K % 4 == 0 is required); the BN gamma / beta sections
+    receive `d_gamma[c] += ..` / `d_beta[c] += ..`, 4-byte scalars (bn_bwd_finalize_kernel, launched by launch_bn_relu_bwd_g).  No
+    access wider than 4 bytes touches that boundary, so it may sit anywhere; today the plan rounds it up to the granule anyway."""
+    for N, H, W in ((2, 64, 96), (3, 90, 130), (1, 75, 101)):
+        plan, ranges, bn = _plan_ranges(N, H, W)
+        for k in range(3):
+            assert ranges[k][0] % 4 == 0, (k, ranges[k])
+        for name, off, kind, dims, aux in plan.table:
+            if kind in (0, 1):                                   # conv weights (OHWI, Cin padded) and conv biases
+                n = int(np.prod([d for d in dims if d > 0]))
+                assert off % 4 == 0 and n % 4 == 0, (name, off, n)
+            elif kind == 6:                                      # FC weights: float4 inside rows of K floats
+                assert off % 4 == 0 and dims[1] % 4 == 0, (name, off, dims)
+        # the last tensor below the BN range is the output layer's bias, written with scalar stores only
+        last = max((e for e in plan.table if e[1] < bn[0]), key=lambda e: e[1])
+        assert last[0] == "fc/fc_bias" and last[2] == 7 and last[1] + last[3][0] <= bn[0], last
