@@ -131,6 +131,19 @@ int conv_launch_pair(const ConvArgs& a, const ConvPair& pr, hipStream_t st, Prof
 bool conv_b2b_supported(const ConvArgs& c2, const ConvArgs& c3);
 int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof* prof = nullptr);
 
+// A unit's 1x1 `conv3` (+ bias + residual) and the next identity unit's 1x1 `conv1` as ONE launch (conv_pair_kernel.h): c3 / c1 are the
+// two planned convolutions as conv_launch() would take them in operand mode 4 (c1.in_scale / in_shift = the pre-activation between them,
+// c1.x is not read: it is c3.y).  conv_unit_pair_form(): the kernel's form for the pair, false if it does not take it -- both 1x1 / stride 1
+// / pad 0 over the same pixels without a K split, c1.Cin == c3.Cout a multiple of 128, a plain residual (stride 1, same map), c1.Cout 64
+// (BM = 64) or 128 (BM = 32), c3.K a multiple of 64 up to 256 with A tile + chunk within conv_unit_pair_lds_limit(), AND conv_route() sending the two launches to the kernels whose
+// arithmetic the fused kernel repeats: c3 to the exact-f32 register-staged kernel over 64 channels (f32 form, no image needed) or to a
+// packed kernel without prologue / K groups (packed form), c1 to the packed prologue kernel.  bound as in conv_route().
+struct ConvUnitPairForm { int f32a, bm; int prof_kind; size_t lds_bytes; };
+bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, bool bound, ConvUnitPairForm& f);
+size_t conv_unit_pair_lds_limit();
+ConvGrid conv_unit_pair_grid(const ConvUnitPairForm& f, const ConvArgs& c3);
+int conv_unit_pair_launch(const ConvArgs& c3, const ConvArgs& c1, const float* w3_img, const float* w1_img, hipStream_t st, Prof* prof = nullptr);
+
 // Exact unsigned division by an invariant divisor d >= 1 for numerators n < 2^31 (Granlund-Montgomery round-up form):
 //   l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1, n / d = (mulhi(mul, n) + n) >> l.
 // Three instructions instead of the ~40 of a software 32-bit division; the kernels' per-tile index setup is VALU work

@@ -27,6 +27,7 @@
 #include "conv_astat_kernel.h"
 #include "conv_patch_kernel.h"
 #include "conv_b2b_kernel.h"
+#include "conv_pair_kernel.h"
 
 // Sums the split-K partial slabs in a fixed order and applies the epilogue.  One thread per 4 channels.
 template <int PAIR>
@@ -118,6 +119,7 @@ struct ConvSwitches {
     int patch = env_int("STABNET_CONV_PATCH", 1), patch_min_m = env_int("STABNET_CONV_PATCH_MIN_M", 0);
     int patch_cfg = env_int("STABNET_CONV_PATCH_CFG", 0);
     int b2b = env_int("STABNET_CONV_B2B", 1), b2b_wgs_per_cu = env_int("STABNET_CONV_B2B_WGS_PER_CU", 2);   // 80 KB of LDS each
+    int unit_pair = env_int("STABNET_CONV_PAIR", 1);               // 0: no pair of launches is fused (conv_unit_pair_form() refuses)
 };
 static const ConvSwitches& sw() {
     static const ConvSwitches s;
@@ -388,7 +390,7 @@ int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
 const char* conv_prof_kind_name(int kind) {
     // every route the launchers take, named as rocprofv3 prints the template instantiation, at the kind route_prof_kind() gives it
     static const std::vector<std::string> names = [] {
-        std::vector<std::string> v(PK_KERNEL_CONV_BASE + 144);
+        std::vector<std::string> v(PK_KERNEL_CONV_UNIT_PAIR + 4);
         char buf[96];
         auto ring = [&](int family, int mode, int operand, int kg, int pro) {
             ConvRoute r{};
@@ -433,6 +435,10 @@ const char* conv_prof_kind_name(int kind) {
         }
         v[PK_KERNEL_CONV_B2B] = "conv_b2b_f32_kernel<2>";
         v[PK_KERNEL_CONV_B2B + 1] = "conv_b2b_f32_kernel<4>";
+        for (int i = 0; i < 4; ++i) {
+            snprintf(buf, sizeof(buf), "conv_unit_pair_f32_kernel<%d, %d>", i >> 1, (i & 1) ? 64 : 32);
+            v[PK_KERNEL_CONV_UNIT_PAIR + i] = buf;
+        }
         return v;
     }();
     return (kind >= 0 && kind < (int)names.size() && !names[kind].empty()) ? names[kind].c_str() : nullptr;
@@ -913,6 +919,91 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
     return STABNET_OK;
 }
 
+// ---- conv3 -> next unit's conv1 as one launch (conv_pair_kernel.h) -------------------------------------------
+// A property a plan gets when asked (stabnet_net_fuse_unit_pairs, net.hip): conv_route() and the default plans do not know it.
+// Rule: both pair shapes of the network stay fused, by measurement (one visit, layer tables of the plan as built and of the fused plan,
+// profiles/r23_layers_*): the fused row beats the sum of its two rows at every size taken --
+//   f32 form <1, 64>   (64 -> 256 + residual, 256 -> 64)    720p, M = 57 600: 32.3 + 27.4 -> 53.7 us;  1080p, M = 129 600: 66.6 + 51.9 -> 107.0 us;
+//                                                            360 x 640, M = 14 400: 13.8 + 14.3 -> 20.5 us
+//   packed form <0, 32> (128 -> 512 + residual, 512 -> 128)  720p, M = 14 400: 21.3 + 22.9 -> 38.4 us; 1080p, M = 32 400: 42.0 + 40.8 -> 66.4 us
+// (the other two instantiations, <1, 32> and <0, 64>, are the same code for 64 -> N1 -> 128 and 128 -> N1 -> 64 channels: no plan of the
+// network has such a pair; the operator entry and its tests reach them).  Passes of 64 channels with the 64-row tile (half the chunk, three
+// workgroups per CU) were measured and dropped: 57.8 - 58.5 us against 55.5 - 56.1 us.
+constexpr size_t SN_PAIR_LDS_MAX = 96 * 1024;                 // the network's pairs take 48 / 64 KB (three / two workgroups per CU); K = 128 with 64-row tiles 96 KB
+size_t conv_unit_pair_lds_limit() { return SN_PAIR_LDS_MAX; }
+
+bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, bool bound, ConvUnitPairForm& f) {
+    f = ConvUnitPairForm{};
+    if (!sw().unit_pair) return false;
+    auto plain1x1 = [](const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.up == 1 && !a.rowrun && a.splitk == 1; };
+    if (!plain1x1(c3) || !plain1x1(c1)) return false;
+    if (c1.N != c3.N || c1.H != c3.Ho || c1.W != c3.Wo || c1.M != c3.M || c1.Cin != c3.Cout || c1.x_ld != c1.Cin) return false;
+    if (c3.Cout % 128 != 0 || c3.K % 64 != 0 || c3.K > 256 || (c1.Cout != 64 && c1.Cout != 128)) return false;
+    if (c3.res_stride != 1 || c3.res_H != c3.Ho || c3.res_W != c3.Wo || c3.res_ld % 4 != 0 || c3.x_ld % 4 != 0) return false;
+    if (c3.out_floor != nullptr || c1.out_floor != nullptr || c1.bias != nullptr || c1.residual != nullptr) return false;
+    if (bound ? (c3.out_scale != nullptr || c3.in_scale != nullptr || c1.in_scale == nullptr) : (c3.in_scale_expected != 0 || c1.in_scale_expected == 0)) return false;
+    // the two launches' own routes: the fused kernel repeats the arithmetic of exactly these kernels
+    const ConvRoute r3 = conv_route(c3, 4, img3, bound), r1 = conv_route(c1, 4, img1, bound);
+    if (!(r1.family == CONV_PACKED && r1.pro == 1 && r1.kg == 1 && r1.reduce == 0)) return false;
+    if (r3.family == CONV_IGEMM && r3.operand == 0 && r3.bk == 32 && c3.K == 64 && r3.reduce == 0) f.f32a = 1;
+    else if ((r3.family == CONV_ASTAT || (r3.family == CONV_PACKED && r3.pro == 0 && r3.kg == 1)) && r3.reduce == 0) f.f32a = 0;
+    else return false;
+    f.bm = c1.Cout == 64 ? 64 : 32;
+    f.lds_bytes = sn_pair_lds_bytes(f.f32a, f.bm, c3.K);
+    f.prof_kind = PK_KERNEL_CONV_UNIT_PAIR + 2 * f.f32a + (f.bm == 64 ? 1 : 0);
+    return f.lds_bytes <= SN_PAIR_LDS_MAX;
+}
+
+ConvGrid conv_unit_pair_grid(const ConvUnitPairForm& f, const ConvArgs& c3) {
+    ConvGrid g{};
+    g.gx = cdiv(c3.M, f.bm); g.gy = g.gz = 1;
+    g.tiles = g.wgs = g.gx;
+    return g;
+}
+
+template <int F32A, int BM>
+static int launch_unit_pair_one(const ConvUnitPairArgs& P, size_t lds, int gx, hipStream_t st) {
+    auto kern = conv_unit_pair_f32_kernel<F32A, BM>;
+    static bool configured = false;
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SN_PAIR_LDS_MAX);
+        if (e != hipSuccess) {
+            stabnet_set_error("conv unit pair: hipFuncSetAttribute(%zu B LDS) failed: %s", SN_PAIR_LDS_MAX, hipGetErrorString(e));
+            return STABNET_ERR_LAUNCH;
+        }
+        configured = true;
+    }
+    kern<<<gx, 256, lds, st>>>(P);
+    SN_LAUNCH_CHECK("conv_unit_pair_f32_kernel");
+    return STABNET_OK;
+}
+
+int conv_unit_pair_launch(const ConvArgs& c3, const ConvArgs& c1, const float* w3_img, const float* w1_img, hipStream_t st, Prof* prof) {
+    ConvUnitPairForm f;
+    SN_REQUIRE(conv_unit_pair_form(c3, c1, w3_img != nullptr, w1_img != nullptr, true, f), "conv unit pair: unsupported pair of convolutions");
+    SN_REQUIRE(c3.div_hw_mul != 0 && c1.div_hw_mul != 0, "conv unit pair: conv_plan() not called on both convolutions");
+    SN_REQUIRE(c3.x && c3.w && c3.y && c1.y && c1.in_scale && c1.in_shift && w1_img && (f.f32a || w3_img), "conv unit pair: null pointer");
+    SN_REQUIRE(c1.x == nullptr || c1.x == c3.y, "conv unit pair: conv1 must read conv3's output");
+    ConvUnitPairArgs P;
+    P.a = c3;
+    P.b = c1;
+    if (!f.f32a) P.a.w = w3_img;
+    P.b.w = w1_img;
+    P.b.x = c3.y;
+    const ConvGrid g = conv_unit_pair_grid(f, c3);
+    g_last_launch_kind = f.prof_kind;
+    const bool rec = prof != nullptr && prof->begin(st);
+    int rc;
+    if (f.f32a) rc = f.bm == 64 ? launch_unit_pair_one<1, 64>(P, f.lds_bytes, g.gx, st) : launch_unit_pair_one<1, 32>(P, f.lds_bytes, g.gx, st);
+    else rc = f.bm == 64 ? launch_unit_pair_one<0, 64>(P, f.lds_bytes, g.gx, st) : launch_unit_pair_one<0, 32>(P, f.lds_bytes, g.gx, st);
+    if (rec) prof->end(st, f.prof_kind, 2.0 * c3.M * ((double)c3.K * c3.Cout + (double)c1.K * c1.Cout),
+                       // algorithmic bytes: conv3's input + both weights + conv3's output + the residual read + conv1's output
+                       4.0 * ((double)c3.M * c3.K + (double)c3.K * c3.Cout + (double)c1.K * c1.Cout + (double)c3.M * c3.Cout * (c3.residual ? 2 : 1) +
+                              (double)c1.M * c1.Cout),
+                       c3.M, c1.Cout, c3.K + c1.K, 1);
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 static int fill_args(ConvArgs& a, const float* x, const float* w, const float* bias, const float* in_scale,
                      const float* in_shift, const float* residual, int res_H, int res_W, int res_stride, float* y,
@@ -1100,6 +1191,26 @@ int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, 
     a.out_scale = out_scale;
     a.out_shift = out_shift;
     return conv_launch(a, (hipStream_t)stream, nullptr, 4, w_img);
+}
+
+/* conv3 -> next unit's conv1 as one launch (include/stabnet_hip.h) */
+int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float* w3_img, const float* bias3, const float* residual, int res_ld,
+                               const float* pre_scale, const float* pre_shift, const float* w1_ohwi, const float* w1_img, const float* out_scale,
+                               const float* out_shift, float* y3, float* y1, int N, int H, int W, int K1, int N1, int N2, int relu_out, void* stream) {
+    SN_REQUIRE(x && w3_ohwi && pre_scale && pre_shift && w1_ohwi && w1_img && y3 && y1, "conv_unit_pair_fwd: null pointer");
+    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv_unit_pair_fwd: out_scale and out_shift go together");
+    SN_REQUIRE(res_ld == 0 || (res_ld >= N1 && res_ld % 4 == 0), "conv_unit_pair_fwd: res_ld=%d must be 0 or a multiple of 4 >= N1=%d", res_ld, N1);
+    ConvArgs c3, c1;
+    int rc = fill_args(c3, x, w3_ohwi, bias3, nullptr, nullptr, residual, H, W, 1, y3, N, H, W, K1, N1, 1, 1, 1, 0, 0);
+    if (rc) return rc;
+    c3.res_ld = res_ld;
+    (void)plan_packed(c3, 1);
+    rc = fill_args(c1, y3, w1_ohwi, nullptr, pre_scale, pre_shift, nullptr, 0, 0, 1, y1, N, H, W, N1, N2, 1, 1, 1, 0, relu_out);
+    if (rc) return rc;
+    (void)plan_packed(c1, 1);
+    c1.out_scale = out_scale;
+    c1.out_shift = out_shift;
+    return conv_unit_pair_launch(c3, c1, w3_img, w1_img, (hipStream_t)stream);
 }
 
 /* conv2 (3x3, pad 1, stride 1 | 2, C -> C channels, C = 64 | 128, no bias) -> folded BN (mid_scale, mid_shift) + ReLU -> conv3

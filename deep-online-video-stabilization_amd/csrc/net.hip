@@ -27,7 +27,8 @@
 extern "C" int stabnet_black_accumulate(const float* black, int* all_black, long n, void* stream);
 
 enum { PK_CONV_W = 0, PK_BIAS = 1, PK_GAMMA = 2, PK_BETA = 3, PK_MEAN = 4, PK_VAR = 5, PK_FC_W = 6, PK_FC_B = 7 };
-enum { S_PAD = 0, S_CONV = 1, S_POOL = 2, S_GAP = 3, S_FC = 4, S_CONV_B2B = 5 /* conv2 -> conv3 of a unit as one launch (inference) */ };
+enum { S_PAD = 0, S_CONV = 1, S_POOL = 2, S_GAP = 3, S_FC = 4, S_CONV_B2B = 5 /* conv2 -> conv3 of a unit as one launch (inference) */,
+       S_CONV_PAIR = 6 /* conv3 -> the next unit's conv1 as one launch (inference plans in operand mode 4, stabnet_net_fuse_unit_pairs) */ };
 static int fc_launches(int M) { int n = 0, m0 = 0; for (; M - m0 > 8; m0 += 16) ++n; return n + (m0 < M ? 1 : 0); }   // launch_fc's passes
 static const long EXT_IN = -2, EXT_OUT = -3, NONE = -1;
 
@@ -57,6 +58,8 @@ struct Step {
     // output tensor, written only when the step runs as two launches (bf16-operand mode)
     ConvArgs conv_b;
     long mid_obn_off, w3_off, mid_out_off;
+    // S_CONV_PAIR: a copy of the conv3 step; Net::plain_steps[pair_first] and [pair_first + 1] are the two S_CONV steps it stands for
+    int pair_first;
     int N, H, W, C, Ho, Wo, k, stride, pt, pl;   // pool / pad / gap
     int M, K, Nout, relu;                        // fc
     size_t splitk_bytes;
@@ -138,6 +141,8 @@ struct Net {
     size_t n_floats = 0, n_trainable = 0, G = 0;
     size_t off_gamma = 0, off_beta = 0, off_mean = 0, off_var = 0;
     std::vector<Step> steps;
+    std::vector<Step> plain_steps;                // the plan as built, kept while `steps` holds fused pairs (stabnet_net_fuse_unit_pairs); empty otherwise
+    const std::vector<Step>& built_steps() const { return plain_steps.empty() ? steps : plain_steps; }
     size_t act_floats = 0, splitk_bytes = 0;
     double flops = 0;
     int feat_H = 0, feat_W = 0;
@@ -595,7 +600,7 @@ static int run_steps(const Net* net, const float* params, const float* fold, con
         int rc = STABNET_OK;
         if (s.kind == S_PAD && skip_pad) continue;
         if (s.kind == S_FC && fused_head && (s.in_off == net->t_gap.off || s.out_off == EXT_OUT)) continue;   // fc_1 rides with the GAP, the output layer with the mesh
-        const bool rec = (s.kind != S_CONV && s.kind != S_CONV_B2B) && prof != nullptr && prof->begin(st);
+        const bool rec = (s.kind != S_CONV && s.kind != S_CONV_B2B && s.kind != S_CONV_PAIR) && prof != nullptr && prof->begin(st);
         switch (s.kind) {
             case S_PAD:
                 if (net->stem_rowrun) rc = launch_embed_border(x, s.N, s.H, s.W, s.C, 3, ws + s.out_off, st);   // (+ the slack row)
@@ -622,6 +627,13 @@ static int run_steps(const Net* net, const float* params, const float* fold, con
                     rc = conv_launch(a, st, prof, net->bf16_operands);
                     if (!rc) rc = conv_launch(b, st, prof, net->bf16_operands);
                 }
+                break;
+            }
+            case S_CONV_PAIR: {
+                const float *w3_img = nullptr, *w1_img = nullptr;
+                const ConvArgs a = bind_conv(net, net->plain_steps[s.pair_first], params, fold, ws, w3_img);
+                const ConvArgs b = bind_conv(net, net->plain_steps[s.pair_first + 1], params, fold, ws, w1_img);
+                rc = conv_unit_pair_launch(a, b, w3_img, w1_img, st, prof);
                 break;
             }
             case S_POOL:
@@ -813,6 +825,64 @@ int stabnet_net_set_bf16_operands(void* netp, int on) {
         return STABNET_OK;
     }
     net->bf16_operands = (on >= 1 && on <= 4) ? on : 0;     // 1: bf16 operands; 2 / 3: split operands (conv_kernel.h sn_split3)
+    if (!net->plain_steps.empty()) {                        // fused unit pairs belong to the mode they were asked in: back to the plan as built
+        net->steps = net->plain_steps;
+        net->plain_steps.clear();
+    }
+    return STABNET_OK;
+}
+
+/* conv3 -> next unit's conv1 as one launch (include/stabnet_hip.h) */
+static bool ranges_meet(long a, size_t an, long b, size_t bn) { return a < b + (long)bn && b < a + (long)an; }
+int stabnet_net_fuse_unit_pairs(void* netp, int on) {
+    Net* net = static_cast<Net*>(netp);
+    SN_REQUIRE(net != nullptr, "fuse_unit_pairs: null net");
+    if (!net->plain_steps.empty()) {                        // from the plan as built, whatever was asked before
+        net->steps = net->plain_steps;
+        net->plain_steps.clear();
+    }
+    if (!on || net->keep_all || net->bf16_operands != 4) return STABNET_OK;
+    // Smallest M: REASONED as the patch kernel's is, not measured -- 12288 rows are 192 tiles of 64 rows / 384 of 32, from where on the one
+    // workgroup per M tile fills most of the chip's resident slots; it also leaves the 288 x 512 frame (M = 9216) and every recorded
+    // small-shape route alone.  STABNET_CONV_PAIR_MIN_M lowers it for tests.
+    static const int min_m = []() { const char* v = getenv("STABNET_CONV_PAIR_MIN_M"); return v ? atoi(v) : 12288; }();
+    const float* fold0 = reinterpret_cast<const float*>((size_t)2 << 40);      // placeholder bases (stabnet_net_step_info): never dereferenced
+    std::vector<Step> fused;
+    const std::vector<Step>& st = net->steps;
+    for (size_t i = 0; i < st.size(); ++i) {
+        bool take = false;
+        if (i + 1 < st.size() && st[i].kind == S_CONV && st[i + 1].kind == S_CONV) {
+            const Step &c3 = st[i], &c1 = st[i + 1];
+            const float *w3_img = nullptr, *w1_img = nullptr;
+            const ConvArgs a = bind_conv(net, c3, reinterpret_cast<const float*>((size_t)1 << 40), fold0, reinterpret_cast<float*>((size_t)3 << 40), w3_img);
+            const ConvArgs b = bind_conv(net, c1, reinterpret_cast<const float*>((size_t)1 << 40), fold0, reinterpret_cast<float*>((size_t)3 << 40), w1_img);
+            ConvUnitPairForm f;
+            // conv3 of a unit whose successor is an identity unit (no consumer BN), conv1 the very next step reading exactly its output
+            // through the prologue; conv1's output may share memory with nothing the other workgroups of the launch still read -- conv3's
+            // input and residual -- except as the same rows in place (same first float, same row pitch: a workgroup holds its rows of
+            // the input in LDS before it writes them)
+            const long o1 = c1.out_off;
+            const size_t n1 = (size_t)b.M * b.Cout;
+            const bool in_place = o1 == c3.in_off && c3.in_base == c3.in_off && a.x_ld == b.Cout && c3.in_floats == n1;
+            take = c3.obn_off < 0 && c3.res_off >= 0 && c1.in_off == c3.out_off && c1.in_base == c3.out_off && a.M >= min_m &&
+                   conv_unit_pair_form(a, b, w3_img != nullptr, w1_img != nullptr, true, f) &&
+                   (in_place || !ranges_meet(o1, n1, c3.in_base, c3.in_floats)) && !ranges_meet(o1, n1, c3.res_off, c3.res_floats) &&
+                   !ranges_meet(o1, n1, c3.out_off, (size_t)a.M * a.Cout);
+        }
+        if (take) {
+            Step p = st[i];
+            p.kind = S_CONV_PAIR;
+            p.pair_first = (int)i;
+            fused.push_back(p);
+            ++i;
+        } else {
+            fused.push_back(st[i]);
+        }
+    }
+    if (fused.size() != st.size()) {
+        net->plain_steps = net->steps;
+        net->steps = fused;
+    }
     return STABNET_OK;
 }
 
@@ -852,6 +922,7 @@ int stabnet_net_num_launches(const void* netp) {
     for (const Step& s : net->steps) {
         const int mode = net->bf16_operands;       // (mode 4 without a weight image: conv_launch runs the exact-f32 kernels)
         if (s.kind == S_CONV_B2B) n += b2b_fused(net) ? 1 : 2 + conv_reduce_launches(s.conv, mode) + conv_reduce_launches(s.conv_b, mode);
+        else if (s.kind == S_CONV_PAIR) n += 1;
         else n += (s.kind == S_CONV) ? 1 + conv_reduce_launches(s.conv, (mode == 4 && s.wimg_off < 0) ? 0 : mode)
                                      : (s.kind == S_FC ? fc_launches(s.M) : (s.kind == S_GAP ? 2 : 1));
     }
@@ -903,7 +974,7 @@ int stabnet_net_fold_bn(const void* netp, const float* params, float* fold, floa
     // `fold` has no image region): from the weights each launch reads
     if (net->keep_all) return STABNET_OK;
     float* img = fold + 2 * net->G + net->stem_w_floats + net->merge_floats;
-    for (const Step& s : net->steps) {
+    for (const Step& s : net->built_steps()) {              // (a fused pair reads the images of its two convolutions)
         if (s.kind != S_CONV || s.wimg_off < 0) continue;
         SN_REQUIRE((size_t)s.wimg_off + conv_weight_image_floats(s.conv.Cout, s.conv.K) <= net->wimg_floats, "fold_bn: weight image outside the fold buffer");
         const float* w = s.conv.rowrun ? fold + 2 * net->G : params + s.w_off;
@@ -951,7 +1022,9 @@ int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int c
     const Step& s = net->steps[step];
     for (int i = 0; i < STABNET_SI_FIELDS; ++i) info[i] = 0;
     info[STABNET_SI_KIND] = s.kind;
-    if (s.kind != S_CONV) return STABNET_OK;
+    // S_CONV_PAIR: the fields describe the conv3 half (routed as its own launch would be); PROF_KIND, the grid and the LDS fields are the fused launch's
+    const bool pair = s.kind == S_CONV_PAIR;
+    if (s.kind != S_CONV && !pair) return STABNET_OK;
     // placeholder bases, far enough apart that no two bound pointers meet; never dereferenced
     const float* params = reinterpret_cast<const float*>((size_t)1 << 40);
     const float* fold = reinterpret_cast<const float*>((size_t)2 << 40);
@@ -989,6 +1062,17 @@ int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int c
     info[STABNET_SI_DIV_W_MUL] = a.div_w_mul; info[STABNET_SI_DIV_W_SHIFT] = a.div_w_shift;
     info[STABNET_SI_LDS_BYTES] = r.family == CONV_ASTAT ? (long)conv_astat_plane_bytes(r, a) : r.family == CONV_PATCH ? (long)conv_patch_lds_bytes(r, a) : 0;
     info[STABNET_SI_LDS_LIMIT] = r.family == CONV_ASTAT ? (long)conv_astat_plane_limit() : r.family == CONV_PATCH ? (long)conv_patch_lds_limit() : 0;
+    if (pair) {
+        const float* w1_img = nullptr;
+        const ConvArgs b = bind_conv(net, net->plain_steps[s.pair_first + 1], params, fold, ws, w1_img);
+        ConvUnitPairForm f;
+        SN_REQUIRE(conv_unit_pair_form(a, b, w_img != nullptr, w1_img != nullptr, true, f), "step_info: step %d is no pair the fused kernel takes", step);
+        const ConvGrid pg = conv_unit_pair_grid(f, a);
+        info[STABNET_SI_PROF_KIND] = f.prof_kind;
+        info[STABNET_SI_TILES] = pg.tiles; info[STABNET_SI_WGS] = pg.wgs; info[STABNET_SI_GX] = pg.gx; info[STABNET_SI_GY] = pg.gy; info[STABNET_SI_GZ] = pg.gz;
+        info[STABNET_SI_LDS_BYTES] = (long)f.lds_bytes;
+        info[STABNET_SI_LDS_LIMIT] = (long)conv_unit_pair_lds_limit();
+    }
     return STABNET_OK;
 }
 

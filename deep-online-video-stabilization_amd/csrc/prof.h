@@ -27,6 +27,7 @@ enum {
     PK_KERNEL_CONV_ASTAT = 77 /* conv_astat_f32_kernel<32> */,
     PK_KERNEL_CONV_PATCH = 24 /* + 0: conv_patch_f32_kernel<8, 8, 1, 3>; + 1: <8, 8, 2, 3> (ConvRoute::patch_cfg - 1) */,
     PK_KERNEL_CONV_B2B = 96 /* conv_b2b_f32_kernel<2>; + 1: <4> */,
+    PK_KERNEL_CONV_UNIT_PAIR = 244 /* + 2 * F32A + (BM == 64): conv_unit_pair_f32_kernel<F32A, BM> (conv_pair_kernel.h) */,
     PK_KERNEL_CONV_SPLIT = 40 /* + 8 * (BF16 - 2) + slot, the read-time split modes 2 / 3: conv_ring_f32_kernel<MODE, BF16, KG, PRO>, slot 0..2 = <MODE, B, 1, 0>,
                                  3 / 4 = <0 / 1, B, 3, 0>, 5 = <0, B, 1, 1>, 6 = <0, B, 2, 1> */,
     PK_KERNEL_CONV_BASE = 100   // + MODE*6 + tile*2 + (BK==32) + 18 if NBUF == 1 + 36 * BF16 (conv_igemm_f32_kernel<..., NBUF, BF16>, BF16 0..3)

@@ -108,7 +108,7 @@ class StabNetStream:
         """operand_mode: conv operand mode of the regressor (regressor.Regressor; 4 = packed split kernels, what bench.py and
         deploy_bundle.py run; default 0 = exact f32 MFMA); bf16_operands=True is the older spelling of mode 1."""
         self.cfg, self.H, self.W, self.S, self.refine = cfg, H, W, streams, refine
-        self.reg = Regressor(params, streams, H, W, cfg, device, bf16_operands=bf16_operands, operand_mode=operand_mode)
+        self.reg = Regressor(params, streams, H, W, cfg, device, bf16_operands=bf16_operands, operand_mode=operand_mode, fuse_unit_pairs=True)
         dev = self.reg.device
         self.lags = [i for i in cfg.indices[1:] if i > 0]
         self.depth = max(self.lags)

@@ -99,6 +99,35 @@ def conv2d_packed(x, w_ohwi, bias=None, in_scale=None, in_shift=None, residual=N
     return y
 
 
+def conv_unit_pair(x, w3_ohwi, bias3, residual, pre_scale, pre_shift, w1_ohwi, out_scale=None, out_shift=None, relu_out=True,
+                   out3=None, out=None):
+    """A unit's 1x1 conv3 (+ bias + residual) and the next identity unit's 1x1 conv1 as one launch (stabnet_conv_unit_pair_fwd):
+    -> (y1, y3); bit-identical to conv2d_packed of the two convolutions (splitk = 1).  residual [N,H,W,Cr]: its first N1 channels are
+    read with a pixel stride of Cr."""
+    x = dev_f32(x, "x")
+    w3 = dev_f32(w3_ohwi, "w3")
+    w1 = dev_f32(w1_ohwi, "w1")
+    N, H, W, K1 = x.shape
+    N1, N2 = w3.shape[0], w1.shape[0]
+    assert tuple(w3.shape[1:]) == (1, 1, K1) and tuple(w1.shape[1:]) == (1, 1, N1)
+    y3 = _out(out3, (N, H, W, N1), x)
+    y1 = _out(out, (N, H, W, N2), x)
+    L = _lib.lib()
+    imgs = []
+    for w, co, ci in ((w3, N1, K1), (w1, N2, N1)):
+        img = torch.empty(int(L.stabnet_conv_weight_image_floats(co, 1, 1, ci)), dtype=torch.float32, device=x.device)
+        _lib.call("stabnet_conv_weight_split_image", ptr(w), co, 1, 1, ci, ptr(img), stream_ptr(x.device), device=x.device)
+        imgs.append(img)
+    res_ld = 0
+    if residual is not None:
+        assert tuple(residual.shape[:3]) == (N, H, W) and residual.shape[3] >= N1
+        res_ld = residual.shape[3]
+    _lib.call("stabnet_conv_unit_pair_fwd", ptr(x), ptr(w3), ptr(imgs[0]), ptr(bias3), ptr(residual), res_ld, ptr(pre_scale), ptr(pre_shift),
+              ptr(w1), ptr(imgs[1]), ptr(out_scale), ptr(out_shift), ptr(y3), ptr(y1), N, H, W, K1, N1, N2, int(relu_out),
+              stream_ptr(x.device), device=x.device)
+    return y1, y3
+
+
 def conv3x3_conv1x1(x, w2_ohwi, mid_scale, mid_shift, w3_ohwi, bias3=None, residual=None, res_stride=1, stride=1, relu_out=False,
                     out_scale=None, out_shift=None, x_ch0=0, res_ch0=0, out=None):
     """The tail of a bottleneck unit as one launch (stabnet_conv3x3_conv1x1_fwd): conv2 3x3 (pad 1, `stride`) -> folded BN + ReLU

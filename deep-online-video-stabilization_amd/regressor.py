@@ -87,7 +87,7 @@ class Regressor:
     """theta = Regressor(params)(x_tensor): resnet_v2_50 -> mean -> FC head in moving-average BN mode."""
 
     def __init__(self, params, N: int, H: int, W: int, cfg: Config = v2_93, device="cuda:0",
-                 keep_activations: bool = False, bf16_operands=False, operand_mode=None):
+                 keep_activations: bool = False, bf16_operands=False, operand_mode=None, fuse_unit_pairs=False):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -106,6 +106,8 @@ class Regressor:
                 _lib.lib().stabnet_conv_tuning_profile(0)
         if mode:
             _lib.call("stabnet_net_set_bf16_operands", self.plan.handle, mode)
+        if fuse_unit_pairs:            # mode 4: conv3 -> next conv1 as one launch where the plan allows it (a no-op in every other mode)
+            _lib.call("stabnet_net_fuse_unit_pairs", self.plan.handle, 1)
         flat = params if isinstance(params, np.ndarray) and params.ndim == 1 else self.plan.pack(params)
         self.params = torch.from_numpy(np.ascontiguousarray(flat)).to(self.device)
         self.fold = torch.empty(int(_lib.lib().stabnet_net_fold_floats(self.plan.handle)), dtype=torch.float32, device=self.device)

@@ -121,6 +121,17 @@ int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, i
 /* The Profiler kind of the convolution kernel the calling thread launched last (forward operators, back-to-back, dgrad, the conv
  * layers of a plan): the route the launch itself took with its pointers bound.  -1 before the first launch.  Host only. */
 int stabnet_conv_last_launch_kind(void);
+/* A bottleneck unit's 1x1 conv3 (K1 -> N1 channels, + bias3 + residual) and the next identity unit's 1x1 conv1 (N1 -> N2 channels) as
+ * ONE launch (conv_unit_pair_f32_kernel; the tail of one slim bottleneck_v2 unit and the head of the next, s_net_bundle_nobm.py:252-253):
+ *   y3 = conv3(x) + bias3 + residual            (written: the next unit's shortcut)
+ *   y1 = act(conv1(relu(y3 * pre_scale + pre_shift)) * out_scale + out_shift)      (out_scale / out_shift optional, relu_out the flag)
+ * bit-identical to stabnet_conv2d_fwd_packed of the two convolutions one after the other (splitk = 1).  x [N,H,W,K1], residual
+ * [N,H,W,N1] with res_ld floats between pixels (0 = N1); w3_img / w1_img = stabnet_conv_weight_split_image of the weights (w3_img may
+ * be null for K1 = 64, which multiplies the float32 weights).  K1 a multiple of 64 up to 256 (not 256 with N2 = 64), N1 a multiple
+ * of 128, N2 64 or 128, pre_shift behind pre_scale within 4 GiB (one buffer); STABNET_ERR_BAD_ARG otherwise. */
+int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float* w3_img, const float* bias3, const float* residual, int res_ld,
+                               const float* pre_scale, const float* pre_shift, const float* w1_ohwi, const float* w1_img, const float* out_scale,
+                               const float* out_shift, float* y3, float* y1, int N, int H, int W, int K1, int N1, int N2, int relu_out, void* stream);
 /* The tail of a slim bottleneck_v2 unit as ONE launch (resnet_v2 `bottleneck`, called at s_net_bundle_nobm.py:252-253; what the
  * inference plan runs for the block-1 / block-2 units of a frame): conv2 (3x3, pad 1, stride 1 | 2, C -> C channels, C = 64 | 128,
  * no bias) -> folded batch_norm (mid_scale, mid_shift) + ReLU -> conv3 (1x1, C -> Cout, Cout % C == 0) with conv2d_fwd_ex's
@@ -166,6 +177,16 @@ void stabnet_net_destroy(void* net);
  * writes itself, inside its workspace -- call it BEFORE stabnet_net_train_workspace_bytes().  Off by default in the Python
  * mirror (no sustained gain at 8 pairs per GPU on a power-limited part; it pays at larger batches). */
 int stabnet_net_set_bf16_operands(void* net, int on);
+/* Inference plans in operand mode 4: on != 0 replaces every eligible [conv3, next unit's conv1] pair of plan steps by ONE step (kind 6,
+ * conv_unit_pair_f32_kernel): conv3 still writes its output (the next residual), conv1 takes its operand from conv3's accumulators
+ * instead of reading that output back.  Bit-identical to the two launches.  A pair is eligible when both are 1x1 / stride 1 / pad 0
+ * without a K split, conv3 has no consumer BN, a residual of stride 1 and K <= 256, conv1 is the very next step, reads exactly
+ * conv3's output through its prologue and has 64 or 128 output channels, M >= 12288 (STABNET_CONV_PAIR_MIN_M lowers it for tests),
+ * conv_route() sends the two launches to the kernels whose arithmetic the fused kernel repeats, and conv1's output overlaps neither
+ * conv3's residual nor its input (other than in place).  on == 0 restores the plan as built; so does a later
+ * stabnet_net_set_bf16_operands().  In any other mode, on a training plan, or with STABNET_CONV_PAIR=0 the plan stays what it is.
+ * Workspace, fold buffer and tensor offsets never change.  Returns 0. */
+int stabnet_net_fuse_unit_pairs(void* net, int on);
 int stabnet_net_num_params(const void* net);
 int stabnet_net_param_info(const void* net, int idx, char* name, int name_cap, long* offset, int* kind, int* dims4,
                            int* aux);
@@ -193,7 +214,9 @@ int stabnet_backbone_fwd_infer(const void* net, const float* params, const float
 
 /* ---- inference plans, one step at a time (keep_activations = 0 only) -------------------------------------------
  * A plan is a list of steps: 0 pad / embed the input, 1 convolution, 2 max-pool, 3 global pool, 4 fully connected, 5 conv2 -> conv3
- * as one launch (STABNET_CONV_B2B_PLAN=1 plans).  stabnet_net_step_info() says what a step is and, for a convolution (kind 1),
+ * as one launch (STABNET_CONV_B2B_PLAN=1 plans), 6 conv3 -> the next unit's conv1 as one launch (stabnet_net_fuse_unit_pairs; the fields
+ * describe the conv3 half as its own launch would be routed, PROF_KIND / TILES .. GZ / LDS_* the fused launch).
+ * stabnet_net_step_info() says what a step is and, for a convolution (kind 1),
  * everything its launch is made of, as the forward would bind and route it in the plan's operand mode (stabnet_net_set_bf16_operands)
  * on a chip of `cus` CUs.  HOST ONLY: no GPU is needed and the device is not read -- `cus` is the caller's (an MI355X has 256).
  * info[STABNET_SI_*], `cap` >= STABNET_SI_FIELDS (= stabnet_net_step_info_fields()) longs; every field of a non-conv step but KIND is 0:
