@@ -54,8 +54,8 @@ struct Prof;
 int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof = nullptr, int bf16_operands = 0, const float* w_img = nullptr,
                 bool lowk_ring = false);
 
-// Which kernel a convolution runs: decided ONCE, by conv_route(), for the launcher (conv_launch), for the plan-time launch count
-// (conv_reduce_launches) and for the Profiler's kernel name alike.
+// Which kernel a convolution runs: decided ONCE, by conv_route(), for the launcher (conv_launch), for the plan's launch count and step
+// info (net.hip) and for the Profiler's kernel name alike.
 enum ConvFamily {
     CONV_IGEMM,        // register-staged conv_igemm_f32_kernel<tile, bk, ..., mode, nbuf, operand>
     CONV_RING,         // LDS-DMA ring, conv_ring_f32_kernel<mode, operand, 1, 0>
@@ -81,11 +81,13 @@ struct ConvRoute {
                        // multiplies both 32-row blocks of the patch with one B fragment)
 };
 // operand_mode: conv_launch's bf16_operands; has_image: the launch comes with a pre-split weight image (mode 4 without one is mode 0).
-// bound = true, the launcher's view: the pointers of `a` are the launch's.  bound = false, the plan-time view: the prologue is
-// a.in_scale_expected and every condition on a pointer that is bound later (in_scale / in_shift, out_scale, partial; out_floor is
-// read as the plan holds it) counts as met -- `reduce` is then the launcher's for every launch a plan makes.  Reads nothing but its
-// arguments, the once-per-process STABNET_CONV_* switches and the tuning hooks (stabnet_conv_tuning_*).
-ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound, bool lowk_ring = false /* see conv_launch() */);
+// The pointers of `a` are the launch's: a prologue is a.in_scale != null, and out_scale, out_floor and partial are looked at (never
+// through).  Host code that asks before memory exists binds placeholders (sn_placeholder_base).  Reads nothing but its arguments, the
+// once-per-process STABNET_CONV_* switches and the tuning hooks (stabnet_conv_tuning_*).
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool lowk_ring = false /* see conv_launch() */);
+// Base pointers for host code that wants the launcher's view of a launch whose memory does not exist yet: base k = k << 40, far enough
+// apart that no two pointers bound to different bases meet; never dereferenced.
+static inline float* sn_placeholder_base(int k) { return reinterpret_cast<float*>((size_t)k << 40); }
 // The grid of the conv launch of route `r` on a chip of `cus` CUs (less the reserved ones, stabnet_conv_reserve_cus): the ONE rule the
 // launchers size their grids by.  tiles = units of work the workgroups walk: (M tile, N tile, K slice) of the 64 x 64 kernels (K
 // groups inside the workgroup are no tiles), (M tile | patch, pass over the column blocks its waves take side by side) of the
@@ -110,9 +112,6 @@ int launch_weight_split_image(const float* w, int Cout, int K, float* img, hipSt
 struct WeightImageTable { long w_off[64], img_off[64], tprefix[65]; int Cout[64], K[64]; int n; };
 void weight_image_table_add(WeightImageTable& t, long w_off, long img_off, int Cout, int K);
 int launch_weight_split_images(const float* w_base, float* img_base, const WeightImageTable& t, hipStream_t st);
-// 1 if conv_launch() of this planned convolution is followed by a split-K reduce launch (0: no split, or the split runs inside the
-// workgroups): conv_route()'s plan-time view; operand_mode 4 = as conv_launch() with a weight image decides
-int conv_reduce_launches(const ConvArgs& a, int operand_mode = 0);
 
 // The two siamese towers of a training step as ONE launch (forward convolutions, conv_kernel.h).  `a` describes the pair as one
 // batch of 2N samples whose first N live where a.x / a.y / a.residual / a.in_scale / a.in_shift point; tiles of rows >= m_tower
@@ -137,9 +136,9 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
 // / pad 0 over the same pixels without a K split, c1.Cin == c3.Cout a multiple of 128, a plain residual (stride 1, same map), c1.Cout 64
 // (BM = 64) or 128 (BM = 32), c3.K a multiple of 64 up to 256 with A tile + chunk within conv_unit_pair_lds_limit(), AND conv_route() sending the two launches to the kernels whose
 // arithmetic the fused kernel repeats: c3 to the exact-f32 register-staged kernel over 64 channels (f32 form, no image needed) or to a
-// packed kernel without prologue / K groups (packed form), c1 to the packed prologue kernel.  bound as in conv_route().
+// packed kernel without prologue / K groups (packed form), c1 to the packed prologue kernel.  Pointers as in conv_route().
 struct ConvUnitPairForm { int f32a, bm; int prof_kind; size_t lds_bytes; };
-bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, bool bound, ConvUnitPairForm& f);
+bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, ConvUnitPairForm& f);
 size_t conv_unit_pair_lds_limit();
 ConvGrid conv_unit_pair_grid(const ConvUnitPairForm& f, const ConvArgs& c3);
 int conv_unit_pair_launch(const ConvArgs& c3, const ConvArgs& c1, const float* w3_img, const float* w1_img, hipStream_t st, Prof* prof = nullptr);

@@ -228,8 +228,7 @@ static bool ring_eligible(const ConvArgs& a, int tile, bool has_prologue, bool l
 // prologue; not on bf16 operands (mode 1).
 // The PRO form fetches a step's scales AND shifts with one DMA instruction: the shifts are addressed as an unsigned 32-bit byte
 // offset from the (running) scale pointer.  Callers of the public operators pass two independent pointers: a shift vector below
-// the scales, or 4 GiB or more above them, must take the register-staged kernel (which dereferences both pointers).  Plan time
-// (pointers not bound yet): true -- the launch decides again with the real pointers.
+// the scales, or 4 GiB or more above them, must take the register-staged kernel (which dereferences both pointers).
 static bool ring_pro_vectors_ok(const ConvArgs& a) {
     if (a.in_scale == nullptr || a.in_shift == nullptr) return true;
     const long d = (long)(a.in_shift - a.in_scale);                   // floats
@@ -298,25 +297,25 @@ static int route_prof_kind(const ConvRoute& r) {
     return split ? split + 3 + r.mode : PK_KERNEL_CONV_KG + r.mode;
 }
 
-ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool bound, bool lowk_ring) {
+ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool lowk_ring) {
     const ConvSwitches& s = sw();
     const bool image = operand_mode == 4 && has_image;
     const int op = operand_mode == 4 ? 0 : operand_mode;     // every kernel but the packed one runs mode 4 as exact f32
     int splitk_unused = 1;
     const int t = pick_tile(a, splitk_unused);
     const bool t64 = t == T64x64, bk32 = conv_bk(a) == 32;
-    const bool has_pro = bound ? a.in_scale != nullptr : a.in_scale_expected != 0;
+    const bool has_pro = a.in_scale != nullptr;
     const bool ring = ring_eligible(a, t, has_pro, lowk_ring && image);
-    const bool slabs = !bound || a.splitk == 1 || a.partial != nullptr;
+    const bool slabs = a.splitk == 1 || a.partial != nullptr;
     int kg = t64 ? conv_kgroups(a, op, ring, has_pro) : 1;
     // the packed split kernel has no three-way in-workgroup split-K (60 KiB of ring per group): a ring launch that would split K three
     // ways inside the workgroup goes through the slabs + reduce launch instead
     if (image && s.packed_kg3 && ring && kg == 3 && a.K % 32 == 0 && slabs) kg = 1;
-    const bool pro = kg == 1 && !ring && t64 && bk32 && (bound ? ring_pro_eligible(a, op) : ring_pro_geometry(a, op, has_pro));
+    const bool pro = kg == 1 && !ring && t64 && bk32 && ring_pro_eligible(a, op);
     // packed split kernel with the fragment prologue: 1x1 / stride 1 layers that carry an input BN + ReLU (register-staged kernel or
     // the two-group PRO ring form otherwise); a K split goes through the slabs + reduce launch, or runs as two K groups (below)
     const bool packed_pro = image && s.packed_pro && !ring && t64 && bk32 && ring_pro_geometry(a, op, has_pro) &&
-                            (!bound || a.out_floor == nullptr) /* the kernel's pair distance */ && ring_pro_vectors_ok(a) && slabs;
+                            a.out_floor == nullptr /* the kernel's pair distance */ && ring_pro_vectors_ok(a) && slabs;
     if (packed_pro) kg = 1;
     const bool packed = (image && ring && kg == 1 && a.K % 32 == 0) || packed_pro;
     // a two-way K split with equal halves runs inside the packed workgroup (no slabs, no reduce launch)
@@ -381,10 +380,6 @@ ConvRoute conv_route(const ConvArgs& a, int operand_mode, bool has_image, bool b
     }
     r.prof_kind = route_prof_kind(r);
     return r;
-}
-
-int conv_reduce_launches(const ConvArgs& a, int operand_mode) {
-    return a.splitk < 2 ? 0 : conv_route(a, operand_mode, operand_mode == 4, false).reduce;
 }
 
 const char* conv_prof_kind_name(int kind) {
@@ -522,24 +517,27 @@ size_t conv_patch_lds_limit() { return SN_PATCH_LDS_MAX; }
 int conv_plan_total_steps(const ConvArgs& a) { return conv_total_steps(a); }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
+// Dynamic LDS above what `kern` is set up for: a launch that needs `need` bytes opts the kernel in to `limit` bytes first.  `configured`
+// is the caller's record, one per kernel instantiation, of the size set up so far (64 KB need no opt-in).
+static int lds_opt_in(const void* kern, size_t need, size_t limit, size_t& configured, const char* who) {
+    if (need <= configured) return STABNET_OK;
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit);
+    if (e != hipSuccess) {
+        stabnet_set_error("%s: hipFuncSetAttribute(%zu B LDS) failed: %s", who, limit, hipGetErrorString(e));
+        return STABNET_ERR_LAUNCH;
+    }
+    configured = limit;
+    return STABNET_OK;
+}
+
 template <int BM, int BN, int BK, int WM, int WN, int MODE, int NBUF, int BF16 = 0>
 static int launch_one_nb(const ConvArgs& a, hipStream_t st) {
     constexpr size_t lds_op = NBUF * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
     constexpr size_t lds_epi = 4 * (size_t)SN_EPI_WAVE_BYTES;        // the epilogue's transposition scratch
     constexpr size_t lds = lds_op > lds_epi ? lds_op : lds_epi;
-    static bool configured = false;
+    static size_t configured = 64 * 1024;
     auto kern = conv_igemm_f32_kernel<BM, BN, BK, WM, WN, MODE, NBUF, BF16>;
-    if (!configured) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) {
-                stabnet_set_error("conv: hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-                return STABNET_ERR_LAUNCH;
-            }
-        }
-        configured = true;
-    }
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(kern), lds, lds, configured, "conv")) return rc;
     const ConvGrid g = igemm_grid(a, BM, BN);
     kern<<<dim3(g.gx, g.gy, g.gz), 256, lds, st>>>(a);
     SN_LAUNCH_CHECK("conv_igemm_f32_kernel");
@@ -651,15 +649,8 @@ template <int PH, int PW, int WR, int NS>
 static int launch_patch_one(const ConvArgs& a, int cus, hipStream_t st) {
     const size_t lds = sn_patch_lds_bytes(PH, PW, a.Cin);
     auto kern = conv_patch_f32_kernel<PH, PW, WR, NS>;
-    static size_t configured = 64 * 1024;                    // the largest dynamic LDS size this instantiation is set up for
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SN_PATCH_LDS_MAX);
-        if (e != hipSuccess) {
-            stabnet_set_error("conv: hipFuncSetAttribute(%zu B LDS) failed: %s", SN_PATCH_LDS_MAX, hipGetErrorString(e));
-            return STABNET_ERR_LAUNCH;
-        }
-        configured = SN_PATCH_LDS_MAX;
-    }
+    static size_t configured = 64 * 1024;
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(kern), lds, SN_PATCH_LDS_MAX, configured, "conv")) return rc;
     const ConvGrid g = patch_grid(a, PH, PW, WR, cus);
     const dim3 grid(g.gx, g.gy);
     kern<<<grid, 256, lds, st>>>(a);
@@ -769,7 +760,7 @@ int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof, int bf16_operands
     SN_REQUIRE(a.Cout % 4 == 0, "conv: Cout=%d must be a multiple of 4", a.Cout);
     SN_REQUIRE(a.splitk >= 1 && a.steps_per_split >= 1 && a.div_hw_mul != 0, "conv: conv_plan() not called");
     SN_REQUIRE(a.splitk == 1 || a.partial != nullptr, "conv: split-K needs a workspace");
-    const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, true, lowk_ring);
+    const ConvRoute r = conv_route(a, bf16_operands, w_img != nullptr, lowk_ring);
     SN_REQUIRE(r.family != CONV_IGEMM || a.x_ld == a.Cin, "conv: a strided input (x_ld %d != Cin %d) needs the ring kernel", a.x_ld, a.Cin);
     g_last_launch_kind = r.prof_kind;
     const bool rec = prof != nullptr && prof->begin(st);
@@ -932,7 +923,7 @@ int conv_b2b_launch(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st, Prof
 constexpr size_t SN_PAIR_LDS_MAX = 96 * 1024;                 // the network's pairs take 48 / 64 KB (three / two workgroups per CU); K = 128 with 64-row tiles 96 KB
 size_t conv_unit_pair_lds_limit() { return SN_PAIR_LDS_MAX; }
 
-bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, bool bound, ConvUnitPairForm& f) {
+bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool img1, ConvUnitPairForm& f) {
     f = ConvUnitPairForm{};
     if (!sw().unit_pair) return false;
     auto plain1x1 = [](const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.up == 1 && !a.rowrun && a.splitk == 1; };
@@ -941,9 +932,9 @@ bool conv_unit_pair_form(const ConvArgs& c3, const ConvArgs& c1, bool img3, bool
     if (c3.Cout % 128 != 0 || c3.K % 64 != 0 || c3.K > 256 || (c1.Cout != 64 && c1.Cout != 128)) return false;
     if (c3.res_stride != 1 || c3.res_H != c3.Ho || c3.res_W != c3.Wo || c3.res_ld % 4 != 0 || c3.x_ld % 4 != 0) return false;
     if (c3.out_floor != nullptr || c1.out_floor != nullptr || c1.bias != nullptr || c1.residual != nullptr) return false;
-    if (bound ? (c3.out_scale != nullptr || c3.in_scale != nullptr || c1.in_scale == nullptr) : (c3.in_scale_expected != 0 || c1.in_scale_expected == 0)) return false;
+    if (c3.out_scale != nullptr || c3.in_scale != nullptr || c1.in_scale == nullptr) return false;
     // the two launches' own routes: the fused kernel repeats the arithmetic of exactly these kernels
-    const ConvRoute r3 = conv_route(c3, 4, img3, bound), r1 = conv_route(c1, 4, img1, bound);
+    const ConvRoute r3 = conv_route(c3, 4, img3), r1 = conv_route(c1, 4, img1);
     if (!(r1.family == CONV_PACKED && r1.pro == 1 && r1.kg == 1 && r1.reduce == 0)) return false;
     if (r3.family == CONV_IGEMM && r3.operand == 0 && r3.bk == 32 && c3.K == 64 && r3.reduce == 0) f.f32a = 1;
     else if ((r3.family == CONV_ASTAT || (r3.family == CONV_PACKED && r3.pro == 0 && r3.kg == 1)) && r3.reduce == 0) f.f32a = 0;
@@ -964,15 +955,8 @@ ConvGrid conv_unit_pair_grid(const ConvUnitPairForm& f, const ConvArgs& c3) {
 template <int F32A, int BM>
 static int launch_unit_pair_one(const ConvUnitPairArgs& P, size_t lds, int gx, hipStream_t st) {
     auto kern = conv_unit_pair_f32_kernel<F32A, BM>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SN_PAIR_LDS_MAX);
-        if (e != hipSuccess) {
-            stabnet_set_error("conv unit pair: hipFuncSetAttribute(%zu B LDS) failed: %s", SN_PAIR_LDS_MAX, hipGetErrorString(e));
-            return STABNET_ERR_LAUNCH;
-        }
-        configured = true;
-    }
+    static size_t configured = 0;                            // (set up on the first launch, whatever it needs)
+    if (const int rc = lds_opt_in(reinterpret_cast<const void*>(kern), lds, SN_PAIR_LDS_MAX, configured, "conv unit pair")) return rc;
     kern<<<gx, 256, lds, st>>>(P);
     SN_LAUNCH_CHECK("conv_unit_pair_f32_kernel");
     return STABNET_OK;
@@ -980,7 +964,7 @@ static int launch_unit_pair_one(const ConvUnitPairArgs& P, size_t lds, int gx, h
 
 int conv_unit_pair_launch(const ConvArgs& c3, const ConvArgs& c1, const float* w3_img, const float* w1_img, hipStream_t st, Prof* prof) {
     ConvUnitPairForm f;
-    SN_REQUIRE(conv_unit_pair_form(c3, c1, w3_img != nullptr, w1_img != nullptr, true, f), "conv unit pair: unsupported pair of convolutions");
+    SN_REQUIRE(conv_unit_pair_form(c3, c1, w3_img != nullptr, w1_img != nullptr, f), "conv unit pair: unsupported pair of convolutions");
     SN_REQUIRE(c3.div_hw_mul != 0 && c1.div_hw_mul != 0, "conv unit pair: conv_plan() not called on both convolutions");
     SN_REQUIRE(c3.x && c3.w && c3.y && c1.y && c1.in_scale && c1.in_shift && w1_img && (f.f32a || w3_img), "conv unit pair: null pointer");
     SN_REQUIRE(c1.x == nullptr || c1.x == c3.y, "conv unit pair: conv1 must read conv3's output");
@@ -1094,7 +1078,7 @@ int stabnet_conv2d_fwd(const float* x, const float* w_ohwi, const float* bias, c
 
 /* The Profiler kind (stabnet_prof_kind_name) of the convolution kernel this thread launched last through conv_launch() -- the forward
  * operators, dgrad, the layers of a plan --, conv_launch_pair() or conv_b2b_launch(): the route the launch itself took with its
- * pointers bound, not a plan-time view.  -1 before the first launch.  Host only. */
+ * pointers.  -1 before the first launch.  Host only. */
 int stabnet_conv_last_launch_kind(void) { return g_last_launch_kind; }
 
 int stabnet_conv2d_fwd_ex(const float* x, const float* w_ohwi, const float* bias, const float* in_scale,
@@ -1148,15 +1132,18 @@ static size_t plan_packed(ConvArgs& a, int splitk) {
     return need;
 }
 
-/* The Profiler kind (stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry: conv_route()'s
- * plan-time view, with (prologue != 0) or without an input BN + ReLU.  Host only; < 0 on a bad geometry. */
+/* The Profiler kind (stabnet_prof_kind_name) of the conv launch stabnet_conv2d_fwd_packed makes for this geometry, with (prologue != 0)
+ * or without an input BN + ReLU: conv_route() of the launch bound to placeholders -- prologue vectors, split-K workspace and weight
+ * image; every other pointer null.  Host only; < 0 on a bad geometry. */
 int stabnet_conv2d_packed_kind(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int prologue, int splitk) {
     ConvArgs a;
     if (fill_args(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, N, H, W, Cin, Cout, KH, KW, stride, pad, 0))
         return STABNET_ERR_BAD_ARG;
     a.in_scale_expected = prologue ? 1 : 0;
     (void)plan_packed(a, splitk);
-    return conv_route(a, 4, true, false).prof_kind;       // (the call always comes with an image pointer)
+    if (prologue) { a.in_scale = sn_placeholder_base(1); a.in_shift = a.in_scale + a.Cin; }
+    a.partial = sn_placeholder_base(2);
+    return conv_route(a, 4, true).prof_kind;              // (the call always comes with an image pointer)
 }
 
 int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,

@@ -687,7 +687,7 @@ int dgrad_launch(const float* dy, const float* wt, float* dx, const float* resid
     }
     a.partial = splitk_ws;
     if (packed_out != nullptr) {                             // the route conv_launch() is about to take, for the operator tests
-        const int family = conv_route(a, wt_img != nullptr ? 4 : 0, wt_img != nullptr, true, true).family;
+        const int family = conv_route(a, wt_img != nullptr ? 4 : 0, wt_img != nullptr, true /* lowk_ring */).family;
         *packed_out = (family == CONV_PACKED || family == CONV_PACKED_KG2) ? 1 : 0;
     }
     // (with an image every launch the packed split kernel can take goes there, the two-step 1x1 ones included: conv.h, lowk_ring)

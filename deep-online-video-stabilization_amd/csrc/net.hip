@@ -27,8 +27,10 @@
 extern "C" int stabnet_black_accumulate(const float* black, int* all_black, long n, void* stream);
 
 enum { PK_CONV_W = 0, PK_BIAS = 1, PK_GAMMA = 2, PK_BETA = 3, PK_MEAN = 4, PK_VAR = 5, PK_FC_W = 6, PK_FC_B = 7 };
-enum { S_PAD = 0, S_CONV = 1, S_POOL = 2, S_GAP = 3, S_FC = 4, S_CONV_B2B = 5 /* conv2 -> conv3 of a unit as one launch (inference) */,
-       S_CONV_PAIR = 6 /* conv3 -> the next unit's conv1 as one launch (inference plans in operand mode 4, stabnet_net_fuse_unit_pairs) */ };
+// build_net() emits the first five kinds: the plain plan.  The two fused kinds stand for two consecutive S_CONV steps of it and are
+// put in by rebuild_steps() (inference plans only).
+enum { S_PAD = 0, S_CONV = 1, S_POOL = 2, S_GAP = 3, S_FC = 4, S_CONV_B2B = 5 /* conv2 -> conv3 of a unit as one launch (STABNET_CONV_B2B_PLAN=1) */,
+       S_CONV_PAIR = 6 /* conv3 -> the next unit's conv1 as one launch (operand mode 4, stabnet_net_fuse_unit_pairs) */ };
 static int fc_launches(int M) { int n = 0, m0 = 0; for (; M - m0 > 8; m0 += 16) ++n; return n + (m0 < M ? 1 : 0); }   // launch_fc's passes
 static const long EXT_IN = -2, EXT_OUT = -3, NONE = -1;
 
@@ -53,13 +55,9 @@ struct Step {
     long wimg_off;                               // inference only: this conv's pre-split weight image inside the image region of `fold`
     long fvec_off;                               // inference only: per-channel (bias, scale, shift, floor) vectors of a merged
                                                  // shortcut|conv1 launch, offset inside the merge region of `fold` (-1: none)
-    // S_CONV_B2B (inference plans): `conv` is the unit's 3x3 conv2 (in_off, w_off; its consumer BN bn2 = mid_obn_off), `conv_b` its
-    // 1x1 conv3 (w3_off, b_off, res_off, out_off, obn_off = the NEXT unit's pre-activation, if fused); mid_out_off = conv2's own
-    // output tensor, written only when the step runs as two launches (bf16-operand mode)
-    ConvArgs conv_b;
-    long mid_obn_off, w3_off, mid_out_off;
-    // S_CONV_PAIR: a copy of the conv3 step; Net::plain_steps[pair_first] and [pair_first + 1] are the two S_CONV steps it stands for
-    int pair_first;
+    // S_CONV_B2B / S_CONV_PAIR: a view, nothing but the kind and these two -- Net::plain_steps[first] and [first + 1] are the S_CONV
+    // steps it stands for; one_launch = 0: this operand mode runs the two as they are (S_CONV_B2B in modes 1 / 2 / 3)
+    int first, one_launch;
     int N, H, W, C, Ho, Wo, k, stride, pt, pl;   // pool / pad / gap
     int M, K, Nout, relu;                        // fc
     size_t splitk_bytes;
@@ -140,9 +138,9 @@ struct Net {
     std::vector<ParamEntry> bn_entries[4];        // gamma, beta, mean, var (appended after the weights)
     size_t n_floats = 0, n_trainable = 0, G = 0;
     size_t off_gamma = 0, off_beta = 0, off_mean = 0, off_var = 0;
-    std::vector<Step> steps;
-    std::vector<Step> plain_steps;                // the plan as built, kept while `steps` holds fused pairs (stabnet_net_fuse_unit_pairs); empty otherwise
-    const std::vector<Step>& built_steps() const { return plain_steps.empty() ? steps : plain_steps; }
+    std::vector<Step> plain_steps;                // the plan as build_net() made it
+    std::vector<Step> steps;                      // the plan that runs: rebuild_steps() of plain_steps (equal to it for training plans)
+    int unit_pairs = 0;                           // stabnet_net_fuse_unit_pairs asked for them in the operand mode the plan is in
     size_t act_floats = 0, splitk_bytes = 0;
     double flops = 0;
     int feat_H = 0, feat_W = 0;
@@ -228,6 +226,30 @@ static Step conv_step(Net& net, const TensorRef& in, const TensorRef& out, int K
     return s;
 }
 
+// ---- fusions: passes over the plain plan ---------------------------------------------------------------------------------
+// Steps i, i + 1 of the plain plan as ONE S_CONV_B2B step: a unit's 3x3 conv2 and the 1x1 conv3 that reads exactly its output
+// (conv_b2b_kernel.h: the activated conv2 tile stays in LDS, the low-K conv3 launch and the round trip of its input go).
+// OFF by default (STABNET_CONV_B2B_PLAN=1 turns it on): measured in the 720p frame (same box, same build) every choice
+// of units loses to the two launches -- all six eligible units 549.0 against 556.4 frames/s, the three 225-tile
+// units of block 1 / block 2 550.5, block 1's strided unit alone 555.3 (the fused
+// launch has no more matrix throughput per step than the two kernels, 80 / 136 KB of LDS leave two / one workgroup per
+// CU, and the 1x1 phase costs its 8 K-steps plus four epilogues that nothing overlaps).  The window [min_tiles,
+// max_tiles] and the d_b mask (bit 0: 64, bit 1: 128) select units when the plan switch is on.  Read once per process.
+static bool b2b_takes(const Net* net, size_t i) {
+    auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    static const int plan_on = env("STABNET_CONV_B2B_PLAN", 0);
+    static const int min_tiles = env("STABNET_CONV_B2B_MIN_TILES", 200), max_tiles = env("STABNET_CONV_B2B_MAX_TILES", 1 << 30);
+    static const int cmask = env("STABNET_CONV_B2B_CMASK", 3);
+    const std::vector<Step>& p = net->plain_steps;
+    if (!plan_on || net->keep_all || i + 1 >= p.size() || p[i].kind != S_CONV || p[i + 1].kind != S_CONV) return false;
+    const Step &c2 = p[i], &c3 = p[i + 1];
+    const int tiles = (c3.conv.M + 63) / 64;
+    return c3.in_off == c2.out_off && c3.in_base == c2.out_off && conv_b2b_supported(c2.conv, c3.conv) && tiles >= min_tiles && tiles <= max_tiles &&
+           ((c2.conv.Cout == 64 && (cmask & 1)) || (c2.conv.Cout == 128 && (cmask & 2)));
+}
+
+static void rebuild_steps(Net* net);             // (below, next to stabnet_net_fuse_unit_pairs)
+
 static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all) {
     Net* net = new Net();
     net->N = N; net->H = H; net->W = W; net->in_ch = in_ch; net->n_theta = n_theta; net->keep_all = keep_all;
@@ -301,7 +323,7 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
             // is a conv of the pre-activation), so its producer -- the max-pool or the previous block's last conv3 -- applies
             // this unit's preact BN + ReLU itself and both convs of the unit run prologue-free on the ring kernel.
             const bool pre_act = !keep_all && want_ring && cin != b.depth && !net->steps.empty() &&
-                                 (net->steps.back().kind == S_POOL || net->steps.back().kind == S_CONV || net->steps.back().kind == S_CONV_B2B) &&
+                                 (net->steps.back().kind == S_POOL || net->steps.back().kind == S_CONV) &&
                                  net->steps.back().out_off == cur.off && net->steps.back().obn_off < 0;
             if (pre_act) net->steps.back().obn_off = bn_pre;
             auto mark_preactivated = [&](Step& st_) {
@@ -389,35 +411,6 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
                     net->splitk_bytes = std::max(net->splitk_bytes, c3.splitk_bytes);
                 }
                 ui.w3 = w; ui.b3 = bb;
-            }
-            // Inference plan, block 1 / block 2 units with enough 64-pixel tiles to fill the chip: conv2 and conv3 as ONE launch
-            // (conv_b2b_kernel.h): the activated conv2 tile stays in LDS, the low-K conv3 launch and the round trip of its input go.
-            // OFF by default (STABNET_CONV_B2B_PLAN=1 turns it on): measured in the 720p frame (same box, same build) every choice
-            // of units loses to the two launches -- all six eligible units 549.0 against 556.4 frames/s, the three 225-tile
-            // units of block 1 / block 2 550.5, block 1's strided unit alone 555.3 (the fused
-            // launch has no more matrix throughput per step than the two kernels, 80 / 136 KB of LDS leave two / one workgroup per
-            // CU, and the 1x1 phase costs its 8 K-steps plus four epilogues that nothing overlaps).  The window [min_tiles,
-            // max_tiles] and the d_b mask (bit 0: 64, bit 1: 128) select units when the plan switch is on.
-            if (!keep_all && i_conv2 + 2 == net->steps.size()) {
-                auto env = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-                static const int plan_on = env("STABNET_CONV_B2B_PLAN", 0);
-                static const int min_tiles = env("STABNET_CONV_B2B_MIN_TILES", 200), max_tiles = env("STABNET_CONV_B2B_MAX_TILES", 1 << 30);
-                static const int cmask = env("STABNET_CONV_B2B_CMASK", 3);
-                const Step c2 = net->steps[i_conv2], c3 = net->steps[i_conv2 + 1];
-                const int tiles = (c3.conv.M + 63) / 64;
-                if (plan_on && conv_b2b_supported(c2.conv, c3.conv) && tiles >= min_tiles && tiles <= max_tiles &&
-                    ((c2.conv.Cout == 64 && (cmask & 1)) || (c2.conv.Cout == 128 && (cmask & 2)))) {
-                    Step f = c2;
-                    f.kind = S_CONV_B2B;
-                    f.conv_b = c3.conv;
-                    f.mid_obn_off = c2.obn_off; f.mid_out_off = c2.out_off;
-                    f.w3_off = c3.w_off; f.b_off = c3.b_off; f.res_off = c3.res_off; f.out_off = c3.out_off;
-                    f.obn_off = NONE;                        // conv3's consumer BN: set by the next unit if it is a projection unit
-                    f.splitk_bytes = std::max(c2.splitk_bytes, c3.splitk_bytes);
-                    net->steps.pop_back();
-                    net->steps.pop_back();
-                    net->steps.push_back(f);
-                }
             }
             ui.sc = sc; ui.r1 = r1; ui.r2 = r2; ui.out = nxt; ui.proj = own_sc; ui.bn1 = bn1; ui.bn2 = bn2;
             net->units.push_back(ui);
@@ -533,16 +526,20 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
             net->fimg_floats += conv_weight_image_floats(st_.conv.Cout, st_.conv.K);
         }
     }
+    net->plain_steps.swap(net->steps);          // what was built is the plain plan; rebuild_steps() below makes the plan that runs
     if (!net->keep_all) {  // pre-split weight images for the packed split kernel (stabnet_net_set_bf16_operands(net, 4))
-        for (Step& st_ : net->steps) {
-            if (st_.kind != S_CONV || st_.conv.K % 32 != 0) continue;
-            st_.wimg_off = (long)net->wimg_floats;
-            net->wimg_floats += conv_weight_image_floats(st_.conv.Cout, st_.conv.K);
+        std::vector<Step>& p = net->plain_steps;
+        for (size_t i = 0; i < p.size(); ++i) {
+            if (b2b_takes(net, i)) { ++i; continue; }      // no mode reads an image of these two: 0 and 4 run the exact-f32 fused kernel
+            if (p[i].kind != S_CONV || p[i].conv.K % 32 != 0) continue;
+            p[i].wimg_off = (long)net->wimg_floats;
+            net->wimg_floats += conv_weight_image_floats(p[i].conv.Cout, p[i].conv.K);
         }
     }
     net->act_floats = ar.peak;
     net->splitk_bytes = std::max(net->splitk_bytes, sizeof(float) * (size_t)N * std::max(8, gap_chunks(net->t_last.H * net->t_last.W)) * net->t_last.C);
     net->max_net = std::max({net->max_net, net->t_c1.size, net->t_pool.size});
+    rebuild_steps(net);
     return net;
 }
 
@@ -550,14 +547,9 @@ static Net* build_net(int N, int H, int W, int in_ch, int n_theta, int keep_all)
 // head (head.hip) they ride in the output layer's launch; `done` tells the caller whether run_forward did them.
 struct MeshTail { int gh, gw; float lim; float* Hs; int* head_adv; int depth; bool done; const float* prefetch_src = nullptr; /* the frame the sampler behind the mesh gathers from */ };
 
-// S_CONV_B2B steps: the fused kernel is exact f32 -- operand modes 0 and 4 run it (mode 4 has no weight images for these convolutions and
-// runs the exact-f32 kernels wherever no packed kernel takes a launch); modes 1 / 2 / 3 run conv2 and conv3 as two launches in their
-// own mode.  run_forward and stabnet_net_num_launches both follow this.
-static bool b2b_fused(const Net* net) { return net->bf16_operands == 0 || net->bf16_operands == 4; }
-
-// An S_CONV step of an inference plan as run_steps() launches it: the plan's ConvArgs with every pointer bound.  w_img: the
-// pre-split weight image the launch comes with (null: none).  Host arithmetic on the four base pointers only -- stabnet_net_step_info
-// binds a step to placeholder bases to ask conv_route() for the launcher's own view.
+// THE binder: a plan's S_CONV step as run_steps() launches it -- the plan's ConvArgs with every pointer bound.  w_img: the pre-split
+// weight image the launch comes with (null: none).  Host arithmetic on the three base pointers only, so host code that wants the
+// launcher's own view of a step before memory exists (the fusion passes, the launch count, stabnet_net_step_info) binds placeholders.
 static ConvArgs bind_conv(const Net* net, const Step& s, const float* params, const float* fold, float* ws, const float*& w_img) {
     const float* scale = fold;
     const float* shift = fold + net->G;
@@ -583,6 +575,30 @@ static ConvArgs bind_conv(const Net* net, const Step& s, const float* params, co
     a.partial = ws + net->act_floats;
     w_img = (net->bf16_operands == 4 && s.wimg_off >= 0 && !net->keep_all) ? fold + 2 * net->G + net->stem_w_floats + net->merge_floats + s.wimg_off : nullptr;
     return a;
+}
+static const float* const PH_PARAMS = sn_placeholder_base(1);
+static const float* const PH_FOLD = sn_placeholder_base(2);
+static float* const PH_WS = sn_placeholder_base(3);
+static ConvArgs bind_conv_placeholders(const Net* net, const Step& s, const float*& w_img) { return bind_conv(net, s, PH_PARAMS, PH_FOLD, PH_WS, w_img); }
+
+// An S_CONV step's launches: the kernel and, where the route the launcher takes says so, the split-K reduce.
+static int conv_step_launches(const Net* net, const Step& s) {
+    const float* w_img = nullptr;
+    const ConvArgs a = bind_conv_placeholders(net, s, w_img);
+    return 1 + conv_route(a, net->bf16_operands, w_img != nullptr).reduce;
+}
+// Launches of one step as the switch of run_steps() below makes them, case by case (the shortened head's saving is taken off the sum in
+// stabnet_net_num_launches).
+static int step_launches(const Net* net, const Step& s) {
+    const Step* half = (s.kind == S_CONV_B2B || s.kind == S_CONV_PAIR) ? &net->plain_steps[s.first] : nullptr;
+    switch (s.kind) {
+        case S_CONV: return conv_step_launches(net, s);
+        case S_CONV_B2B:
+        case S_CONV_PAIR: return s.one_launch ? 1 : conv_step_launches(net, half[0]) + conv_step_launches(net, half[1]);
+        case S_GAP: return 2;
+        case S_FC: return fc_launches(s.M);
+        default: return 1;
+    }
 }
 
 // Steps first..last of the inference forward (run_forward: all of them; stabnet_net_run_steps: the caller's range).  The fused head's
@@ -612,28 +628,19 @@ static int run_steps(const Net* net, const float* params, const float* fold, con
                 rc = conv_launch(a, st, prof, net->bf16_operands, w_img);
                 break;
             }
-            case S_CONV_B2B: {
-                ConvArgs a = s.conv, b = s.conv_b;
-                a.x = ws + s.in_off; a.w = params + s.w_off; a.y = ws + s.mid_out_off;
-                a.out_scale = scale + s.mid_obn_off; a.out_shift = shift + s.mid_obn_off; a.relu_out = 1;
-                b.x = ws + s.mid_out_off; b.w = params + s.w3_off; b.y = ws + s.out_off;
-                b.bias = s.b_off >= 0 ? params + s.b_off : nullptr;
-                b.residual = s.res_off >= 0 ? ws + s.res_off : nullptr;
-                if (s.obn_off >= 0) { b.out_scale = scale + s.obn_off; b.out_shift = shift + s.obn_off; b.relu_out = 1; }
-                a.partial = b.partial = splitk;
-                if (b2b_fused(net)) {
-                    rc = conv_b2b_launch(a, b, st, prof);
-                } else {                                   // modes 1 / 2 / 3: the two convolutions in the plan's own mode
-                    rc = conv_launch(a, st, prof, net->bf16_operands);
-                    if (!rc) rc = conv_launch(b, st, prof, net->bf16_operands);
-                }
-                break;
-            }
+            case S_CONV_B2B:
             case S_CONV_PAIR: {
-                const float *w3_img = nullptr, *w1_img = nullptr;
-                const ConvArgs a = bind_conv(net, net->plain_steps[s.pair_first], params, fold, ws, w3_img);
-                const ConvArgs b = bind_conv(net, net->plain_steps[s.pair_first + 1], params, fold, ws, w1_img);
-                rc = conv_unit_pair_launch(a, b, w3_img, w1_img, st, prof);
+                const float *wa_img = nullptr, *wb_img = nullptr;
+                const ConvArgs a = bind_conv(net, net->plain_steps[s.first], params, fold, ws, wa_img);
+                const ConvArgs b = bind_conv(net, net->plain_steps[s.first + 1], params, fold, ws, wb_img);
+                if (!s.one_launch) {                       // the two plain steps, as S_CONV above
+                    rc = conv_launch(a, st, prof, net->bf16_operands, wa_img);
+                    if (!rc) rc = conv_launch(b, st, prof, net->bf16_operands, wb_img);
+                } else if (s.kind == S_CONV_B2B) {
+                    rc = conv_b2b_launch(a, b, st, prof);
+                } else {
+                    rc = conv_unit_pair_launch(a, b, wa_img, wb_img, st, prof);
+                }
                 break;
             }
             case S_POOL:
@@ -686,121 +693,6 @@ static int run_forward(const Net* net, const float* params, const float* fold, c
 
 extern "C" {
 
-int stabnet_prof_create(void** out, int max_records) {
-    SN_REQUIRE(out && max_records > 0 && max_records <= (1 << 20), "prof_create: bad arguments");
-    Prof* p = new Prof();
-    p->cap = max_records;
-    p->ev.resize(2 * (size_t)max_records);
-    p->kind.resize(max_records); p->flops.resize(max_records); p->bytes.resize(max_records);
-    p->shape.resize(4 * (size_t)max_records);
-    for (auto& e : p->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            stabnet_set_error("prof_create: hipEventCreate failed");
-            return STABNET_ERR_LAUNCH;
-        }
-    *out = p;
-    return STABNET_OK;
-}
-void stabnet_prof_destroy(void* pp) {
-    Prof* p = static_cast<Prof*>(pp);
-    if (!p) return;
-    for (auto& e : p->ev) (void)hipEventDestroy(e);
-    delete p;
-}
-int stabnet_prof_reset(void* pp) {
-    SN_REQUIRE(pp, "prof_reset: null");
-    static_cast<Prof*>(pp)->n = 0;
-    return STABNET_OK;
-}
-/* Records one event pair with nothing between them on `stream` (kind 0): the per-pair overhead to subtract. */
-int stabnet_prof_record_empty(void* pp, void* stream) {
-    Prof* p = static_cast<Prof*>(pp);
-    SN_REQUIRE(p, "prof_record_empty: null");
-    if (p->begin((hipStream_t)stream)) p->end((hipStream_t)stream, 0, 0.0, 0.0);
-    return STABNET_OK;
-}
-int stabnet_prof_num_records(const void* pp) { return pp ? static_cast<const Prof*>(pp)->n : -1; }
-/* The stream the records were taken on must have been synchronised by the caller. */
-int stabnet_prof_record(const void* pp, int idx, int* kind, float* ms, double* flops, double* bytes) {
-    const Prof* p = static_cast<const Prof*>(pp);
-    SN_REQUIRE(p && idx >= 0 && idx < p->n && kind && ms && flops && bytes, "prof_record: bad arguments");
-    hipError_t e = hipEventElapsedTime(ms, p->ev[2 * idx], p->ev[2 * idx + 1]);
-    if (e != hipSuccess) {
-        stabnet_set_error("prof_record: %s", hipGetErrorString(e));
-        return STABNET_ERR_LAUNCH;
-    }
-    *kind = p->kind[idx]; *flops = p->flops[idx]; *bytes = p->bytes[idx];
-    return STABNET_OK;
-}
-/* GEMM view of a record: shape4 = {M, N, K, split-K}; zeros for non-GEMM kernels. */
-int stabnet_prof_record_shape(const void* pp, int idx, int* shape4) {
-    const Prof* p = static_cast<const Prof*>(pp);
-    SN_REQUIRE(p && idx >= 0 && idx < p->n && shape4, "prof_record_shape: bad arguments");
-    for (int i = 0; i < 4; ++i) shape4[i] = p->shape[4 * idx + i];
-    return STABNET_OK;
-}
-const char* stabnet_prof_kind_name(int kind) {
-    switch (kind) {
-        case PK_KERNEL_PAD: return "pad_channels_kernel";
-        case PK_KERNEL_POOL: return "max_pool_kernel";
-        case PK_KERNEL_GAP: return "gap_bn_relu_partial_kernel";
-        case PK_KERNEL_FC: return "fc_kernel";
-        case PK_KERNEL_MESH: return "mesh_homography_kernel";
-        case PK_KERNEL_HEAD: return "theta_mesh_kernel";
-        case PK_KERNEL_WARP: return "warp_sample_kernel";
-        case PK_KERNEL_ASSEMBLE: return "stack_assemble_bordered_kernel";
-        case PK_KERNEL_PUSH: return "ring_push_kernel";
-        case PK_KERNEL_SPLITK_REDUCE: return "conv_splitk_reduce_kernel";
-        case PK_KERNEL_WGRAD: return "conv_wgrad_f32_kernel";
-        case PK_KERNEL_MJPEG_TRANSFORM: return "mjpeg_transform_kernel";
-        case PK_KERNEL_MJPEG_ENTROPY: return "mjpeg_entropy_kernel";
-        case PK_KERNEL_MJPEG_LAYOUT: return "mjpeg_layout_kernel";
-        case PK_KERNEL_MJPEG_GATHER: return "mjpeg_gather_kernel";
-        case PK_KERNEL_INGEST_GREY_ROWS: return "ingest_grey_rows_kernel";
-        case PK_KERNEL_INGEST_GREY_COLS: return "ingest_grey_cols_kernel";
-        case PK_KERNEL_INGEST_COLOUR: return "ingest_colour_kernel";
-        case PK_KERNEL_MAP_SHRINK: return "map_shrink_kernel";
-        case PK_KERNEL_REMAP_SRC: return "remap_src_kernel";
-        case PK_KERNEL_REMAP_SRC4: return "remap_src4_kernel";
-        case PK_KERNEL_REMAP_WIN: return "remap_win_kernel";
-        case PK_KERNEL_REMAP_WIN4: return "remap_win4_kernel";
-        case PK_KERNEL_REMAP_WIN_DEV: return "remap_win_dev_kernel";
-        case PK_KERNEL_REMAP_WIN4_DEV: return "remap_win4_dev_kernel";
-        case PK_KERNEL_REMAP_I420: return "remap_i420_kernel";
-        case PK_KERNEL_REMAP_CUBIC + 0: return "remap_cubic_kernel<1, 0>";
-        case PK_KERNEL_REMAP_CUBIC + 1: return "remap_cubic_kernel<4, 0>";
-        case PK_KERNEL_REMAP_CUBIC + 2: return "remap_cubic_kernel<1, 1>";
-        case PK_KERNEL_REMAP_CUBIC + 3: return "remap_cubic_kernel<4, 1>";
-        case PK_KERNEL_REMAP_CUBIC + 4: return "remap_cubic_kernel<1, 2>";
-        case PK_KERNEL_REMAP_CUBIC + 5: return "remap_cubic_kernel<4, 2>";
-        case PK_KERNEL_REMAP_I420_CUBIC: return "remap_i420_kernel<true>";
-        case PK_KERNEL_MJPEGD_PLANES: return "mjpegd_planes_kernel";
-        case PK_KERNEL_MJPEG_TRANSFORM_PLANAR: return "mjpeg_transform_planar_kernel";
-        case PK_KERNEL_TF_GET_IMG: return "tf_get_img_kernel";
-        case PK_KERNEL_TVL1_STEP: return "tvl1_step_kernel";
-        case PK_KERNEL_TVL1_FUSED: return "tvl1_fused_kernel";
-        case PK_KERNEL_TVL1_DOWN: return "tvl1_down_kernel";
-        case PK_KERNEL_TVL1_GRAD: return "tvl1_grad_kernel";
-        case PK_KERNEL_TVL1_WARP: return "tvl1_warp_kernel";
-        case PK_KERNEL_TVL1_UP: return "tvl1_up_kernel";
-        case PK_KERNEL_TVL1_MAP: return "tvl1_map_kernel";
-        case PK_KERNEL_KLT_DETECT: return "klt_detect_kernel";
-        case PK_KERNEL_KLT_TRACK: return "klt_track_kernel";
-        case PK_KERNEL_KLT_FINISH: return "klt_finish_kernel";
-        case PK_KERNEL_HOMFIT: return "homfit_kernel";
-        default: break;
-    }
-    if (kind >= PK_KERNEL_WGRAD_SAME && kind < PK_KERNEL_WGRAD_SAME + 6) {      // names as rocprofv3 prints them: <K3, PRO, BIAS>
-        static const char* const names[6] = {"conv_wgrad_same_f32_kernel<0, 0, 0>", "conv_wgrad_same_f32_kernel<0, 1, 0>",
-                                             "conv_wgrad_same_f32_kernel<1, 0, 0>", "conv_wgrad_same_f32_kernel<1, 1, 0>",
-                                             "conv_wgrad_same_f32_kernel<0, 0, 1>", "conv_wgrad_same_f32_kernel<0, 1, 1>"};
-        return names[kind - PK_KERNEL_WGRAD_SAME];
-    }
-    const char* conv = conv_prof_kind_name(kind);              // the PK_KERNEL_CONV_* kinds: named where they are numbered (conv.hip)
-    if (conv != nullptr) return conv;
-    return "?";
-}
-
 int stabnet_net_create(void** out, int N, int H, int W, int in_ch, int n_theta, int keep_activations) {
     SN_REQUIRE(out != nullptr, "net_create: null out");
     SN_REQUIRE(N > 0 && N <= 4096 && H >= 32 && W >= 32 && in_ch > 0 && in_ch <= 64 && n_theta > 0,
@@ -825,64 +717,65 @@ int stabnet_net_set_bf16_operands(void* netp, int on) {
         return STABNET_OK;
     }
     net->bf16_operands = (on >= 1 && on <= 4) ? on : 0;     // 1: bf16 operands; 2 / 3: split operands (conv_kernel.h sn_split3)
-    if (!net->plain_steps.empty()) {                        // fused unit pairs belong to the mode they were asked in: back to the plan as built
-        net->steps = net->plain_steps;
-        net->plain_steps.clear();
-    }
+    net->unit_pairs = 0;                                    // fused unit pairs belong to the mode they were asked in
+    rebuild_steps(net);
     return STABNET_OK;
 }
 
-/* conv3 -> next unit's conv1 as one launch (include/stabnet_hip.h) */
+// Steps i, i + 1 of the plain plan as ONE S_CONV_PAIR step (operand mode 4, when asked: include/stabnet_hip.h): conv3 of a unit whose
+// successor is an identity unit (no consumer BN), conv1 the very next step reading exactly its output through the prologue, and the
+// launcher's own routes of the two (bound to placeholders) the ones the fused kernel repeats (conv_unit_pair_form).
 static bool ranges_meet(long a, size_t an, long b, size_t bn) { return a < b + (long)bn && b < a + (long)an; }
-int stabnet_net_fuse_unit_pairs(void* netp, int on) {
-    Net* net = static_cast<Net*>(netp);
-    SN_REQUIRE(net != nullptr, "fuse_unit_pairs: null net");
-    if (!net->plain_steps.empty()) {                        // from the plan as built, whatever was asked before
-        net->steps = net->plain_steps;
-        net->plain_steps.clear();
-    }
-    if (!on || net->keep_all || net->bf16_operands != 4) return STABNET_OK;
+static bool unit_pair_takes(const Net* net, size_t i) {
     // Smallest M: REASONED as the patch kernel's is, not measured -- 12288 rows are 192 tiles of 64 rows / 384 of 32, from where on the one
     // workgroup per M tile fills most of the chip's resident slots; it also leaves the 288 x 512 frame (M = 9216) and every recorded
     // small-shape route alone.  STABNET_CONV_PAIR_MIN_M lowers it for tests.
     static const int min_m = []() { const char* v = getenv("STABNET_CONV_PAIR_MIN_M"); return v ? atoi(v) : 12288; }();
-    const float* fold0 = reinterpret_cast<const float*>((size_t)2 << 40);      // placeholder bases (stabnet_net_step_info): never dereferenced
-    std::vector<Step> fused;
-    const std::vector<Step>& st = net->steps;
-    for (size_t i = 0; i < st.size(); ++i) {
-        bool take = false;
-        if (i + 1 < st.size() && st[i].kind == S_CONV && st[i + 1].kind == S_CONV) {
-            const Step &c3 = st[i], &c1 = st[i + 1];
-            const float *w3_img = nullptr, *w1_img = nullptr;
-            const ConvArgs a = bind_conv(net, c3, reinterpret_cast<const float*>((size_t)1 << 40), fold0, reinterpret_cast<float*>((size_t)3 << 40), w3_img);
-            const ConvArgs b = bind_conv(net, c1, reinterpret_cast<const float*>((size_t)1 << 40), fold0, reinterpret_cast<float*>((size_t)3 << 40), w1_img);
-            ConvUnitPairForm f;
-            // conv3 of a unit whose successor is an identity unit (no consumer BN), conv1 the very next step reading exactly its output
-            // through the prologue; conv1's output may share memory with nothing the other workgroups of the launch still read -- conv3's
-            // input and residual -- except as the same rows in place (same first float, same row pitch: a workgroup holds its rows of
-            // the input in LDS before it writes them)
-            const long o1 = c1.out_off;
-            const size_t n1 = (size_t)b.M * b.Cout;
-            const bool in_place = o1 == c3.in_off && c3.in_base == c3.in_off && a.x_ld == b.Cout && c3.in_floats == n1;
-            take = c3.obn_off < 0 && c3.res_off >= 0 && c1.in_off == c3.out_off && c1.in_base == c3.out_off && a.M >= min_m &&
-                   conv_unit_pair_form(a, b, w3_img != nullptr, w1_img != nullptr, true, f) &&
-                   (in_place || !ranges_meet(o1, n1, c3.in_base, c3.in_floats)) && !ranges_meet(o1, n1, c3.res_off, c3.res_floats) &&
-                   !ranges_meet(o1, n1, c3.out_off, (size_t)a.M * a.Cout);
+    const std::vector<Step>& p = net->plain_steps;
+    if (i + 1 >= p.size() || p[i].kind != S_CONV || p[i + 1].kind != S_CONV) return false;
+    const Step &c3 = p[i], &c1 = p[i + 1];
+    const float *w3_img = nullptr, *w1_img = nullptr;
+    const ConvArgs a = bind_conv_placeholders(net, c3, w3_img), b = bind_conv_placeholders(net, c1, w1_img);
+    ConvUnitPairForm f;
+    // conv1's output may share memory with nothing the other workgroups of the launch still read -- conv3's input and residual -- except
+    // as the same rows in place (same first float, same row pitch: a workgroup holds its rows of the input in LDS before it writes them)
+    const long o1 = c1.out_off;
+    const size_t n1 = (size_t)b.M * b.Cout;
+    const bool in_place = o1 == c3.in_off && c3.in_base == c3.in_off && a.x_ld == b.Cout && c3.in_floats == n1;
+    return c3.obn_off < 0 && c3.res_off >= 0 && c1.in_off == c3.out_off && c1.in_base == c3.out_off && a.M >= min_m &&
+           conv_unit_pair_form(a, b, w3_img != nullptr, w1_img != nullptr, f) &&
+           (in_place || !ranges_meet(o1, n1, c3.in_base, c3.in_floats)) && !ranges_meet(o1, n1, c3.res_off, c3.res_floats) &&
+           !ranges_meet(o1, n1, c3.out_off, (size_t)a.M * a.Cout);
+}
+
+// Net::steps from the plain plan, the B2B switches, the pair request and the operand mode.  B2B first: a pair is formed only from two
+// steps B2B left as S_CONV.  The exact-f32 B2B kernel runs in operand modes 0 and 4 (mode 4 runs the exact-f32 kernels wherever no
+// packed kernel takes a launch); in modes 1 / 2 / 3 the step keeps its place and runs its two convolutions in the plan's own mode.
+static void rebuild_steps(Net* net) {
+    const std::vector<Step>& p = net->plain_steps;
+    const bool pairs = net->unit_pairs && !net->keep_all && net->bf16_operands == 4;
+    net->steps.clear();
+    for (size_t i = 0; i < p.size(); ++i) {
+        const bool b2b = b2b_takes(net, i);
+        if (!b2b && !(pairs && !b2b_takes(net, i + 1) && unit_pair_takes(net, i))) {
+            net->steps.push_back(p[i]);
+            continue;
         }
-        if (take) {
-            Step p = st[i];
-            p.kind = S_CONV_PAIR;
-            p.pair_first = (int)i;
-            fused.push_back(p);
-            ++i;
-        } else {
-            fused.push_back(st[i]);
-        }
+        Step f{};
+        f.kind = b2b ? S_CONV_B2B : S_CONV_PAIR;
+        f.first = (int)i;
+        f.one_launch = (!b2b || net->bf16_operands == 0 || net->bf16_operands == 4) ? 1 : 0;
+        net->steps.push_back(f);
+        ++i;
     }
-    if (fused.size() != st.size()) {
-        net->plain_steps = net->steps;
-        net->steps = fused;
-    }
+}
+
+/* conv3 -> next unit's conv1 as one launch (include/stabnet_hip.h): a request the mode-4 inference plan keeps until its mode is set again */
+int stabnet_net_fuse_unit_pairs(void* netp, int on) {
+    Net* net = static_cast<Net*>(netp);
+    SN_REQUIRE(net != nullptr, "fuse_unit_pairs: null net");
+    net->unit_pairs = (on && !net->keep_all && net->bf16_operands == 4) ? 1 : 0;
+    rebuild_steps(net);
     return STABNET_OK;
 }
 
@@ -919,13 +812,7 @@ int stabnet_net_num_launches(const void* netp) {
     if (!net) return -1;
     int n = 0;
     // (shortened head: GAP partials + fc_1 = 2 launches, fc_2, fc_3, output layer [+ mesh] = 3; else 2 + 4 x fc_launches)
-    for (const Step& s : net->steps) {
-        const int mode = net->bf16_operands;       // (mode 4 without a weight image: conv_launch runs the exact-f32 kernels)
-        if (s.kind == S_CONV_B2B) n += b2b_fused(net) ? 1 : 2 + conv_reduce_launches(s.conv, mode) + conv_reduce_launches(s.conv_b, mode);
-        else if (s.kind == S_CONV_PAIR) n += 1;
-        else n += (s.kind == S_CONV) ? 1 + conv_reduce_launches(s.conv, (mode == 4 && s.wimg_off < 0) ? 0 : mode)
-                                     : (s.kind == S_FC ? fc_launches(s.M) : (s.kind == S_GAP ? 2 : 1));
-    }
+    for (const Step& s : net->steps) n += step_launches(net, s);
     if (head_fused_supported(net->N, net->t_last.C, net->fc_dims)) n -= 1 /* gap_finalize */ + (fc_launches(net->N) - 1) * 2;
     return n;
 }
@@ -974,7 +861,7 @@ int stabnet_net_fold_bn(const void* netp, const float* params, float* fold, floa
     // `fold` has no image region): from the weights each launch reads
     if (net->keep_all) return STABNET_OK;
     float* img = fold + 2 * net->G + net->stem_w_floats + net->merge_floats;
-    for (const Step& s : net->built_steps()) {              // (a fused pair reads the images of its two convolutions)
+    for (const Step& s : net->plain_steps) {                // (a fused pair reads the images of its two convolutions)
         if (s.kind != S_CONV || s.wimg_off < 0) continue;
         SN_REQUIRE((size_t)s.wimg_off + conv_weight_image_floats(s.conv.Cout, s.conv.K) <= net->wimg_floats, "fold_bn: weight image outside the fold buffer");
         const float* w = s.conv.rowrun ? fold + 2 * net->G : params + s.w_off;
@@ -1011,7 +898,7 @@ int stabnet_net_num_steps(const void* netp) { return netp ? (int)static_cast<con
 int stabnet_net_step_info_fields(void) { return STABNET_SI_FIELDS; }
 
 /* What plan step `step` of an inference plan is and, for a convolution, everything its launch is made of (include/stabnet_hip.h).
- * Host only: the step is bound to placeholder bases (conv_route() and conv_grid() look at no memory) and asked for the route and
+ * Host only: the step is bound to the placeholder bases (conv_route() and conv_grid() look at no memory) and asked for the route and
  * the grid the launcher would take on a chip of `cus` CUs. */
 int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int cap) {
     const Net* net = static_cast<const Net*>(netp);
@@ -1019,19 +906,15 @@ int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int c
     SN_REQUIRE(!net->keep_all, "step_info: inference plans only (keep_activations = 0)");
     SN_REQUIRE(step >= 0 && step < (int)net->steps.size(), "step_info: step %d outside the plan's %d steps", step, (int)net->steps.size());
     SN_REQUIRE(cus > 0 && cap >= STABNET_SI_FIELDS, "step_info: cus %d must be positive and info hold %d fields (cap %d)", cus, STABNET_SI_FIELDS, cap);
-    const Step& s = net->steps[step];
     for (int i = 0; i < STABNET_SI_FIELDS; ++i) info[i] = 0;
-    info[STABNET_SI_KIND] = s.kind;
+    info[STABNET_SI_KIND] = net->steps[step].kind;
     // S_CONV_PAIR: the fields describe the conv3 half (routed as its own launch would be); PROF_KIND, the grid and the LDS fields are the fused launch's
-    const bool pair = s.kind == S_CONV_PAIR;
-    if (s.kind != S_CONV && !pair) return STABNET_OK;
-    // placeholder bases, far enough apart that no two bound pointers meet; never dereferenced
-    const float* params = reinterpret_cast<const float*>((size_t)1 << 40);
-    const float* fold = reinterpret_cast<const float*>((size_t)2 << 40);
-    float* ws = reinterpret_cast<float*>((size_t)3 << 40);
+    const bool pair = net->steps[step].kind == S_CONV_PAIR;
+    if (net->steps[step].kind != S_CONV && !pair) return STABNET_OK;
+    const Step& s = pair ? net->plain_steps[net->steps[step].first] : net->steps[step];
     const float* w_img = nullptr;
-    const ConvArgs a = bind_conv(net, s, params, fold, ws, w_img);
-    const ConvRoute r = conv_route(a, net->bf16_operands, w_img != nullptr, true);
+    const ConvArgs a = bind_conv_placeholders(net, s, w_img);
+    const ConvRoute r = conv_route(a, net->bf16_operands, w_img != nullptr);
     const ConvGrid g = conv_grid(r, a, cus);
     info[STABNET_SI_N] = a.N; info[STABNET_SI_H] = a.H; info[STABNET_SI_W] = a.W; info[STABNET_SI_CIN] = a.Cin;
     info[STABNET_SI_HO] = a.Ho; info[STABNET_SI_WO] = a.Wo; info[STABNET_SI_COUT] = a.Cout;
@@ -1050,7 +933,7 @@ int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int c
     info[STABNET_SI_OUT_BN_OFF] = s.obn_off >= 0 ? s.obn_off : -1;
     info[STABNET_SI_MERGED_OFF] = s.fvec_off >= 0 ? (long)(2 * net->G + net->stem_w_floats) + s.fvec_off : -1;
     info[STABNET_SI_W_ROWRUN_OFF] = a.rowrun ? (long)(2 * net->G) : -1;
-    info[STABNET_SI_W_IMAGE_OFF] = w_img ? (long)(w_img - fold) : -1;
+    info[STABNET_SI_W_IMAGE_OFF] = w_img ? (long)(w_img - PH_FOLD) : -1;
     info[STABNET_SI_INF_PREACTIVATED] = s.inf_preactivated; info[STABNET_SI_PROLOGUE] = a.in_scale ? 1 : 0;
     info[STABNET_SI_SPLITK] = a.splitk; info[STABNET_SI_STEPS_PER_SPLIT] = a.steps_per_split; info[STABNET_SI_TOTAL_STEPS] = conv_plan_total_steps(a);
     info[STABNET_SI_FAMILY] = r.family; info[STABNET_SI_MODE] = r.mode; info[STABNET_SI_OPERAND] = r.operand; info[STABNET_SI_KG] = r.kg;
@@ -1064,9 +947,9 @@ int stabnet_net_step_info(const void* netp, int step, int cus, long* info, int c
     info[STABNET_SI_LDS_LIMIT] = r.family == CONV_ASTAT ? (long)conv_astat_plane_limit() : r.family == CONV_PATCH ? (long)conv_patch_lds_limit() : 0;
     if (pair) {
         const float* w1_img = nullptr;
-        const ConvArgs b = bind_conv(net, net->plain_steps[s.pair_first + 1], params, fold, ws, w1_img);
+        const ConvArgs b = bind_conv_placeholders(net, net->plain_steps[net->steps[step].first + 1], w1_img);
         ConvUnitPairForm f;
-        SN_REQUIRE(conv_unit_pair_form(a, b, w_img != nullptr, w1_img != nullptr, true, f), "step_info: step %d is no pair the fused kernel takes", step);
+        SN_REQUIRE(conv_unit_pair_form(a, b, w_img != nullptr, w1_img != nullptr, f), "step_info: step %d is no pair the fused kernel takes", step);
         const ConvGrid pg = conv_unit_pair_grid(f, a);
         info[STABNET_SI_PROF_KIND] = f.prof_kind;
         info[STABNET_SI_TILES] = pg.tiles; info[STABNET_SI_WGS] = pg.wgs; info[STABNET_SI_GX] = pg.gx; info[STABNET_SI_GY] = pg.gy; info[STABNET_SI_GZ] = pg.gz;
@@ -1231,8 +1114,9 @@ static size_t unit_slab_floats(const UnitInfo& u, int T) {
     if (u.proj) n += wgrad_slab_floats(u.depth, u.cin, u.x.N * u.x.H * u.x.W, T);
     return n;
 }
+static const int kBlockFirstUnit[5] = {0, 3, 7, 13, 16};     // first unit of block 1..4, and the end (resnet_v2_50: 3, 4, 6, 3 units)
 static size_t net_slab_floats(const Net* net, int T, int s0, int s1) {
-    const int first[5] = {0, 3, 7, 13, 16};               // units of block 1..4 (resnet_v2_50: 3, 4, 6, 3)
+    const int* first = kBlockFirstUnit;
     size_t n = 0;
     for (int sg = s0; sg < s1; ++sg) {
         const int blk = 3 - sg;
@@ -1407,10 +1291,8 @@ static int run_forward_train(const Net* net, float* params, int T, const float* 
 // ends with the ordered reduction of its wgrad slabs, so its gradients are final when the stage's kernels are done.
 static const int kNumStages = 4;
 static void stage_units(const Net* net, int stage, int& u_hi, int& u_lo) {      // units [u_lo, u_hi] processed descending
-    // blocks of resnet_v2_50: 3, 4, 6, 3 units
-    const int first[5] = {0, 3, 7, 13, 16};
     const int blk = 3 - stage;
-    u_lo = first[blk]; u_hi = first[blk + 1] - 1;
+    u_lo = kBlockFirstUnit[blk]; u_hi = kBlockFirstUnit[blk + 1] - 1;
     (void)net;
 }
 

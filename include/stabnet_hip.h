@@ -215,7 +215,8 @@ int stabnet_backbone_fwd_infer(const void* net, const float* params, const float
 /* ---- inference plans, one step at a time (keep_activations = 0 only) -------------------------------------------
  * A plan is a list of steps: 0 pad / embed the input, 1 convolution, 2 max-pool, 3 global pool, 4 fully connected, 5 conv2 -> conv3
  * as one launch (STABNET_CONV_B2B_PLAN=1 plans), 6 conv3 -> the next unit's conv1 as one launch (stabnet_net_fuse_unit_pairs; the fields
- * describe the conv3 half as its own launch would be routed, PROF_KIND / TILES .. GZ / LDS_* the fused launch).
+ * describe the conv3 half as its own launch would be routed, PROF_KIND / TILES .. GZ / LDS_* the fused launch).  Kinds 5 and 6 each stand
+ * for two consecutive convolution steps of the plan as built, which is made of kinds 0 - 4 only.
  * stabnet_net_step_info() says what a step is and, for a convolution (kind 1),
  * everything its launch is made of, as the forward would bind and route it in the plan's operand mode (stabnet_net_set_bf16_operands)
  * on a chip of `cus` CUs.  HOST ONLY: no GPU is needed and the device is not read -- `cus` is the caller's (an MI355X has 256).

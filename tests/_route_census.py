@@ -286,7 +286,7 @@ def census(check=True):
             info = p.infos()
             sel = np.flatnonzero(info[:, c_kind] == S_CONV)
             if check:
-                # the plan-time launch count (what a captured frame is sized by) is the launches the BOUND routes make: every conv and
+                # the plan's launch count (what a captured frame is sized by) is the launches the BOUND routes make: every conv and
                 # its reduce launch + pad, pool, pooled partials, fc_1, fc_2, fc_3 and the output layer (the fused head, batch <= 8)
                 n_conv = int(len(sel) + info[sel, col("reduce")].sum())
                 assert _lib().stabnet_net_num_launches(p.h) == n_conv + 7, (mode, N, H, W, _lib().stabnet_net_num_launches(p.h), n_conv)

@@ -7,13 +7,15 @@ stabnet_net_set_bf16_operands).  The plan switches are read once per process, so
   b. kernel class: every conv record of the Profiler names an instantiation of the mode (BF16 template argument = the mode;
      mode 4 also runs the exact-f32 kernels wherever no packed kernel takes a launch);
   c. launch accounting: the records of one forward / one deploy step equal stabnet_net_num_launches /
-     stabnet_deploy_frame_launches (conv_route()'s plan-time view of the launcher's routing);
+     stabnet_deploy_frame_launches (counted from the routes the launcher takes: the steps bound to placeholders);
   d. the same bits every time;
   e. guard bands: `fold` and the workspace carry 64 KiB canary tails beyond their queried sizes, `fold` is NaN before
      stabnet_net_fold_bn and the workspace NaN before every forward -- theta stays finite and within (a);
   f. the same kernels: the ordered Profiler names of the forward at both shapes and of the deploy step equal
      tests/golden/conv_routes.json, recorded (twice, with equal results) with this child before conv_route() became the single routing
-     decision of conv.hip.  A change that moves a launch to another kernel has to say so by recording the fixture again."""
+     decision of conv.hip.  A change that moves a launch to another kernel has to say so by recording the fixture again.
+One more comparison across routes: in mode 1 the B2B plan runs its fused steps as their two plain convolutions, through the code of any
+conv step -- the launches and arguments of the default plan, so theta and the Profiler names are the default plan's, `==`."""
 import functools
 import json
 import os
@@ -210,3 +212,17 @@ def test_mode1_is_off_the_f32_bar(cuda, tmp_path_factory, switches):
     errs = _errors(_child(1, switches, str(tmp_path_factory.getbasetemp())))
     print("mode 1 %s: theta max error vs float64 %s (f32 bar %g)" % (switches, ["%.3e" % e for e in errs], F32_BAR))
     assert min(errs) >= 5 * F32_BAR, errs
+
+
+def test_mode1_b2b_plan_is_the_default_plan(cuda, tmp_path_factory):
+    """STABNET_CONV_B2B_PLAN=1 (MIN_TILES=1: all seven units of blocks 1 and 2) in operand mode 1: every fused step runs as conv2 then conv3,
+    the same launches with the same arguments as the default plan makes -- equal theta bits and equal Profiler name lists, forward (both
+    shapes) and deploy step."""
+    tmp = str(tmp_path_factory.getbasetemp())
+    b2b, plain = _child(1, "b2b", tmp), _child(1, "default", tmp)
+    for si, shape in enumerate(SHAPES):
+        assert np.array_equal(b2b["x_%d" % si], plain["x_%d" % si])
+        assert np.array_equal(b2b["theta_%d" % si], plain["theta_%d" % si]), shape
+        assert [str(n) for n in b2b["names_%d" % si]] == [str(n) for n in plain["names_%d" % si]], shape
+        assert int(b2b["launches_%d" % si]) == int(plain["launches_%d" % si])
+    assert [str(n) for n in b2b["deploy_names"]] == [str(n) for n in plain["deploy_names"]]

@@ -49,6 +49,28 @@ def test_regressor_taps_and_theta(cuda, N, H, W):
     assert (theta - theta2).abs().max().item() <= 2e-6
 
 
+def test_keep_activations_plan_counts_its_launches(cuda):
+    """stabnet_net_num_launches of a keep_activations plan is what stabnet_backbone_fwd_infer launches on it (one Profiler record per
+    launch; the GAP step's record covers two).  conv2 / conv3 of such a plan are planned as prologue convolutions and run without one
+    (the producer's epilogue activates their input): the count follows the routes the launcher takes, not the plan-time hint."""
+    from stabnet_amd import _lib
+    from stabnet_amd._tensor import ptr, stream_ptr
+    from stabnet_amd.deploy import Profiler
+    from stabnet_amd.regressor import Regressor
+    N, H, W = 1, 288, 512
+    cfg, ocfg, P, x = _setup(N, H, W)
+    reg = Regressor(P, N, H, W, cfg, keep_activations=True)
+    prof = Profiler(max_records=512, device=cuda)
+    prof.reset()
+    xt = torch.from_numpy(x).to(cuda)
+    theta = torch.empty((N, cfg.n_theta), dtype=torch.float32, device=cuda)
+    _lib.call("stabnet_backbone_fwd_infer", reg.plan.handle, ptr(reg.params), ptr(reg.fold), ptr(xt), ptr(theta), ptr(reg.workspace),
+              reg.workspace.numel(), stream_ptr(cuda), prof.handle, device=cuda)
+    torch.cuda.synchronize()
+    names = [r[0] for r in prof.records(raw=True)]
+    assert len(names) + names.count("gap_bn_relu_partial_kernel") == reg.plan.num_launches, names
+
+
 def test_full_frame_matches_oracle(cuda):
     """x_tensor -> (output_img, black_pix, Hs, x_map, y_map): the fetch list of deploy_bundle.py:286."""
     from stabnet_amd.regressor import Regressor
