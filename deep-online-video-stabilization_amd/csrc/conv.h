@@ -54,6 +54,17 @@ struct Prof;
 int conv_launch(const ConvArgs& a, hipStream_t st, Prof* prof = nullptr, int bf16_operands = 0, const float* w_img = nullptr,
                 bool lowk_ring = false);
 
+// The range every conv launch is held to ("Conv extents"): the kernels reach their operands through 32-bit offsets from the
+// operand's pointer -- BYTE offsets in the ring and back-to-back kernels (input, OHWI weights, the back-to-back residual), element
+// offsets built from `int` products elsewhere -- so an operand's whole extent, ALL x_ld / res_ld columns of every pixel, stays below
+// 2^30 floats.  One limit for every family: which kernel a launch runs depends on the operand mode and the fusions, its buffers do not.
+constexpr long SN_CONV_EXTENT_LIMIT = 1L << 30;
+// The first operand of the planned launch `a` (conv_plan() called, x_ld / res_ld final) that reaches the limit -- "input", "output",
+// "residual" or "weights", null when all are inside; *floats = its extent.  in_floats: floats from a.x to the end of the buffer the
+// input lives in (<= 0: the dense [N][H][W][x_ld] tensor; the plan passes its own, the row-run stem's bordered image too); has_residual: the
+// launch reads one ([N][res_H][res_W][res_ld]).  Host only.
+const char* conv_extent_over(const ConvArgs& a, long in_floats, bool has_residual, long* floats);
+
 // Which kernel a convolution runs: decided ONCE, by conv_route(), for the launcher (conv_launch), for the plan's launch count and step
 // info (net.hip) and for the Profiler's kernel name alike.
 enum ConvFamily {

@@ -989,6 +989,31 @@ int conv_unit_pair_launch(const ConvArgs& c3, const ConvArgs& c1, const float* w
 }
 
 // ---------------------------------------------------------------------------------------------------------
+const char* conv_extent_over(const ConvArgs& a, long in_floats, bool has_residual, long* floats) {
+    const long pixels = (long)a.N * a.H * a.W;
+    const long in = in_floats > 0 ? in_floats : pixels * (a.x_ld ? a.x_ld : a.Cin);
+    const long out = (long)a.N * a.Ho * a.Wo * a.Cout;
+    const long res = has_residual ? (long)a.N * a.res_H * a.res_W * (a.res_ld ? a.res_ld : a.Cout) : 0;
+    const long w = (long)a.Cout * (a.K ? a.K : a.KH * a.KW * a.Cin);
+    const struct { const char* name; long n; } ops[4] = {{"input", in}, {"output", out}, {"residual", res}, {"weights", w}};
+    for (const auto& o : ops)
+        if (o.n >= SN_CONV_EXTENT_LIMIT) {
+            if (floats) *floats = o.n;
+            return o.name;
+        }
+    return nullptr;
+}
+// The operator entries' form of it: the input counted over the zero-padded frame, as fill_args() has always counted it (with Cin),
+// now with every x_ld column.  Call with x_ld / res_ld set and conv_plan() done.
+static int check_extents(const ConvArgs& a, const char* who) {
+    long n = 0;
+    const long in = (long)a.N * (a.H + 2 * a.pad) * (a.W + 2 * a.pad) * (a.x_ld ? a.x_ld : a.Cin);
+    const char* op = conv_extent_over(a, in, a.residual != nullptr, &n);
+    SN_REQUIRE(op == nullptr, "%s: the %s spans %ld floats (x_ld=%d, res_ld=%d): every conv operand must stay below 2^30 floats, all x_ld / res_ld columns counted",
+               who, op, n, a.x_ld, a.res_ld);
+    return STABNET_OK;
+}
+
 static int fill_args(ConvArgs& a, const float* x, const float* w, const float* bias, const float* in_scale,
                      const float* in_shift, const float* residual, int res_H, int res_W, int res_stride, float* y,
                      int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu_out) {
@@ -1010,6 +1035,11 @@ static int fill_args(ConvArgs& a, const float* x, const float* w, const float* b
     a.relu_out = relu_out;
     SN_REQUIRE((long)N * a.Ho * a.Wo * Cout < (1L << 30) && (long)N * (H + 2 * pad) * (W + 2 * pad) * Cin < (1L << 30) &&
                    (long)Cout * KH * KW * Cin < (1L << 30), "conv2d: tensors must have < 2^30 elements");
+    // the residual's frame as the caller states it, with or without a pointer: a strided one ([N][res_H][res_W][Cout], read at
+    // (oy*res_stride, ox*res_stride)) is larger than the output
+    const long res_floats = (long)N * (res_H > 0 ? res_H : a.Ho) * (res_W > 0 ? res_W : a.Wo) * Cout;
+    SN_REQUIRE(res_floats < SN_CONV_EXTENT_LIMIT, "conv2d: the residual spans %ld floats (res_H=%d, res_W=%d): every conv operand must stay below 2^30 floats",
+               res_floats, res_H, res_W);
     SN_REQUIRE(KH * KW <= 64, "conv2d: filter larger than 64 taps");
     return STABNET_OK;
 }
@@ -1161,8 +1191,7 @@ int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, 
                                  const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
                                  int Cout, int KH, int KW, int stride, int pad, int relu_out, int splitk, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-    SN_REQUIRE(x && w_ohwi && w_img && y, "conv2d_fwd_packed: null pointer");
-    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv2d_fwd_packed: out_scale and out_shift go together");
+    // (the shape is judged before the pointers: a geometry outside the kernels' range is refused whatever it comes with)
     SN_REQUIRE(x_ld == 0 || (x_ld >= Cin && x_ld % 4 == 0), "conv2d_fwd_packed: x_ld=%d must be 0 or a multiple of 4 >= Cin=%d", x_ld, Cin);
     ConvArgs a;
     int rc = fill_args(a, x, w_ohwi, bias, in_scale, in_shift, residual, res_H, res_W, res_stride, y, N, H, W, Cin, Cout,
@@ -1170,6 +1199,9 @@ int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, 
     if (rc) return rc;
     a.x_ld = x_ld;
     const size_t need = plan_packed(a, splitk);
+    if ((rc = check_extents(a, "conv2d_fwd_packed")) != 0) return rc;
+    SN_REQUIRE(x && w_ohwi && w_img && y, "conv2d_fwd_packed: null pointer");
+    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv2d_fwd_packed: out_scale and out_shift go together");
     if (need > workspace_bytes || (need > 0 && workspace == nullptr)) {
         stabnet_set_error("conv2d_fwd_packed: workspace %zu B < %zu B needed", workspace_bytes, need);
         return STABNET_ERR_WORKSPACE;
@@ -1184,8 +1216,7 @@ int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, 
 int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float* w3_img, const float* bias3, const float* residual, int res_ld,
                                const float* pre_scale, const float* pre_shift, const float* w1_ohwi, const float* w1_img, const float* out_scale,
                                const float* out_shift, float* y3, float* y1, int N, int H, int W, int K1, int N1, int N2, int relu_out, void* stream) {
-    SN_REQUIRE(x && w3_ohwi && pre_scale && pre_shift && w1_ohwi && w1_img && y3 && y1, "conv_unit_pair_fwd: null pointer");
-    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv_unit_pair_fwd: out_scale and out_shift go together");
+    // (the shapes are judged before the pointers; res_ld counts whether or not this call reads a residual)
     SN_REQUIRE(res_ld == 0 || (res_ld >= N1 && res_ld % 4 == 0), "conv_unit_pair_fwd: res_ld=%d must be 0 or a multiple of 4 >= N1=%d", res_ld, N1);
     ConvArgs c3, c1;
     int rc = fill_args(c3, x, w3_ohwi, bias3, nullptr, nullptr, residual, H, W, 1, y3, N, H, W, K1, N1, 1, 1, 1, 0, 0);
@@ -1195,6 +1226,13 @@ int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float
     rc = fill_args(c1, y3, w1_ohwi, nullptr, pre_scale, pre_shift, nullptr, 0, 0, 1, y1, N, H, W, N1, N2, 1, 1, 1, 0, relu_out);
     if (rc) return rc;
     (void)plan_packed(c1, 1);
+    long ext = 0;
+    const char* over = conv_extent_over(c3, 0, true, &ext);
+    SN_REQUIRE(over == nullptr, "conv_unit_pair_fwd: conv3's %s spans %ld floats (res_ld=%d): every conv operand must stay below 2^30 floats, all res_ld columns counted",
+               over, ext, c3.res_ld);
+    if ((rc = check_extents(c1, "conv_unit_pair_fwd (conv1)")) != 0) return rc;
+    SN_REQUIRE(x && w3_ohwi && pre_scale && pre_shift && w1_ohwi && w1_img && y3 && y1, "conv_unit_pair_fwd: null pointer");
+    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv_unit_pair_fwd: out_scale and out_shift go together");
     c1.out_scale = out_scale;
     c1.out_shift = out_shift;
     return conv_unit_pair_launch(c3, c1, w3_img, w1_img, (hipStream_t)stream);
@@ -1209,13 +1247,15 @@ int stabnet_conv3x3_conv1x1_fwd(const float* x, int x_ld, const float* w2_ohwi, 
                                 const float* w3_ohwi, const float* bias3, const float* residual, int res_H, int res_W,
                                 int res_stride, int res_ld, const float* out_scale, const float* out_shift, float* y, int N, int H,
                                 int W, int C, int Cout, int stride, int relu_out, void* stream) {
-    SN_REQUIRE(x && w2_ohwi && mid_scale && mid_shift && w3_ohwi && y, "conv3x3_conv1x1_fwd: null pointer");
-    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv3x3_conv1x1_fwd: out_scale and out_shift go together");
+    // (the shapes are judged before the pointers; res_ld counts whether or not this call reads a residual)
+    SN_REQUIRE(x_ld == 0 || (x_ld >= C && x_ld % 4 == 0), "conv3x3_conv1x1_fwd: x_ld=%d must be 0 or a multiple of 4 >= C=%d", x_ld, C);
+    SN_REQUIRE(res_ld == 0 || (res_ld >= Cout && res_ld % 4 == 0), "conv3x3_conv1x1_fwd: res_ld=%d must be 0 or a multiple of 4 >= Cout=%d", res_ld, Cout);
     ConvArgs c2, c3;
     int rc = fill_args(c2, x, w2_ohwi, nullptr, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, N, H, W, C, C, 3, 3, stride, 1, 1);
     if (rc) return rc;
     c2.x_ld = x_ld;
     (void)conv_plan(c2);
+    if ((rc = check_extents(c2, "conv3x3_conv1x1_fwd (conv2)")) != 0) return rc;
     c2.out_scale = mid_scale;
     c2.out_shift = mid_shift;
     rc = fill_args(c3, nullptr, w3_ohwi, bias3, nullptr, nullptr, residual, res_H, res_W, res_stride, y, N, c2.Ho, c2.Wo, C, Cout,
@@ -1223,6 +1263,16 @@ int stabnet_conv3x3_conv1x1_fwd(const float* x, int x_ld, const float* w2_ohwi, 
     if (rc) return rc;
     c3.res_ld = res_ld;
     (void)conv_plan(c3);
+    {
+        long ext = 0;
+        ConvArgs t = c3;                                   // (the residual's frame as the caller states it, with or without a pointer)
+        if (res_H > 0 && res_W > 0) { t.res_H = res_H; t.res_W = res_W; }
+        const char* over = conv_extent_over(t, 0, true, &ext);
+        SN_REQUIRE(over == nullptr, "conv3x3_conv1x1_fwd: conv3's %s spans %ld floats (res_ld=%d): every conv operand must stay below 2^30 floats, all res_ld columns counted",
+                   over, ext, c3.res_ld);
+    }
+    SN_REQUIRE(x && w2_ohwi && mid_scale && mid_shift && w3_ohwi && y, "conv3x3_conv1x1_fwd: null pointer");
+    SN_REQUIRE((out_scale == nullptr) == (out_shift == nullptr), "conv3x3_conv1x1_fwd: out_scale and out_shift go together");
     c3.out_scale = out_scale;
     c3.out_shift = out_shift;
     SN_REQUIRE(conv_b2b_supported(c2, c3), "conv3x3_conv1x1_fwd: C must be 64 or 128, Cout a multiple of C, stride 1 or 2");

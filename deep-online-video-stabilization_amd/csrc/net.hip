@@ -697,7 +697,28 @@ int stabnet_net_create(void** out, int N, int H, int W, int in_ch, int n_theta, 
     SN_REQUIRE(out != nullptr, "net_create: null out");
     SN_REQUIRE(N > 0 && N <= 4096 && H >= 32 && W >= 32 && in_ch > 0 && in_ch <= 64 && n_theta > 0,
                "net_create: bad shape N=%d H=%d W=%d in_ch=%d n_theta=%d (H,W >= 32)", N, H, W, in_ch, n_theta);
-    *out = build_net(N, H, W, in_ch, n_theta, keep_activations);
+    Net* net = build_net(N, H, W, in_ch, n_theta, keep_activations);
+    // Every conv step inside the range the kernels address (conv.h, SN_CONV_EXTENT_LIMIT), judged on the plain plan: the operand modes
+    // and the fusions (unit pairs, back-to-back) change which kernel reads a buffer, never the buffer, and the one limit is the tightest
+    // of all families.  For a training plan this covers what wgrad_launch_g() would refuse in the middle of a backward pass (its tensors
+    // are these, held to 2^31 there), the dgrad launches (the same tensors with the roles swapped) and the lockstep pair launches, which
+    // build_net() admits only below the same limit over both towers (Step::pair_ok).
+    for (size_t i = 0; i < net->plain_steps.size(); ++i) {
+        const Step& s = net->plain_steps[i];
+        if (s.kind != S_CONV) continue;
+        long ext = 0;
+        const char* over = conv_extent_over(s.conv, s.in_base + (long)s.in_floats - s.in_off, s.res_off >= 0, &ext);
+        if (over == nullptr) continue;
+        std::string layer = "?";
+        for (const ParamEntry& e : net->params)
+            if (e.kind == PK_CONV_W && (long)e.off == s.w_off) layer = e.name.substr(0, e.name.rfind('/'));
+        if (s.fvec_off >= 0) layer += "|conv1";            // the merged launch: one buffer [M][depth + dbn], which conv2 reads with x_ld = depth + dbn
+        stabnet_set_error("net_create: N=%d H=%d W=%d: the %s of %s (plan step %zu) spans %ld floats; every conv operand must stay below 2^30 floats "
+                          "(all x_ld / res_ld columns counted): lower the batch or the frame size", N, H, W, over, layer.c_str(), i, ext);
+        delete net;
+        return STABNET_ERR_BAD_ARG;
+    }
+    *out = net;
     return STABNET_OK;
 }
 

@@ -66,7 +66,9 @@ int stabnet_interp_fwd(const float* im, const float* x, const float* y, int N, i
  * Ho = (H + 2 pad - KH)/stride + 1.   A-operand prologue (both or neither): a = relu(a*in_scale[c] + in_shift[c]),
  * applied to in-frame pixels only (padding stays 0).  Epilogue: + bias[n] (or NULL), + residual (or NULL; NHWC
  * [N,res_H,res_W,Cout] read at (oy*res_stride, ox*res_stride) -- slim's `subsample` identity shortcut), relu if
- * relu_out.  Arithmetic: exact float32 MFMA, fp32 accumulate.  workspace: stabnet_conv2d_workspace_bytes(). */
+ * relu_out.  Arithmetic: exact float32 MFMA, fp32 accumulate.  workspace: stabnet_conv2d_workspace_bytes().
+ * Range: input (over the zero-padded frame), output, weights and the residual's own [N,res_H,res_W,Cout] frame each span fewer than 2^30
+ * floats (STABNET_ERR_BAD_ARG otherwise). */
 size_t stabnet_conv2d_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 /* Tuning hook (tools/autotune.py): force tile (0 128x128, 1 128x64, 2 64x64; < 0 = built-in choice) and split-K. */
 void stabnet_conv_tuning_override(int tile, int splitk);
@@ -109,7 +111,10 @@ int stabnet_conv2d_fwd_packed(const float* x, const float* w_ohwi, const float* 
                               size_t workspace_bytes, void* stream);
 /* stabnet_conv2d_fwd_packed on an input whose pixels lie x_ld floats apart (0 = Cin; else a multiple of 4 >= Cin): Cin columns of a
  * wider buffer, as the inference plan's conv2 layers read conv1's columns of the merged shortcut | conv1 buffer.  Geometries the ring
- * and packed kernels do not take (the register-staged path) need x_ld == Cin. */
+ * and packed kernels do not take (the register-staged path) need x_ld == Cin.
+ * Range: every operand of the launch -- input, output, residual, weights -- must span fewer than 2^30 floats from its pointer, all
+ * x_ld / res_ld columns of every pixel counted (the kernels address with 32-bit offsets); refused with STABNET_ERR_BAD_ARG before the
+ * pointers are looked at. */
 int stabnet_conv2d_fwd_packed_ld(const float* x, int x_ld, const float* w_ohwi, const float* w_img, const float* bias, const float* in_scale,
                                  const float* in_shift, const float* residual, int res_H, int res_W, int res_stride,
                                  const float* out_scale, const float* out_shift, float* y, int N, int H, int W, int Cin,
@@ -128,7 +133,10 @@ int stabnet_conv_last_launch_kind(void);
  * bit-identical to stabnet_conv2d_fwd_packed of the two convolutions one after the other (splitk = 1).  x [N,H,W,K1], residual
  * [N,H,W,N1] with res_ld floats between pixels (0 = N1); w3_img / w1_img = stabnet_conv_weight_split_image of the weights (w3_img may
  * be null for K1 = 64, which multiplies the float32 weights).  K1 a multiple of 64 up to 256 (not 256 with N2 = 64), N1 a multiple
- * of 128, N2 64 or 128, pre_shift behind pre_scale within 4 GiB (one buffer); STABNET_ERR_BAD_ARG otherwise. */
+ * of 128, N2 64 or 128, pre_shift behind pre_scale within 4 GiB (one buffer); STABNET_ERR_BAD_ARG otherwise.
+ * Range: every operand of the launch -- input, output, residual, weights -- must span fewer than 2^30 floats from its pointer, all
+ * x_ld / res_ld columns of every pixel counted (the kernels address with 32-bit offsets); refused with STABNET_ERR_BAD_ARG before the
+ * pointers are looked at. */
 int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float* w3_img, const float* bias3, const float* residual, int res_ld,
                                const float* pre_scale, const float* pre_shift, const float* w1_ohwi, const float* w1_img, const float* out_scale,
                                const float* out_shift, float* y3, float* y1, int N, int H, int W, int K1, int N1, int N2, int relu_out, void* stream);
@@ -138,7 +146,10 @@ int stabnet_conv_unit_pair_fwd(const float* x, const float* w3_ohwi, const float
  * epilogue: y = act((conv3 + bias3 + residual) * out_scale + out_shift).  The C-channel intermediate never reaches memory (a
  * workgroup keeps its activated 64-pixel tile in LDS and feeds the 1x1 GEMM from there).  x [N,H,W,C] with x_ld floats between
  * pixels (0 = C); residual read at (oy*res_stride, ox*res_stride) with res_ld floats between pixels (0 = Cout); y [N,Ho,Wo,Cout].
- * No workspace.  STABNET_ERR_BAD_ARG for other geometries (use two stabnet_conv2d_fwd_ex calls). */
+ * No workspace.  STABNET_ERR_BAD_ARG for other geometries (use two stabnet_conv2d_fwd_ex calls).
+ * Range: every operand of the launch -- input, output, residual, weights -- must span fewer than 2^30 floats from its pointer, all
+ * x_ld / res_ld columns of every pixel counted (the kernels address with 32-bit offsets); refused with STABNET_ERR_BAD_ARG before the
+ * pointers are looked at. */
 int stabnet_conv3x3_conv1x1_fwd(const float* x, int x_ld, const float* w2_ohwi, const float* mid_scale, const float* mid_shift,
                                 const float* w3_ohwi, const float* bias3, const float* residual, int res_H, int res_W,
                                 int res_stride, int res_ld, const float* out_scale, const float* out_shift, float* y, int N, int H,
@@ -154,7 +165,10 @@ int stabnet_conv3x3_conv1x1_fwd(const float* x, int x_ld, const float* w2_ohwi, 
  * the first stabnet_net_trainable_floats() floats are the trainables.  Conv weights are OHWI with Cin padded to 16,
  * FC weights [out][in]; stabnet_net_param_info() gives name (TF variable name under stable_net/resnet/), offset,
  * kind (0 conv w, 1 conv bias, 2 gamma, 3 beta, 4 moving_mean, 5 moving_variance, 6 FC w, 7 FC bias), dims, aux
- * (conv: un-padded Cin). */
+ * (conv: un-padded Cin).
+ * Range: stabnet_net_create() refuses (STABNET_ERR_BAD_ARG, the message names the layer, the operand and its extent) a shape in which any
+ * convolution's input, output, residual or weights would span 2^30 floats or more from its pointer, all x_ld / res_ld columns of the
+ * merged buffers counted -- the range the conv kernels address with 32-bit offsets, in every operand mode and fusion, forward and backward. */
 int stabnet_net_create(void** net, int N, int H, int W, int in_ch, int n_theta, int keep_activations);
 void stabnet_net_destroy(void* net);
 /* Conv operand mode of the inference forward (tensors are float32 in memory and accumulation is float32 in every mode):
