@@ -17,6 +17,12 @@ its published algorithm and flagged `[external]`:
   * tf.contrib.slim.nets.resnet_v2.resnet_v2_50 / batch_norm / max_pool2d / fully_connected
   * tf.round = round-half-to-even; float->int32 cast with x86 cvttss2si semantics
 
+PINNED BY EXECUTION since oracle/run_reference.py: the warp and loss functions below (get_4_pts, get_Hs .. transformer, _interpolate /
+interpolate, get_black_pos, the distortion / consistency / feature / image losses, warp_pts, the tower from theta on) are compared with the
+reference's own text run on an eager NumPy stand-in for its tf.* ops (tests/test_reference_run_cpu.py): bit for bit, reductions within a
+float32 summation bar.  inv8_partial_piv_lu is what that run uses for tf.matrix_inverse, so it stays an assumption; the backbone, Adam
+and the script bodies (train_bundle_nobm.py, deploy_bundle.py, get_data_mini_after.py) stay restatements.
+
 All arithmetic is float32 with one rounding per TF op (TF 1.3 CPU wheels are built
 without FMA, and every elementwise TF op is its own kernel), so the HIP warp path can
 be compared bit-for-bit.

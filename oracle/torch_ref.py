@@ -4,6 +4,8 @@ TEST INFRASTRUCTURE ONLY (same rules as stabnet_oracle.py; parity unpinned for t
 defines the forward values; this file exists because the reference differentiates its graph with TF autodiff
 (`opt.minimize(total_loss)`, train_bundle_nobm.py:160) and the HIP backward kernels need an independent gradient to
 be checked against.  tests/test_oracle_cpu.py checks this file's forward against stabnet_oracle.py.
+tests/test_reference_run_cpu.py checks it (under `constants(np.float64)`) against the reference's own warp and loss text evaluated in float64
+(oracle/run_reference.py): values to 1e-12, decisions outright, and its autograd gradient against central differences of that text.
 
 Autodiff conventions reproduced (they decide the gradient): floor / int casts / comparisons carry no gradient, so
 sampler corners, `black_pix`, `warp_pts` indices and the z-sign are constants; clip_by_value / minimum / maximum pass
@@ -20,6 +22,7 @@ the corners of `interpolate(., flow)`) are taken in float32 here, as the referen
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
@@ -29,6 +32,33 @@ import torch.nn.functional as Fnn
 from . import stabnet_oracle as O
 
 DT = torch.float64
+
+# The graph's constants -- the crop limit 1 / do_crop_rate, the ridge 1e-4, the z offset 1e-8 and the linspace grid -- are float32 values
+# in the reference's graph, and by default they are taken as those float32 values here (this file shadows the float32 graph in exact
+# arithmetic).  `with constants(np.float64):` takes them in float64 instead, which is how the reference's own text evaluates when it is
+# run in float64 (oracle/run_reference.py, mode f64); the two differ by 1e-8 relative in the maps, far below every float32 bar.
+CONST = np.float32
+
+
+def _c(v):
+    return float(CONST(v))
+
+
+@contextlib.contextmanager
+def constants(dtype):
+    global CONST
+    old, CONST = CONST, dtype
+    try:
+        yield
+    finally:
+        CONST = old
+
+
+def _linspace(n):
+    """tf.linspace(-1.0, 1.0, n) in the constants' type: start + i * ((stop - start) / (n - 1))."""
+    if CONST is np.float32:
+        return torch.tensor(O.linspace_tf(-1.0, 1.0, n), dtype=DT)
+    return torch.tensor(-1.0 + (2.0 / (n - 1)) * np.arange(n, dtype=np.float64), dtype=DT)
 
 
 def t(x, requires_grad=False):
@@ -41,7 +71,7 @@ def get_4_pts(theta, cfg):
     gh, gw = cfg.grid_h, cfg.grid_w
     # the limit is a float32 value of the reference's graph (1 / 0.8 rounds to 1.25 there), and tf.clip_by_value passes the whole
     # gradient to a vertex that sits exactly on it: torch.clamp does the same, torch.minimum / maximum would halve it at the tie
-    lim = float(np.float32(1.0) / np.float32(cfg.do_crop_rate))
+    lim = float(CONST(1.0) / CONST(cfg.do_crop_rate))
     base = torch.tensor([[[j * (2.0 / gw) - 1, i * (2.0 / gh) - 1] for j in range(gw + 1)] for i in range(gh + 1)], dtype=DT)
     pts2 = base[None] + theta.reshape(N, gh + 1, gw + 1, 2)
     pts2 = torch.clamp(pts2, -lim, lim)
@@ -56,7 +86,7 @@ def get_Hs(pts2, cfg):
     gh, gw = cfg.grid_h, cfg.grid_w
     h, w = 2.0 / gh, 2.0 / gw
     out = []
-    ridge = torch.eye(8, dtype=DT) * float(np.float32(1e-4))
+    ridge = torch.eye(8, dtype=DT) * _c(1e-4)
     for i in range(gh):
         for j in range(gw):
             hh, ww = i * h - 1, j * w - 1
@@ -81,6 +111,15 @@ def get_Hs(pts2, cfg):
     return torch.stack(out, dim=1).reshape(N, gh, gw, 9)
 
 
+def _floor_i32(v):
+    """tf.cast(tf.floor(v), 'int32') as the reference's x86 host computes it (spatial_transformer3.py:85,87): a value outside the int32
+    range, or NaN, becomes INT_MIN (cvttss2si / cvttsd2si) -- it does NOT saturate -- so a coordinate beyond +2^31 pixels clips to tap 0,
+    not to the last one.  -> int64 tensor."""
+    f = torch.floor(v)
+    ok = (f >= -2.0 ** 31) & (f < 2.0 ** 31)
+    return torch.where(ok, f, torch.full_like(f, -2.0 ** 31)).long()
+
+
 def _sample(im, x, y, corners=None):
     """spatial_transformer3.py:62-123; im [N,H,W,C]; x,y [N,H,W] -> [N,H,W,C].
     corners = (x0, y0, x1, y1) clipped int arrays: the (non-differentiable) floor decisions taken in float32 by the
@@ -92,8 +131,7 @@ def _sample(im, x, y, corners=None):
         if corners is not None:
             x0, y0, x1, y1 = [torch.as_tensor(np.asarray(c).reshape(N, H, W).astype(np.int64)) for c in corners]
         else:
-            x0 = torch.floor(xp).clamp(-2 ** 31, 2 ** 31 - 1).long()
-            y0 = torch.floor(yp).clamp(-2 ** 31, 2 ** 31 - 1).long()
+            x0, y0 = _floor_i32(xp), _floor_i32(yp)
             x1, y1 = x0 + 1, y0 + 1
             x0, x1 = x0.clamp(0, W - 1), x1.clamp(0, W - 1)
             y0, y1 = y0.clamp(0, H - 1), y1.clamp(0, H - 1)
@@ -116,16 +154,15 @@ def corners_f32(x, y, H, W):
     y = np.asarray(y, np.float32)
     xp = (x + np.float32(1.0)) * np.float32(W) / np.float32(2.0)
     yp = (y + np.float32(1.0)) * np.float32(H) / np.float32(2.0)
-    x0 = np.clip(np.floor(xp), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
-    y0 = np.clip(np.floor(yp), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+    x0 = O.cast_i32_x86(np.floor(xp)).astype(np.int64)
+    y0 = O.cast_i32_x86(np.floor(yp)).astype(np.int64)
     return (np.clip(x0, 0, W - 1), np.clip(y0, 0, H - 1), np.clip(x0 + 1, 0, W - 1), np.clip(y0 + 1, 0, H - 1))
 
 
 def _own_corners(x, y, H, W):
     xp = (x.detach() + 1.0) * W / 2.0
     yp = (y.detach() + 1.0) * H / 2.0
-    x0 = torch.floor(xp).clamp(-2 ** 31, 2 ** 31 - 1).long()
-    y0 = torch.floor(yp).clamp(-2 ** 31, 2 ** 31 - 1).long()
+    x0, y0 = _floor_i32(xp), _floor_i32(yp)
     return tuple(a.numpy() for a in (x0.clamp(0, W - 1), y0.clamp(0, H - 1), (x0 + 1).clamp(0, W - 1), (y0 + 1).clamp(0, H - 1)))
 
 
@@ -135,8 +172,8 @@ def transformer(U, pts2, cfg, corners=None, black=None, record=None):
     N, H, W, C = U.shape
     gh, gw = cfg.grid_h, cfg.grid_w
     Hs = get_Hs(pts2, cfg)
-    xs = torch.tensor(O.linspace_tf(-1.0, 1.0, W), dtype=DT)
-    ys = torch.tensor(O.linspace_tf(-1.0, 1.0, H), dtype=DT)
+    xs = _linspace(W)
+    ys = _linspace(H)
     rows, cols = O.cell_bounds(H, W, gh, gw)
     xrows = []
     yrows = []
@@ -150,7 +187,7 @@ def transformer(U, pts2, cfg, corners=None, black=None, record=None):
             ty = h[:, 3] * gx + h[:, 4] * gy + h[:, 5]
             tz = h[:, 6] * gx + h[:, 7] * gy + h[:, 8]
             sign = torch.where(tz >= 0, 1.0, -1.0).detach()
-            tz = tz + sign * float(np.float32(1e-8))
+            tz = tz + sign * _c(1e-8)
             xr.append(tx / tz)
             yr.append(ty / tz)
         xrows.append(torch.cat(xr, dim=2))
@@ -178,7 +215,7 @@ def interpolate(im, x, y, corners=None):
 
 # ---- losses ------------------------------------------------------------------------------------------------
 def get_black_pos(pts1, cfg):
-    lim = float(np.float32(1.0) / np.float32(cfg.do_crop_rate))       # the float32 limit of get_4_pts
+    lim = float(CONST(1.0) / CONST(cfg.do_crop_rate))       # the float32 limit of get_4_pts
     z = torch.zeros((), dtype=DT)
     e = torch.where(pts1 > lim, pts1 - lim, z) + torch.where(-lim > pts1, -lim - pts1, z)
     return e.reshape(pts1.shape[0], -1)

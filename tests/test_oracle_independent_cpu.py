@@ -10,7 +10,15 @@ oracle/torch_ref.py, which shares structure with it), on different libraries:
   clip       the committed 256x256 trajectory (tests/golden/clip_256x256_t64.npz)
 
 None of this pins the oracle to TensorFlow's outputs; it shows two independent readings of the same published
-algorithms agree."""
+algorithms agree.
+
+What IS pinned by execution since tests/test_reference_run_cpu.py: the reference's own warp and loss text (transformer, interpolate,
+get_4_pts, get_black_pos, the distortion / consistency / feature / image / id2 losses, warp_pts, the tower's gated total), run on an
+eager NumPy stand-in for its tf.* ops -- the oracle is bit for bit that run, torch_ref within 1e-12 of its float64 evaluation.
+What still is NOT, and rests on this file and on reading: tf.matrix_inverse's pivoting (the stand-in borrows inv8_partial_piv_lu, so
+the 8x8 LU check below is the only independent evidence for it) and the slim backbone; Adam; the temporal-loss and optimiser wiring
+in the body of train_bundle_nobm.py; the deploy_bundle.py loop and its crop search (script bodies, not functions);
+get_data_mini_after.py (needs cv2)."""
 import os
 import zlib
 
